@@ -13,18 +13,25 @@ ceil(reads/N)*r .. (sharding.shard_range); --scaling weak: every rank maps its o
 data-path collective either way; the only exchange is one integer per rank that chains the tie-break RNG
 stream in input order.
 
-Launch:  python bench.py [--gpus 1] [--steps K] [--warmup W]
+A plain run sets up, warms up, times the K steps and prints the JSON line (value, ms_per_step, the per-kernel and per-stage times
+of the timed steps).  --full adds everything that takes runs of its own: the counting pass and the kernel alone (roofline, kstats),
+the steps one after the other (pipeline1), the drain of smaller launches, hit statistics, the CPU baseline with its parity sample
+and the e2e ps_map calls.  --dump-outputs DIR saves the per-read records of the last timed step (a fixed sample, float64 .npy).
+
+Launch:  python bench.py [--gpus 1] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
          python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 """
 import argparse
 import json
 import os
+import shutil
 import sys
 import tempfile
 import time
 
 import numpy as np
 
+T_START = time.time()
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(ROOT, "para-suite_amd"))
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
@@ -147,22 +154,25 @@ def add_repeats(torch, dev, contigs, seed, share=0.45, info=None, satellite_reps
 
 
 def write_fasta(path, contigs, width=50):
-    lut = np.frombuffer(b"ACGTN", dtype=np.uint8)
+    """letters and line breaks are laid out where the codes live (the device, for gen_genome's contigs): a host-side table
+    lookup over 3.1 Gbp took most of the set-up time of a bench run"""
     with open(path, "wb") as f:
         for name, codes in contigs:
             f.write(b">" + name.encode() + b"\n")
             n = codes.numel()
             for a in range(0, n, 50_000_000):
                 b = min(n, a + 50_000_000)
-                asc = lut[codes[a:b].cpu().numpy()]
-                full = asc.size // width * width
+                c = codes[a:b]
+                # A C G T N = 65 67 71 84 78, elementwise: no gather (large indexing calls are avoided on this stack, gen_genome)
+                asc = (c >= 1).to(c.dtype) * 2 + (c >= 2).to(c.dtype) * 4 + (c >= 3).to(c.dtype) * 13 - (c >= 4).to(c.dtype) * 6 + 65
+                full = asc.numel() // width * width
                 if full:
-                    body = np.empty((full // width, width + 1), dtype=np.uint8)
-                    body[:, :width] = asc[:full].reshape(-1, width)
+                    body = asc.new_empty((full // width, width + 1))
+                    body[:, :width] = asc[:full].view(-1, width)
                     body[:, width] = 10
-                    f.write(body.tobytes())
-                if full < asc.size:
-                    f.write(asc[full:].tobytes() + b"\n")
+                    f.write(body.cpu().numpy())
+                if full < asc.numel():
+                    f.write(asc[full:].cpu().numpy().tobytes() + b"\n")
 
 
 def gen_reads(torch, dev, contigs, n_reads, L, seed, bound=0.6, indels=True):
@@ -264,6 +274,23 @@ def write_java_profile(prefix, P, ins, dele):
     return prefix + ".errorprofile", prefix + ".indelprofile"
 
 
+DUMP_READS = 200_000        # 31 float64 columns x 200,000 reads = 49.6 MB, under the 64 MB a dump may take
+
+
+def dump_outputs(d, hits, first_read, share, suffix=""):
+    """what the timed path hands its caller -- the per-read records of ps_batch_hits -- for a fixed sample of the reads (seeded:
+    the same reads in every run with the same arguments), every field as float64 (exact for all of them): <field>.npy, CIGAR words
+    as an [n, 16] array, and read_index.npy, the sampled reads' places in the job's input order"""
+    os.makedirs(d, exist_ok=True)
+    n = len(hits)
+    k = min(n, max(1, DUMP_READS // share))
+    idx = np.sort(np.random.default_rng(0x5EED0004).choice(n, k, replace=False)) if k < n else np.arange(n)
+    sel = hits[idx]
+    np.save(os.path.join(d, "read_index%s.npy" % suffix), (idx + first_read).astype(np.float64))
+    for f in sel.dtype.names:
+        np.save(os.path.join(d, "%s%s.npy" % (f, suffix)), sel[f].astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -271,7 +298,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--reads", type=int, default=10_000_000, help="reads of the job (--scaling strong: shared by the ranks; weak: per GPU)")
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong", help="N>1: strong = --reads in all, contiguous range per rank (BASELINE configs[3]); weak = --reads per GPU")
-    ap.add_argument("--drain", type=int, default=1, help="N=1: also time single launches of 1/8, 1/4, 1/2 of the batch (what a rank of a 8/4/2-GPU strong-scaling job would run)")
+    ap.add_argument("--drain", type=int, default=1, help="N=1, --full: also time single launches of 1/8, 1/4, 1/2 of the batch (what a rank of a 8/4/2-GPU strong-scaling job would run)")
     ap.add_argument("--read-len", type=int, default=50)
     ap.add_argument("--genome-mbp", type=int, default=3100)
     ap.add_argument("--contigs", type=int, default=24)
@@ -279,7 +306,7 @@ def main():
                     help="repeats: ~45 %% of the genome in interspersed repeat families (300-bp and 6-kb units, 2-20 %% diverged), microsatellites and "
                          "satellite arrays (add_repeats) instead of an i.i.d. text with 4 %% two-copy segments")
     ap.add_argument("--workload", choices=["full", "exact"], default="full")
-    ap.add_argument("--cpu-sample", type=int, default=250000, help="reads of the same workload timed on the CPU oracle (0 = skip)")
+    ap.add_argument("--cpu-sample", type=int, default=250000, help="--full: reads of the same workload timed on the CPU oracle (0 = skip)")
     ap.add_argument("--threads", type=int, default=0)
     ap.add_argument("--penalty", choices=["profile", "stock"], default="profile", help="full workload: PAR-CLIP error-profile costs (bwa parasuite) or stock costs (bwa aln -n 0.04)")
     ap.add_argument("--sub-batches", type=int, default=1, help="2: the batch of a step is mapped as two halves on two lanes (streams) driven by two threads; measured slower than 1 (DESIGN.md section 5)")
@@ -288,12 +315,18 @@ def main():
                     "so that it takes the CUs step k's retiring workgroups leave (tools/backfill_probe.py, tools/pipeline_probe.py).  0 (default) = 2: three in "
                     "flight were measured slower than two at every batch size (1.25 M reads: 280 against 232 ms per step; 10 M: 1230 against 1228)")
     ap.add_argument("--stagger-ms", type=float, default=-1.0, help="pipelined steps: how long a search launch has the GPU to itself before the next step is started (default: 50 ms per 10 M reads)")
-    ap.add_argument("--e2e", type=int, default=1, help="N=1: also time one ps_map call, FASTQ file -> closed SAM file (the reference's own timer scope)")
+    ap.add_argument("--e2e", type=int, default=1, help="N=1, --full: also time one ps_map call, FASTQ file -> closed SAM file (the reference's own timer scope)")
     ap.add_argument("--dump-hits", default="", help="directory: every rank saves the per-read hit records of its last step (tests)")
+    ap.add_argument("--dump-outputs", default="", help="directory: after the timed steps, the per-read records of the last step for a fixed sample of "
+                    "the reads, one float64 <field>.npy each (rank r > 0 of N > 1: <field>_rank<r>.npy)")
+    ap.add_argument("--full", action="store_true", help="also what takes runs of its own: counting pass and kernel alone (roofline, kstats), pipeline1, "
+                    "drain, hit statistics, CPU baseline + parity sample, e2e ps_map calls.  Without it the run only sets up, warms up and times the steps")
     ap.add_argument("--keep", default="")
     ap.add_argument("--share-gpu", action="store_true", help="rehearsal: all ranks use GPU 0")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="gloo: rehearsal of the N>1 path (index staged through the host)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import threading
     import torch
@@ -319,7 +352,7 @@ def main():
     log = (lambda *a: print("[bench r%d]" % rank, *a, file=sys.stderr, flush=True))
     S = 2 if args.sub_batches >= 2 else 1
     PIPE = 0                                                   # set below, once the rank's share of the reads is known
-    do_e2e = bool(args.e2e) and world == 1
+    do_e2e = args.full and bool(args.e2e) and world == 1
 
     # ---------------- data: genome on every rank (same seed), index built on rank 0 ----------------
     t0 = time.time()
@@ -525,6 +558,7 @@ def main():
                 b.search()
     run_steps(args.warmup)
     sync()
+    log("set-up and %d warm-up step(s) done %.1fs after start" % (args.warmup, time.time() - T_START))
     for k in wall:
         wall[k] = 0.0
     acc = {}
@@ -540,12 +574,47 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    K = args.steps
+    last = sets[(K - 1) % PIPE]                               # the batch the last timed step ran on
     if args.dump_hits:
         os.makedirs(args.dump_hits, exist_ok=True)
-        last = sets[(max(1, args.steps) - 1) % PIPE]          # the batch the last timed step ran on
         np.save(os.path.join(args.dump_hits, "hits_rank%d.npy" % rank), np.concatenate([b.hits() for b in last]))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, np.concatenate([b.hits() for b in last]), lo if strong else 0, world,
+                     "" if world == 1 else "_rank%d" % rank)
     if rank == 0:
-        K = max(1, args.steps)
+        res = {
+            "metric": "aligned reads/sec (10Mx50bp PAR-CLIP vs hg19-size genome) on MI355X; SAM bit-exact vs own CPU restatement (parity unpinned)",
+            "value": (args.reads if strong else world * args.reads) * args.steps / elapsed,
+            "unit": "reads/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": 1e3 * elapsed / K,
+            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
+            "dtype": "u64", "data": "synthetic",
+            "config": {"workload": "%s: %dx%dbp simulated PAR-CLIP reads %s, %s, vs %d Mbp synthetic genome "
+                                   "(hg19-size synthetic genome; 33-bit BWT rows)" % (
+                                   "configs[2]" if world == 1 else ("configs[3]" if strong else "configs[2] per GPU"), args.reads, args.read_len,
+                                   "in all, contiguous ranges of ceil(reads/%d) per GPU" % world if strong else "per GPU",
+                                   "error-profile seed + banded extension" if args.workload == "full" else "exact-match seed only",
+                                   args.genome_mbp),
+                       "reads_total": args.reads if strong else world * args.reads,
+                       "reads_per_gpu": -(-args.reads // world) if strong else args.reads, "read_len": args.read_len, "genome_mbp": args.genome_mbp,
+                       "genome_profile": args.genome_profile,
+                       "mode": args.workload, "penalty": args.penalty, "sub_batches": S, "pipeline": PIPE,
+                       "parallelism": "reads sharded x%d, index replicated" % world},
+            "value_scope": "search + samse stages on reads already packed in HBM -> per-read alignment records in pinned host memory "
+                           "(FASTQ parsing, upload and SAM text are outside; see value_e2e, --full)",
+            "kernels_ms_per_step": {k: acc[k] / K for k in ("ms_width", "ms_backtrack", "ms_select", "ms_sa2pos",
+                                                            "ms_refine", "ms_host_post", "ms_classify", "ms_sel_hard", "ms_sel_easy")},
+            "stage_wall_ms_per_step": {k: 1e3 * v / K for k, v in wall.items()},
+            "note_pipelined_timings": ("config.pipeline = 2: the per-stage and per-kernel times above are taken on steps that overlap in time -- ms_backtrack "
+                                       "there brackets the launch's wait for free CUs as well, stage walls add up to more than ms_per_step; the kernel alone is "
+                                       "roofline.avg_launch_ms (--full)") if PIPE > 1 else None,
+            "overflow_reads": [int(acc["n_overflow_tier1"] / K), int(acc["n_overflow_tier2"] / K)],
+        }
+        if not args.full:
+            print(json.dumps(res), flush=True)
+    if rank == 0 and args.full:
         # ---- counters: the timed kernel carries none.  One more, untimed pass of the search stage with the counting kernel,
         # one sub-batch at a time (nothing overlaps: these launch durations are the kernel alone); the counts of a batch are the
         # same in every pass (the search is deterministic)
@@ -633,27 +702,7 @@ def main():
         launches_per_step = (n_bt if dominant_bt else max(1, acc["n_width_launches"])) / K
         ach = (alg_bt / (ms_bt_union_step * 1e-3) if dominant_bt else alg_w / (ms_w_step * 1e-3)) / 1e9
         hits = np.concatenate([b.hits() for b in batches])
-        res = {
-            "metric": "aligned reads/sec (10Mx50bp PAR-CLIP vs hg19-size genome) on MI355X; SAM bit-exact vs own CPU restatement (parity unpinned)",
-            "value": (args.reads if strong else world * args.reads) * args.steps / elapsed,
-            "unit": "reads/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / K,
-            "higher_is_better": True, "scaling": args.scaling, "vs_baseline": None,
-            "dtype": "u64", "data": "synthetic",
-            "config": {"workload": "%s: %dx%dbp simulated PAR-CLIP reads %s, %s, vs %d Mbp synthetic genome "
-                                   "(hg19-size synthetic genome; 33-bit BWT rows)" % (
-                                   "configs[2]" if world == 1 else ("configs[3]" if strong else "configs[2] per GPU"), args.reads, args.read_len,
-                                   "in all, contiguous ranges of ceil(reads/%d) per GPU" % world if strong else "per GPU",
-                                   "error-profile seed + banded extension" if args.workload == "full" else "exact-match seed only",
-                                   args.genome_mbp),
-                       "reads_total": args.reads if strong else world * args.reads,
-                       "reads_per_gpu": -(-args.reads // world) if strong else args.reads, "read_len": args.read_len, "genome_mbp": args.genome_mbp,
-                       "genome_profile": args.genome_profile,
-                       "mode": args.workload, "penalty": args.penalty, "sub_batches": S, "pipeline": PIPE,
-                       "parallelism": "reads sharded x%d, index replicated" % world},
-            "value_scope": "search + samse stages on reads already packed in HBM -> per-read alignment records in pinned host memory "
-                           "(FASTQ parsing, upload and SAM text are outside; see value_e2e)",
+        res.update({
             "roofline": {"bound": "hbm", "kernel": "k_backtrack_n" if dominant_bt else "k_width",
                          "achieved": ach, "peak": 8000.0, "unit": "GB/s", "frac": ach / 8000.0, "traffic": None, "traffic_source": None,
                          "achieved_definition": "ALGORITHMIC bytes of the reference's algorithm (SURVEY.md 8d: 64 B per distinct Occ block of every search step, counted by "
@@ -689,18 +738,11 @@ def main():
                                             frac=alg_bt / (pipe1["kernel_ms_per_step"] * 1e-3) / 1e9 / 8000.0,
                                             note="the same batch, steps one after the other right after the timed region (what `bench.py --pipeline 1` times): "
                                                  "HIP events around every launch, inside the region, nothing overlapping") if pipe1 and dominant_bt else None)},
-            "kernels_ms_per_step": {k: acc[k] / K for k in ("ms_width", "ms_backtrack", "ms_select", "ms_sa2pos",
-                                                            "ms_refine", "ms_host_post", "ms_classify", "ms_sel_hard", "ms_sel_easy")},
-            "stage_wall_ms_per_step": {k: 1e3 * v / K for k, v in wall.items()},
-            "note_pipelined_timings": ("config.pipeline = 2: the per-stage and per-kernel times above are taken on steps that overlap in time -- ms_backtrack "
-                                       "there brackets the launch's wait for free CUs as well, stage walls add up to more than ms_per_step; the kernel alone is "
-                                       "roofline.avg_launch_ms") if PIPE > 1 else None,
             "kstats": {"backtrack": ks_bt, "width": ks_w, "sa2pos": ks_sa, "backtrack_timed_kernel": ks_timed},
             "mapped_frac": float((hits["type"] != 0).mean()),
             "x0_gt1_frac": float((hits["c1"] > 1).mean()), "x0_gt30_frac": float((hits["c1"] > 30).mean()),
-            "overflow_reads": [int(acc["n_overflow_tier1"] / K), int(acc["n_overflow_tier2"] / K)],
             "drain": drain,
-        }
+        })
         # HBM traffic of the dominant kernel: PMC passes cannot run inside the timed job, so the committed passes of
         # the same configuration are quoted (profiles/pmc_traffic.json), null when none matches
         try:
@@ -850,6 +892,8 @@ def main():
     if world > 1:
         dist.barrier()
         dist.destroy_process_group()
+    if not args.keep:
+        shutil.rmtree(tmpdir, ignore_errors=True)           # the 3 GB FASTA (and with --full the index files, FASTQ, SAM) of this run
 
 
 if __name__ == "__main__":

@@ -76,12 +76,11 @@ def test_java_double_to_string():
 
 
 def test_reference_example_profile_is_readable():
-    """the reference's own example profile (hand-written input of its simulator: "0.990" style values, no trailing tab), when the
-    tree is there -- it never travels to the GPU box: the reader the mapping step uses takes it as 16 numbers"""
+    """the reference's own example profile (hand-written input of its simulator: "0.990" style values, no trailing tab; kept as
+    tests/golden/example.errorprofile, a copy of its examples/simulation/example.errorprofile): the reader the mapping step uses
+    takes it as 16 numbers"""
     import ctypes as C
-    p = "/root/reference/examples/simulation/example.errorprofile"
-    if not os.path.exists(p):
-        pytest.skip("reference tree not present")
+    p = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "example.errorprofile")
     P = (C.c_double * 16)()
     a, b = C.c_double(), C.c_double()
     assert orc.lib().orc_read_profile_files(p.encode(), None, P, C.byref(a), C.byref(b)) == 0

@@ -31,7 +31,7 @@ def test_two_ranks_bench_rehearsal(tmp_path, mode):
     mbp, n_reads = 8, 60000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", {"sub_batches": "29655", "pipeline": "29657", "strong": "29659"}[mode], os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
-           "--genome-mbp", str(mbp), "--contigs", "4", "--reads", str(n_reads if mode != "strong" else 2 * n_reads + 1), "--cpu-sample", "0", "--dump-hits", dump]
+           "--genome-mbp", str(mbp), "--contigs", "4", "--reads", str(n_reads if mode != "strong" else 2 * n_reads + 1), "--cpu-sample", "0", "--dump-hits", dump, "--full"]
     cmd += ["--scaling", "strong" if mode == "strong" else "weak"]
     cmd += ["--steps", "1", "--warmup", "1", "--sub-batches", "2"] if mode == "sub_batches" else ["--steps", "4", "--warmup", "1"]
     r = subprocess.run(cmd, env=env, timeout=900, capture_output=True, text=True)

@@ -4,7 +4,7 @@
 #   tools/final_profiles.sh b   -> the other workloads (repeat-rich genome, stock costs, exact matching) and the ps_map timeline
 set -o pipefail
 out=gpurun_out/final; mkdir -p $out
-run() { name=$1; shift; timeout -k 10 500 python bench.py "$@" > $out/$name.json 2> $out/$name.err && python - $out/$name.json <<'PY'
+run() { name=$1; shift; timeout -k 10 500 python bench.py --full "$@" > $out/$name.json 2> $out/$name.err && python - $out/$name.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
 print(sys.argv[1].split("/")[-1], round(d["value"]), "reads/s,", round(d["ms_per_step"], 1), "ms/step, frac", round(d["roofline"]["frac"], 4), "kernel alone", round(d["roofline"]["avg_launch_ms"], 1), "e2e", d.get("t_e2e_s"), d.get("t_e2e_cold_s"), flush=True)

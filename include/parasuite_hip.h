@@ -149,6 +149,34 @@ int     ps_bam_index(const char *bam, int threads);
  * out_prefix NULL or "": the mapping file's name, as in the Java.  A read longer than max_read_len is an error (the
  * Java's arrays would overflow). */
 int     ps_error_profile(const char *mapping_sam_or_bam, const char *ref_fa, int max_read_len, const char *out_prefix);
+/* Everything `new ErrorProfiling(mapping, reference, maxReadLength).inferErrorProfile(infer_qualities, false)` writes -- the
+ * toolkit's `error MAPPING REF MAXLEN [-q true]` mode (Main.java:560-597), whose .qualities and .indels feed the PAR-CLIP
+ * simulator's quality_file / indel_file.  Same records, rules and reference as ps_error_profile, and:
+ *   <out_prefix>.errorprofile, .indelprofile  byte-identical to ps_error_profile with the same arguments
+ *   <out_prefix>.errorprofile.vcf   4 blocks (reference base A C G T) of 4 lines "<ref>\t<read>\t<count as Double.toString>",
+ *                                   a blank line after each block, :504-531
+ *   <out_prefix>.qualityPerMismatch 4 lines x 4 values "mean QUAL\t" (NaN: no pair), pairs of records whose CIGAR has no I
+ *                                   and no D, :379-390,438-447
+ *   <out_prefix>.indels             max_read_len lines "<ins rate>\t<del rate>" per read position (0.0 where no base), :553-579
+ *   <out_prefix>.qualities          max_read_len lines "<mean>\t<sd>" of QUAL per read position (NaN\tNaN where none), the
+ *                                   standard deviation summed in file order, :402-406,421-436; created empty when
+ *                                   infer_qualities == 0
+ * QUAL is Phred (SAM QUAL - 33, BAM bytes), indexed in SAM order and never reversed (:301 takes it before the reverse
+ * complement): column i of a reverse-strand record pairs its complemented bases with QUAL[i].  Where the Java throws, this
+ * does not, and counts the case in stats:
+ *   - deletion and N records with -q: the Java reads QUAL[width - 1] past the read (ArrayIndexOutOfBounds, uncaught); here
+ *     positions i < read length are booked;
+ *   - reverse-strand N records: their .qualityPerMismatch index can pass the read's end; those pairs are left out and
+ *     counted in n_qual_beyond_read;
+ *   - QUAL '*' (BAM 0xFF): the Java throws at the first quality; here the record adds nothing to the two quality files,
+ *     everything else as before, and is counted in n_without_qual (counted records that are not skipped);
+ *   - the Java sums .qualityPerMismatch in a 32-bit int (wraps near 10 M reads); here the sums are exact 64-bit.
+ * max_read_len 1..2028 with infer_qualities, 1..2254 without (the counting kernel's LDS, 160 KiB); a read longer than max_read_len is an error, as in
+ * ps_error_profile, and no file is written then. */
+typedef struct { uint64_t n_records, n_counted, n_unmapped, n_duplicate, n_start_zero, n_indel_reads, n_skipped,
+                 n_without_qual, n_qual_beyond_read; } ps_profile_stats;
+int     ps_error_profile_full(const char *mapping_sam_or_bam, const char *ref_fa, int max_read_len, const char *out_prefix,
+                              int infer_qualities, ps_profile_stats *stats /* may be NULL */);
 /* The first pass and its error profile in one call -- "fed directly from alignment results" (SURVEY.md §8f rank 4): ps_map, and
  * while the SAM is written the same records, straight from memory, go through the counting kernel: the alignments with
  * MAPQ >= min_mapq, i.e. what the pass's filtered BAM holds (samtools view -q, PARAsuiteMapping.java:124-133 /

@@ -44,7 +44,7 @@ EXPORTS = ["ps_version", "ps_last_error", "ps_index", "ps_map", "ps_ctx_open", "
            "ps_ctx_blob", "ps_ctx_meta", "ps_ctx_from_blobs", "ps_ctx_clone", "ps_ctx_fetch", "ps_ctx_export_blob", "ps_ctx_sa_lookup", "ps_ctx_index_check", "ps_sam_to_bam", "ps_map_to_bam", "ps_bam_view", "ps_bam_sort", "ps_bam_index", "ps_batch_from_fastq",
            "ps_batch_from_codes", "ps_batch_free", "ps_batch_n", "ps_batch_search", "ps_batch_select_hard",
            "ps_batch_select_easy", "ps_batch_locate", "ps_batch_run", "ps_batch_write_sam", "ps_batch_n_aln",
-           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_map_profiled", "ps_release_host_cache"]
+           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_map_profiled", "ps_release_host_cache"]
 
 _LIB = None
 
@@ -345,6 +345,21 @@ def ps_error_profile(mapping, ref_fa, max_read_len=101, out_prefix=None):
     """<out_prefix>.errorprofile / .indelprofile from the records of a SAM or BAM file (counted on the GPU)"""
     L = lib(); L.ps_error_profile.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
     _chk(L.ps_error_profile(mapping.encode(), ref_fa.encode(), int(max_read_len), out_prefix.encode() if out_prefix else None))
+
+
+class ProfileStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_records", "n_counted", "n_unmapped", "n_duplicate", "n_start_zero", "n_indel_reads",
+                                          "n_skipped", "n_without_qual", "n_qual_beyond_read")]
+
+
+def ps_error_profile_full(mapping, ref_fa, max_read_len=101, out_prefix=None, infer_qualities=False):
+    """all six files of ErrorProfiling.inferErrorProfile(infer_qualities, false): <out_prefix>.errorprofile, .indelprofile,
+    .errorprofile.vcf, .qualityPerMismatch, .indels, .qualities (empty without infer_qualities); returns the record counters"""
+    L = lib(); L.ps_error_profile_full.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(ProfileStats)]
+    st = ProfileStats()
+    _chk(L.ps_error_profile_full(mapping.encode(), ref_fa.encode(), int(max_read_len), out_prefix.encode() if out_prefix else None,
+                                 int(bool(infer_qualities)), C.byref(st)))
+    return {f: int(getattr(st, f)) for f, _ in ProfileStats._fields_}
 
 
 def ps_map_profiled(threads, mm, error_profile, indel_profile, ref_fa, reads, out_sam, min_mapq, max_read_len, profile_prefix):

@@ -619,7 +619,7 @@ void bam_index(const char *bam, int threads)
     write_bai(std::string(bam) + ".bai", d, lay);
 }
 
-void load_alignments(const char *path, int threads, AlnTable &out)
+void load_alignments(const char *path, int threads, AlnTable &out, bool with_qual)
 {
     threads = clamp_threads(threads);
     unsigned char mg[2] = {0, 0};
@@ -640,6 +640,7 @@ void load_alignments(const char *path, int threads, AlnTable &out)
         (void)w;
     }
     out.cigar.resize(ops); out.seq.assign((size_t)(bases / 2), 0);
+    if (with_qual) out.qual.assign((size_t)bases, 0xff);          // a record's padding base stays 0xFF
     par(threads, threads, [&](int t) {
         for (size_t i = (size_t)t; i < n; i += (size_t)threads) {
             const Rec &r = d.recs[i]; const std::string &e = d.enc[r.part];
@@ -647,6 +648,7 @@ void load_alignments(const char *path, int threads, AlnTable &out)
             const size_t cig_at = r.off + 36 + l_name, seq_at = cig_at + 4 * (size_t)out.n_cig[i];
             for (uint32_t c = 0; c < out.n_cig[i]; ++c) out.cigar[out.cig_off[i] + c] = rd32(e, cig_at + 4 * c);
             std::memcpy(&out.seq[(size_t)(out.seq_off[i] / 2)], e.data() + seq_at, (size_t)((out.l_seq[i] + 1) / 2));
+            if (with_qual) std::memcpy(&out.qual[(size_t)out.seq_off[i]], e.data() + seq_at + (out.l_seq[i] + 1) / 2, (size_t)out.l_seq[i]);
         }
     });
 }

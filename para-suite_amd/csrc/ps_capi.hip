@@ -745,6 +745,35 @@ int ps_error_profile(const char *mapping_sam_or_bam, const char *ref_fa, int max
     PS_CATCH_INT
 }
 
+// All six files of ErrorProfiling.inferErrorProfile(infer_qualities, false) -- the toolkit's `error` mode (Main.java:560-597):
+// the two above, byte for byte, and .errorprofile.vcf, .qualityPerMismatch, .indels, .qualities.  Nothing is written unless
+// every count was taken.
+int ps_error_profile_full(const char *mapping_sam_or_bam, const char *ref_fa, int max_read_len, const char *out_prefix,
+                          int infer_qualities, ps_profile_stats *stats)
+{
+    PS_TRY
+        ProfileCounts c;
+        int dev = 0;
+        if (const char *e = std::getenv("PARASUITE_GPU_IDS")) dev = std::atoi(e);
+        double ms_parse = 0;
+        error_profile_count(mapping_sam_or_bam, ref_fa, max_read_len, dev, 8, c, infer_qualities ? 2 : 1, &ms_parse);
+        const std::string prefix = out_prefix && out_prefix[0] ? out_prefix : mapping_sam_or_bam;
+        error_profile_write(c, prefix);
+        error_profile_write_extra(c, prefix);
+        if (stats) {
+            stats->n_records = c.n_records; stats->n_counted = c.n_processed; stats->n_unmapped = c.n_unmapped; stats->n_duplicate = c.n_duplicate;
+            stats->n_start_zero = c.n_start_zero; stats->n_indel_reads = c.n_indel_reads; stats->n_skipped = c.n_skipped;
+            stats->n_without_qual = c.n_without_qual; stats->n_qual_beyond_read = c.n_qual_beyond_read;
+        }
+        if (std::getenv("PS_VERBOSE"))
+            std::fprintf(stderr, "[parasuite-hip] ps_error_profile_full: %llu records, %llu counted (%llu unmapped, %llu duplicate, %llu without position, %llu with indels, %llu skipped, "
+                                 "%llu without QUAL, %llu mismatch qualities beyond the read); parse %.1f ms, count kernel %.2f ms, SD kernel %.2f ms\n",
+                         c.n_records, c.n_processed, c.n_unmapped, c.n_duplicate, c.n_start_zero, c.n_indel_reads, c.n_skipped,
+                         c.n_without_qual, c.n_qual_beyond_read, ms_parse, c.ms_count, c.ms_sd);
+        return 0;
+    PS_CATCH_INT
+}
+
 int ps_sam_to_bam(const char *sam, const char *bam, int min_mapq, int sort_by_coordinate, int write_index, int threads, ps_bam_stats *st)
 {
     PS_TRY

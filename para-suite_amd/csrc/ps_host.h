@@ -90,27 +90,43 @@ struct ProfileCounts {                 // raw counts, read orientation; [pos][re
     int max_len = 0;
     std::vector<unsigned long long> conv, ins, del;     // conv: max_len*16; ins/del: per alignment column (forward strand), max_len
     unsigned long long n_records = 0, n_processed = 0, n_unmapped = 0, n_duplicate = 0, n_start_zero = 0, n_indel_reads = 0, n_skipped = 0;
+    // quality passes (ProfileAccum with quals >= 1; ErrorProfiling.java:379-406): [ref base * 4 + read base] sums of QUAL and pairs
+    // booked for .qualityPerMismatch; with quals == 2 also per read position the QUAL sum, the number of values and the sum of
+    // (q - mean)^2 taken in file order
+    int quals = 0;
+    std::vector<unsigned long long> qpm_sum, qpm_cnt, qsum, qcnt; std::vector<double> qssd;
+    unsigned long long n_without_qual = 0, n_qual_beyond_read = 0;
+    double ms_count = 0, ms_sd = 0;                     // kernel times (events)
 };
 // alignment records as the counting kernel takes them (BAM conventions: CIGAR words len<<4|op with MIDNSHP=X, bases as nibbles
-// =ACMGRSVTWYHKDBN in the orientation of the SAM record); gpos = start on the packed forward strand, < 0: not counted
+// =ACMGRSVTWYHKDBN in the orientation of the SAM record); gpos = start on the packed forward strand, < 0: not counted;
+// qual (ProfileAccum with quals >= 1 only): one Phred byte per base at the base's seq_off index, 0xFF first byte = QUAL absent
 struct ProfRecords {
     std::vector<int64_t> gpos; std::vector<int32_t> l_seq; std::vector<uint32_t> flag, cig_off, n_cig, cigar;
-    std::vector<uint64_t> seq_off; std::vector<uint8_t> seq;
+    std::vector<uint64_t> seq_off; std::vector<uint8_t> seq, qual;
     size_t n() const { return gpos.size(); }
 };
-// device-side totals that several batches of records add to (the fused first pass adds one batch per piece of the input)
+// device-side totals that several batches of records add to (the fused first pass adds one batch per piece of the input).
+// quals: 0 the two files of the mapper, 1 + the .qualityPerMismatch sums, 2 + the per-position quality values (.qualities);
+// with quals == 2 the batches stay on the device until finish(), which walks them again in order for the standard deviation
 struct Index;
 class ProfileAccum {
 public:
-    ProfileAccum(int device, const Index &ix /* pac and holes; resident on `device` */, int max_len);
+    ProfileAccum(int device, const Index &ix /* pac and holes; resident on `device` */, int max_len, int quals = 0);
     ~ProfileAccum();
     void add(const ProfRecords &r);
     void finish(ProfileCounts &out);          // conv / ins / del and the kernel's counters; the caller fills the record statistics
 private:
     struct Impl; Impl *p;
 };
-void error_profile_count(const char *mapping_sam_or_bam, const char *ref_prefix, int max_len, int device, int threads, ProfileCounts &out);
+// largest max_len of the quality passes, from the counting kernel's LDS (160 KiB per workgroup): 18 words per position + 1.5 KiB
+// for quals == 1 (2254), 20 words per position + 1.5 KiB for quals == 2 (2028); ps_error_profile's own kernel stops at 2275
+int profile_max_len(int quals);
+void error_profile_count(const char *mapping_sam_or_bam, const char *ref_prefix, int max_len, int device, int threads, ProfileCounts &out,
+                         int quals = 0, double *ms_parse = nullptr);
 void error_profile_write(const ProfileCounts &c, const std::string &out_prefix);    // <out_prefix>.errorprofile / .indelprofile
+// the other four files of ErrorProfiling.java: .errorprofile.vcf, .qualityPerMismatch, .indels, .qualities (empty unless c.quals == 2)
+void error_profile_write_extra(const ProfileCounts &c, const std::string &out_prefix);
 std::string java_double_to_string(double v);                                        // java.lang.Double.toString
 
 }  // namespace ps

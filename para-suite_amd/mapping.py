@@ -146,10 +146,13 @@ class PARAsuiteMapping(Mapping):
 
 
 class ErrorProfiling:
-    """mirror of utils.errorprofile.ErrorProfiling (ErrorProfiling.java:57-88, 100-631) for what the mapping step uses of it:
-    `new ErrorProfiling(mappingFileName, referenceFileName, maxReadLength).inferErrorProfile(false, false)` leaves
-    <mappingFileName>.errorprofile and <mappingFileName>.indelprofile behind (Main.java:327-334).  The counting runs on the GPU
-    (`ps_error_profile`); the other files the Java writes (.qualities, .indels, .vcf, plots) have no consumer in the path."""
+    """mirror of utils.errorprofile.ErrorProfiling (ErrorProfiling.java:57-88, 100-631):
+    `new ErrorProfiling(mappingFileName, referenceFileName, maxReadLength).inferErrorProfile(isInferQualities, isShowErrorPlot)`
+    writes the six files the Java writes, counted on the GPU (`ps_error_profile_full`): <mappingFileName>.errorprofile and
+    .indelprofile, which the refine pass reads (Main.java:327-334), and .errorprofile.vcf, .qualityPerMismatch, .indels and
+    .qualities (mean and standard deviation of the base quality per read position; empty unless isInferQualities), the files
+    of the `error` mode that the PAR-CLIP simulator takes as its indel_file and quality_file.  isShowErrorPlot (a Swing window)
+    is ignored.  Returns the paths of the .errorprofile and .indelprofile files."""
 
     def __init__(self, mappingFileName, referenceFileName, maxReadLength):
         self.mappingFileName = mappingFileName
@@ -158,7 +161,7 @@ class ErrorProfiling:
 
     def inferErrorProfile(self, isInferQualities=False, isShowErrorPlot=False):
         try:
-            capi.ps_error_profile(self.mappingFileName, self.referenceFileName, self.maxReadLength, None)
+            capi.ps_error_profile_full(self.mappingFileName, self.referenceFileName, self.maxReadLength, None, bool(isInferQualities))
         except capi.PsError as e:
             raise ExternalCallErrorException("ErrorProfiling %s: %s" % (self.mappingFileName, e))
         return self.mappingFileName + ".errorprofile", self.mappingFileName + ".indelprofile"

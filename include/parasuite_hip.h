@@ -177,6 +177,35 @@ typedef struct { uint64_t n_records, n_counted, n_unmapped, n_duplicate, n_start
                  n_without_qual, n_qual_beyond_read; } ps_profile_stats;
 int     ps_error_profile_full(const char *mapping_sam_or_bam, const char *ref_fa, int max_read_len, const char *out_prefix,
                               int infer_qualities, ps_profile_stats *stats /* may be NULL */);
+/* RBP-bound clusters with T->C statistics -- the toolkit's `clust MAPPING REF OUT SNP_VCF MIN_COVERAGE` mode
+ * (Main.java:601-639, PileupClusters.calculateReadPileups): the six files of the Java, byte for byte as the plain restatement
+ * in tests/java_pileupclusters.py writes them (no JVM is at hand, so this is not pinned to the jar itself):
+ *   <out_file>                      cluster table (header with the Java's "Seqenece"), one line per written cluster
+ *   <out_file>.ccr.fasta / .ccr.tsv crosslink-centred regions: [best site - 20, best site + 20] of every written cluster
+ *                                   with a best site
+ *   <out_file>.report               five counter lines ("Loci found that are SNPs" is always 0)
+ *   <site_prefix>.sitefrequency.tsv mean k-th largest T->C fraction over crosslinked clusters (the first one's k >= 1 counted
+ *                                   twice, as in the Java)
+ *   <site_prefix>.sitepositions.tsv per read index 0..50 the share of crosslinked clusters with a T->C there (NaN for none)
+ * The input must be coordinate-sorted by its header (@HD SO:coordinate); records with flag 4 are skipped, records whose
+ * CIGAR holds (I or D) and N are skipped and counted, and the last cluster is never written (all as in the Java).
+ * site_prefix NULL or "": the mapping file's name.  snp_vcf NULL or "": no known SNPs (an extension); the VCF is read whole
+ * (plain, gzip or BGZF), so no .tbi is needed.  ref_fa needs its index (.ann/.pac, ps_index); sequence text comes from the
+ * FASTA itself.  Where the Java throws or is undefined, this does not, and counts the case in stats instead:
+ *   - T->C at read index >= 51 (the Java's boolean[51] throws): counted everywhere but the read-index flags (n_t2c_beyond_51);
+ *   - CCR window starting before base 1 (htsjdk reads bytes before the contig): empty CCR sequence (n_ccr_clipped);
+ *   - a HashMap bucket of more than 8 sites at the end of a cluster (the Java resizes or makes a tree, and its iteration
+ *     order leaves the model): n_order_unmodelled;
+ *   - a VCF record whose first ALT allele is '.', '*', symbolic or a breakend never matches.
+ * A CCR window past the contig's end gives an empty sequence as in the Java (n_ccr_past_end).  Input that is not
+ * coordinate-sorted (the Java writes six empty files and exits 0), a record on a contig the index lacks, a record or a
+ * cluster-sequence fetch past its contig's end, and a mapped record with SEQ '*' are errors: nothing is written then.
+ * n_clusters_written counts the lines of <out_file>, the MIN_COVERAGE <= 0 line of the empty first pseudo-cluster included. */
+typedef struct { uint64_t n_records, n_unmapped, n_skipped_indel, n_kept, n_clusters, n_clusters_written, n_crosslinked, n_ccr,
+                 n_double_stranded, n_snp_hits, n_snv_sites, n_t2c_beyond_51, n_ccr_clipped, n_ccr_past_end,
+                 n_order_unmodelled; } ps_cluster_stats;
+int     ps_pileup_clusters(const char *mapping_sam_or_bam, const char *ref_fa, const char *out_file, const char *snp_vcf,
+                           int min_read_coverage, const char *site_prefix, ps_cluster_stats *stats /* may be NULL */);
 /* The first pass and its error profile in one call -- "fed directly from alignment results" (SURVEY.md §8f rank 4): ps_map, and
  * while the SAM is written the same records, straight from memory, go through the counting kernel: the alignments with
  * MAPQ >= min_mapq, i.e. what the pass's filtered BAM holds (samtools view -q, PARAsuiteMapping.java:124-133 /

@@ -44,7 +44,7 @@ EXPORTS = ["ps_version", "ps_last_error", "ps_index", "ps_map", "ps_ctx_open", "
            "ps_ctx_blob", "ps_ctx_meta", "ps_ctx_from_blobs", "ps_ctx_clone", "ps_ctx_fetch", "ps_ctx_export_blob", "ps_ctx_sa_lookup", "ps_ctx_index_check", "ps_sam_to_bam", "ps_map_to_bam", "ps_bam_view", "ps_bam_sort", "ps_bam_index", "ps_batch_from_fastq",
            "ps_batch_from_codes", "ps_batch_free", "ps_batch_n", "ps_batch_search", "ps_batch_select_hard",
            "ps_batch_select_easy", "ps_batch_locate", "ps_batch_run", "ps_batch_write_sam", "ps_batch_n_aln",
-           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_map_profiled", "ps_release_host_cache"]
+           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_map_profiled", "ps_release_host_cache"]
 
 _LIB = None
 
@@ -360,6 +360,22 @@ def ps_error_profile_full(mapping, ref_fa, max_read_len=101, out_prefix=None, in
     _chk(L.ps_error_profile_full(mapping.encode(), ref_fa.encode(), int(max_read_len), out_prefix.encode() if out_prefix else None,
                                  int(bool(infer_qualities)), C.byref(st)))
     return {f: int(getattr(st, f)) for f, _ in ProfileStats._fields_}
+
+
+class ClusterStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_records", "n_unmapped", "n_skipped_indel", "n_kept", "n_clusters", "n_clusters_written",
+                                          "n_crosslinked", "n_ccr", "n_double_stranded", "n_snp_hits", "n_snv_sites",
+                                          "n_t2c_beyond_51", "n_ccr_clipped", "n_ccr_past_end", "n_order_unmodelled")]
+
+
+def ps_pileup_clusters(mapping, ref_fa, out_file, snp_vcf=None, min_read_coverage=1, site_prefix=None):
+    """the six files of PileupClusters.calculateReadPileups: <out_file>, .ccr.fasta, .ccr.tsv, .report and
+    <site_prefix or mapping>.sitefrequency.tsv, .sitepositions.tsv (counted on the GPU); returns the counters"""
+    enc = lambda v: v.encode() if v else None
+    L = lib(); L.ps_pileup_clusters.argtypes = [C.c_char_p] * 4 + [C.c_int, C.c_char_p, C.POINTER(ClusterStats)]
+    st = ClusterStats()
+    _chk(L.ps_pileup_clusters(enc(mapping), enc(ref_fa), enc(out_file), enc(snp_vcf), int(min_read_coverage), enc(site_prefix), C.byref(st)))
+    return {f: int(getattr(st, f)) for f, _ in ClusterStats._fields_}
 
 
 def ps_map_profiled(threads, mm, error_profile, indel_profile, ref_fa, reads, out_sam, min_mapq, max_read_len, profile_prefix):

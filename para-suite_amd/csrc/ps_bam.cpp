@@ -628,6 +628,11 @@ void load_alignments(const char *path, int threads, AlnTable &out, bool with_qua
     if (mg[0] == 31 && mg[1] == 139) load_bam(path, threads, d, nullptr, nullptr); else load_sam(path, -1, threads, d);
     out = AlnTable();
     out.refs = d.refs;
+    if (d.text.compare(0, 3, "@HD") == 0) {
+        const std::string hd = d.text.substr(0, d.text.find('\n'));
+        const size_t at = hd.find("\tSO:");
+        if (at != std::string::npos) { const size_t e = hd.find('\t', at + 1); out.sort_order = hd.substr(at + 4, e == std::string::npos ? e : e - at - 4); }
+    }
     const size_t n = d.recs.size();
     out.ref.resize(n); out.pos.resize(n); out.l_seq.resize(n); out.flag.resize(n); out.cig_off.resize(n); out.n_cig.resize(n); out.seq_off.resize(n);
     uint64_t bases = 0; uint32_t ops = 0;

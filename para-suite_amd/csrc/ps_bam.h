@@ -37,6 +37,7 @@ struct AlnTable {
     std::vector<uint32_t> cig_off, n_cig, cigar;
     std::vector<uint64_t> seq_off; std::vector<uint8_t> seq;   // seq_off in bases; base j of a record: nibble (seq_off + j)
     std::vector<uint8_t> qual;    // with_qual only: Phred value of base j at byte (seq_off + j), as BAM stores it (0xFF: QUAL absent)
+    std::string sort_order;       // SO: of the @HD header line ("" when there is none)
     size_t n() const { return ref.size(); }
 };
 void load_alignments(const char *sam_or_bam, int threads, AlnTable &out, bool with_qual = false);                                                          // samtools index -> <bam>.bai

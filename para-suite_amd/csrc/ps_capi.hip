@@ -774,6 +774,19 @@ int ps_error_profile_full(const char *mapping_sam_or_bam, const char *ref_fa, in
     PS_CATCH_INT
 }
 
+// The toolkit's `clust` mode (Main.java:601-639): PileupClusters.calculateReadPileups, its six files.  Nothing is written unless
+// every count was taken.
+int ps_pileup_clusters(const char *mapping_sam_or_bam, const char *ref_fa, const char *out_file, const char *snp_vcf,
+                       int min_read_coverage, const char *site_prefix, ps_cluster_stats *stats)
+{
+    PS_TRY
+        int dev = 0;
+        if (const char *e = std::getenv("PARASUITE_GPU_IDS")) dev = std::atoi(e);
+        pileup_clusters_run(mapping_sam_or_bam, ref_fa, out_file, snp_vcf, min_read_coverage, site_prefix, dev, stats);
+        return 0;
+    PS_CATCH_INT
+}
+
 int ps_sam_to_bam(const char *sam, const char *bam, int min_mapq, int sort_by_coordinate, int write_index, int threads, ps_bam_stats *st)
 {
     PS_TRY

@@ -9,6 +9,7 @@
 #include "ps_types.h"
 #include "ps_model.h"
 #include "ps_kernels.h"
+#include "../../include/parasuite_hip.h"
 
 namespace ps {
 
@@ -128,5 +129,9 @@ void error_profile_write(const ProfileCounts &c, const std::string &out_prefix);
 // the other four files of ErrorProfiling.java: .errorprofile.vcf, .qualityPerMismatch, .indels, .qualities (empty unless c.quals == 2)
 void error_profile_write_extra(const ProfileCounts &c, const std::string &out_prefix);
 std::string java_double_to_string(double v);                                        // java.lang.Double.toString
+
+// ---- RBP-bound clusters from a sorted mapping (ps_clusters.hip; what PileupClusters.calculateReadPileups writes) ----
+void pileup_clusters_run(const char *mapping_sam_or_bam, const char *ref_fa, const char *out_file, const char *snp_vcf, int min_cov,
+                         const char *site_prefix, int device, ps_cluster_stats *stats);
 
 }  // namespace ps

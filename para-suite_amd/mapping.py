@@ -165,3 +165,16 @@ class ErrorProfiling:
         except capi.PsError as e:
             raise ExternalCallErrorException("ErrorProfiling %s: %s" % (self.mappingFileName, e))
         return self.mappingFileName + ".errorprofile", self.mappingFileName + ".indelprofile"
+
+
+class PileupClusters:
+    """mirror of utils.pileupclusters.PileupClusters (PileupClusters.java:62-673), the `clust` mode (Main.java:601-639):
+    `new PileupClusters().calculateReadPileups(alignmentFile, referenceFile, outputFile, snpVcfFile, minReadCoverage)` writes
+    <outputFile>, .ccr.fasta, .ccr.tsv and .report, and <alignmentFile>.sitefrequency.tsv and .sitepositions.tsv, counted on
+    the GPU (`ps_pileup_clusters`).  snpVcfFile None or "": no known SNPs; the VCF needs no .tbi.  Returns the stats dict."""
+
+    def calculateReadPileups(self, alignmentFile, referenceFile, outputFile, snpVcfFile, minReadCoverage):
+        try:
+            return capi.ps_pileup_clusters(alignmentFile, referenceFile, outputFile, snpVcfFile, int(minReadCoverage))
+        except capi.PsError as e:
+            raise ExternalCallErrorException("PileupClusters %s: %s" % (alignmentFile, e))

@@ -37,7 +37,14 @@ int ps_index(const char *ref_fa);
  * mode) or -n (stock mode) argument as the Java passes it, e.g. "-1", "2", "0.04".
  * Devices: the first PARASUITE_GPUS (environment, default 1), each with its own copy of the index; the
  * input is cut into pieces that a parser thread, the device workers and a SAM writer work on side by
- * side; the output does not depend on the cut or on the number of devices. */
+ * side; the output does not depend on the cut or on the number of devices.
+ * Accepted ranges (here and for ps_ctx_set_*; what lies outside is an error naming the limit, never a launch):
+ *   profile -X x: 0..15 (a budget of 8x units: 8x + 1 score buckets, at most PS_MAX_BUCKETS = 128; -X 16 is refused).
+ *     -X -1: BWA's per-length budget cal_maxdiff(len, 0.02, 0.04): 7 differences up to 189 bp, 8 from 190, 9 at 225-250.
+ *   stock -n INT: 0..37 (3n + 15 score buckets; -n 38 is refused); -n with a '.' is a false-negative rate.
+ *   read length: 1..250 bp (PS_MAX_LEN); one longer read fails the call.
+ * Above 64 score buckets (-X 8 and up, -X -1 from 190 bp, -n 17 and up) a launch takes the wide search stack; reads with the
+ * same gap limit share one launch, which the longest of them decides. */
 int ps_map(int threads, const char *mm, const char *error_profile, const char *indel_profile,
            const char *ref_fa, const char *fastq, const char *out_sam);
 
@@ -49,6 +56,7 @@ ps_ctx *ps_ctx_open(const char *ref_fa, int device);                 /* load <re
 ps_ctx *ps_ctx_clone(ps_ctx *src, int device);                  /* a context on `device` with a device-to-device copy of src's index (what ps_map gives every device after the first) */
 ps_ctx *ps_ctx_build(const char *ref_fa, int device, int save_files);/* build the index (GPU), keep it resident */
 void    ps_ctx_close(ps_ctx *);
+/* the ranges of ps_map's mm apply; a model outside them fails at ps_batch_from_fastq / ps_batch_from_codes */
 int     ps_ctx_set_stock(ps_ctx *, const char *n_arg);               /* bwa aln -n */
 int     ps_ctx_set_profile(ps_ctx *, const char *error_profile, const char *indel_profile, const char *x_arg);
 int     ps_ctx_set_profile_matrix(ps_ctx *, const double P[16], double ins_rate, double del_rate, int x);

@@ -196,7 +196,7 @@ void launch_effort_model(const EffortModelArgs &a, hipStream_t s)
     if (blocks > 256 * 8) blocks = 256 * 8;
     if (blocks < 1) blocks = 1;
     const size_t lds = (size_t)256 * 2 * (a.max_units + 2) * sizeof(float);
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_effort_model), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    set_dynamic_lds(reinterpret_cast<const void *>(k_effort_model), "k_effort_model", lds);      // narrow launches only (run_search): max_units <= 63, 133,120 B
     hipLaunchKernelGGL(k_effort_model, dim3(blocks), dim3(256), lds, s, a);
 }
 

@@ -56,6 +56,12 @@ struct RefineArgs {
     uint8_t *zbuf; size_t z_per_block;     // traceback scratch, 64 lanes interleaved per block
 };
 
+// dynamic LDS above the 48 KiB default needs the kernel's opt-in.  A request above a CU's 160 KiB, or one the runtime refuses,
+// throws here with the kernel's name and the byte count -- it must not fail the launch and surface at the next error check
+// as someone else's error
+static const size_t PS_LDS_PER_CU = 160 * 1024;
+void set_dynamic_lds(const void *kernel, const char *name, size_t bytes);
+
 void launch_width(const WidthArgs &a, hipStream_t s);
 void launch_effort(const EffortArgs &a, hipStream_t s);
 void launch_effort_model(const EffortModelArgs &a, hipStream_t s);

@@ -9,6 +9,8 @@
 #include <hip/hip_runtime.h>
 #include <algorithm>
 #include <cstdlib>
+#include <stdexcept>
+#include <string>
 #include "ps_core.h"
 #include "ps_narrow.h"
 #include "ps_kernels.h"
@@ -437,7 +439,7 @@ bool launch_backtrack(const BtArgs &a_in, const BtArgs *d_args, BtArgs *h_stage,
     typedef void (*KernelN)(const BtArgs *, BtHot, int);
     const KernelN kn = stats ? (nb32 ? k_backtrack_n<true, true> : k_backtrack_n<true, false>) : (nb32 ? k_backtrack_n<false, true> : k_backtrack_n<false, false>);
     const void *fn = a.wide ? reinterpret_cast<const void *>(k_backtrack_wide) : reinterpret_cast<const void *>(kn);
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    set_dynamic_lds(fn, a.wide ? "k_backtrack_wide" : "k_backtrack_n", lds);
     if (a.wide) hipLaunchKernelGGL(k_backtrack_wide, dim3(n_blocks), dim3(256), lds, s, d_args, h, lm_stride);
     else hipLaunchKernelGGL(kn, dim3(n_blocks), dim3(256), lds, s, d_args, h, lm_stride);
     return true;
@@ -452,8 +454,16 @@ void launch_sa2pos(const IndexView &ix, const bwtint *rows, bwtint *out, int n, 
 void launch_refine(const RefineArgs &a, int n_blocks, hipStream_t s)
 {
     size_t lds = (size_t)(a.len + 2) * 64 * 4 * 2;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_refine), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    set_dynamic_lds(reinterpret_cast<const void *>(k_refine), "k_refine", lds);
     hipLaunchKernelGGL(k_refine, dim3(n_blocks), dim3(64), lds, s, a);
+}
+void set_dynamic_lds(const void *kernel, const char *name, size_t bytes)
+{
+    if (bytes <= 48 * 1024) return;
+    const std::string what = std::string(name) + ": " + std::to_string(bytes) + " B of dynamic LDS";
+    if (bytes > PS_LDS_PER_CU) throw std::runtime_error(what + " requested, a CU has " + std::to_string(PS_LDS_PER_CU));
+    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    if (e != hipSuccess) throw std::runtime_error(what + " refused: " + hipGetErrorString(e));
 }
 
 }  // namespace ps

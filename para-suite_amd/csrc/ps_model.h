@@ -178,11 +178,23 @@ inline bool make_model(const Options &o, int len, Model &m, std::string &err)
         m.u_mm_pk[s] = m.s_mm_pk[s] = 0;
         for (int c = 0; c < 4; ++c) { m.u_mm_pk[s] |= (uint32_t)m.u_mm[s][c] << (8 * c); m.s_mm_pk[s] |= (uint32_t)m.s_mm[s][c] << (8 * c); }
     }
-    if (m.n_buckets > PS_MAX_BUCKETS) { err = "score range exceeds PS_MAX_BUCKETS; lower -n/-X"; return false; }
-    if (len > PS_MAX_LEN) { err = "read longer than PS_MAX_LEN"; return false; }
+    if (m.n_buckets > PS_MAX_BUCKETS) {
+        err = "score range exceeds PS_MAX_BUCKETS (" + std::to_string(m.n_buckets) + " score buckets, at most " + std::to_string(PS_MAX_BUCKETS) + "); lower -n/-X";
+        return false;
+    }
+    if (len > PS_MAX_LEN) { err = "read longer than PS_MAX_LEN (" + std::to_string(len) + " bp, at most " + std::to_string(PS_MAX_LEN) + ")"; return false; }
     if (m.max_gapo > 7 || m.max_gape > 7) { err = "gap limits above 7 are not supported by the packed stack entry"; return false; }
     if (m.max_units / m.c_min > 126) { err = "difference budget too large"; return false; }
     return true;
+}
+
+// Which stack a search launch of this model takes.  Narrow entries link with 16-bit indices, keep one 64-bit bucket bitmap,
+// count inserted / deleted bases in 3 bits each and saturate the count of best hits at 255 (it is only ever compared with
+// max_top2); anything outside that takes the wide stack (32-byte entries, global bucket heads).  A ragged launch is wide or
+// narrow as a whole, by its longest read's model.
+inline bool launch_is_wide(const Model &m, uint32_t pool_cap)
+{
+    return pool_cap > 65535 || m.n_buckets > 64 || m.max_gapo + m.max_gape > 7 || m.max_top2 >= 255;
 }
 
 }  // namespace ps

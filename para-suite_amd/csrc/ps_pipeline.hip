@@ -647,10 +647,13 @@ static void run_search(Batch &b, const Model &md, int n, const uint32_t *d_bases
     wa.ix = ctx->ix.view; wa.n_reads = n; wa.len = len; wa.lens = d_lens; wa.seed_len = seed_len; wa.use_seed = md.use_seed;
     wa.bases = d_bases; wa.nmask = d_nmask; wa.w = w; wa.cwb = cwb; wa.cswb = cswb; wa.stats = b.d_stats.p + 0;
     { EvTimer t(s); launch_width(wa, s); PS_HIP(hipGetLastError()); b.tm.ms_width += t.stop(); ++b.tm.n_width_launches; }
+    const bool wide = launch_is_wide(md, pool_cap);
     // ---- hand-out order: the reads with the heaviest predicted search first (ps_effort.hip), so that the launch does not end on
-    // them.  PS_ORDER=0 switches it off, 2 orders by the estimated best score alone (A/B runs).
+    // them.  PS_ORDER=0 switches it off, 2 orders by the estimated best score alone (A/B runs).  Narrow launches only: the wide
+    // stack takes its reads in queue order and never reads the estimate (its budget can also pass what k_effort_model's
+    // per-lane LDS holds: -X 10 and up)
     const int32_t *d_order = nullptr; const uint8_t *d_est = nullptr; const uint16_t *d_est_ab = nullptr;
-    {
+    if (!wide) {
         const char *eo = std::getenv("PS_ORDER");
         const int mode = eo ? std::atoi(eo) : 1;
         int min_n = 4096;                                     // below that every read has a lane to itself at once: no order to choose
@@ -711,9 +714,6 @@ static void run_search(Batch &b, const Model &md, int n, const uint32_t *d_bases
     }
     int dev_cus = 256;
     { hipDeviceProp_t p; if (hipGetDeviceProperties(&p, ctx->device) == hipSuccess && p.multiProcessorCount > 0) dev_cus = p.multiProcessorCount; }
-    // narrow entries link with 16-bit indices, keep one 64-bit bucket bitmap and count inserted / deleted bases in 3 bits each
-    // ... and saturate the count of best hits at 255 (it is only ever compared with max_top2)
-    const bool wide = pool_cap > 65535 || md.n_buckets > 64 || md.max_gapo + md.max_gape > 7 || md.max_top2 >= 255;
     const int lm = lm_bytes(len, seed_len, md.n_buckets, wide);
     int per_cu = (int)((size_t)(160 * 1024) / ((size_t)256 * lm));
     if (per_cu < 1) throw Error("read length / score range too large for the per-lane LDS state");
@@ -744,7 +744,7 @@ static void run_search(Batch &b, const Model &md, int n, const uint32_t *d_bases
     a.alns = alns; a.aln_cap = aln_cap; a.n_aln = n_aln; a.status = status;
     a.pool = pool; a.pool_cap = pool_cap; a.heads = heads; a.wide = wide ? 1 : 0; a.stats = b.d_stats.p + 1;
     a.queue = queue; a.fetch_min = ctx->fetch_min; a.hit_min = ctx->hit_min;
-    a.order = wide ? nullptr : d_order; a.est = d_est; a.est_ab = d_est_ab;
+    a.order = d_order; a.est = d_est; a.est_ab = d_est_ab;                   // all null in a wide launch
     // the estimate also spares the search entries (ps_narrow.h, nt_tail): first tier and profile costs only (units == score); a read it fails on starts over without it inside the launch
     a.cap_est = (first_tier && !wide && d_est && md.profile && !(std::getenv("PS_CAP") && std::atoi(std::getenv("PS_CAP")) == 0)) ? 1 : 0;
     if (a.cap_est) if (const char *e = std::getenv("PS_CAP_BIAS")) a.cap_est += std::max(0, std::min(200, std::atoi(e)));      // tests: estimates too low by that much, so that the restart path runs

@@ -304,7 +304,7 @@ void ProfileAccum::add(const ProfRecords &t)
     int blocks = (int)std::min<size_t>(2048, (n + 255) / 256); if (blocks < 1) blocks = 1;
     if (Q == 0) {
         const size_t lds = prof_lds_bytes(0, max_len);
-        if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k_profile<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        set_dynamic_lds(reinterpret_cast<const void *>(k_profile<0>), "k_profile<0>", lds);
         hipLaunchKernelGGL(k_profile<0>, dim3(blocks), dim3(256), lds, s, a);
         PS_HIP(hipGetLastError());
         PS_HIP(hipStreamSynchronize(s));      // the record arrays above are released on return
@@ -312,7 +312,7 @@ void ProfileAccum::add(const ProfRecords &t)
     }
     const size_t lds = prof_lds_bytes(Q, max_len);         // <= 160 KiB: profile_max_len
     void (*kern)(ProfArgs) = Q == 1 ? k_profile<1> : k_profile<2>;
-    if (lds > 48 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    set_dynamic_lds(reinterpret_cast<const void *>(kern), Q == 1 ? "k_profile<1>" : "k_profile<2>", lds);
     p->ms_count += timed(s, [&]() { hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, a); PS_HIP(hipGetLastError()); });
     if (Q == 2) { Impl::Kept k; k.qual = std::move(d_qual); k.soff = std::move(d_soff); k.nq = std::move(d_nq); k.n = (int)n; p->kept.push_back(std::move(k)); }
 }

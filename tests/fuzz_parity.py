@@ -2,7 +2,7 @@
 
 Each case draws a genome shape (plain / repeats / low complexity / tiny), a read length, a cost model (stock -n or a
 random error profile with -X) and read noise (substitutions, indels, N's), maps a few thousand reads both ways and stops at
-the first difference.  usage: python tests/fuzz_parity.py [n_cases] [seed]"""
+the first difference.  usage: python tests/fuzz_parity.py [n_cases] [seed] [default|edges]"""
 import os
 import sys
 import tempfile
@@ -40,39 +40,73 @@ def genome(kind, rng):
     return [("t0", S.make_contig(int(rng.integers(300, 3000)), rng, [], softmask_frac=0.0))]      # tiny: every k-mer repeats
 
 
-def run(n_cases, seed):
+# ranges="edges": the ends of what the library accepts (include/parasuite_hip.h): profile -X 4..15, stock -n 5..37 (wide stacks
+# from -X 8 and -n 17 on), reads up to 250 bp, ragged ones across the 190-bp step of -X -1.  No read of 32 bp or less: it has no
+# seed rule, and one without a hit inside such a budget costs the oracle a near-exhaustive search
+EDGE_LENGTHS = [36, 50, 64, 65, 100, 150, 189, 190, 225, 250]
+
+
+def draw_case(rng, case, work, ranges="default"):
+    """the draw of one case (host only, no GPU): genome (written to work/g<case>.fa), reads (work/r<case>.fq), cost model and tier
+    sizes.  ranges="default" keeps the stream of draws the seeded cases of the suite were recorded with"""
+    edges = ranges == "edges"
+    assert ranges in ("default", "edges"), ranges
+    kind = rng.choice(["plain", "repeats", "lowcomplexity", "tiny"], p=[0.35, 0.3, 0.2, 0.15])
+    g = genome(kind, rng)
+    fa = os.path.join(work, "g%d.fa" % case)
+    S.write_fasta(fa, g)
+    L = int(rng.choice(EDGE_LENGTHS if edges else [20, 28, 36, 50, 51, 64, 65, 75, 100, 150]))
+    L = min(L, min(a.size for _, a in g) - 4)
+    mixed = rng.random() < 0.25
+    if edges:
+        n_reads = 400 if L > 150 else 800
+        min_len = max(36, L - 150) if mixed else None
+    else:
+        n_reads = 1500 if L > 75 else 3000
+        min_len = max(17, L - 20) if mixed else None
+    P = S.EXAMPLE_PROFILE.copy()
+    if rng.random() < 0.7:
+        P[3, 1] = rng.choice([0.02, 0.12, 0.3]); P[3, 3] = 1.0 - P[3, 1] - P[3, 0] - P[3, 2]
+    sim = S.simulate_reads(g, n_reads=n_reads, read_len=L, min_len=min_len, seed=int(rng.integers(1 << 30)),
+                           bound=float(rng.choice([0.0, 0.6, 1.0])), profile=P, indel_scale=float(rng.choice([0, 30, 200])),
+                           n_frac=float(rng.choice([0, 0.002, 0.02])))
+    fq = os.path.join(work, "r%d.fq" % case)
+    S.write_fastq(fq, sim)
+    c = dict(kind=str(kind), fa=fa, fq=fq, L=L, mixed=bool(mixed), n_reads=n_reads, tiers=None)
+    if rng.random() < 0.45:
+        n = str(int(rng.integers(5, 38))) if edges else str(rng.choice(["0.04", "0.02", "0", "1", "2", "4"]))
+        c.update(mode="stock", n=n, what="stock -n " + n)
+    else:
+        x = int(rng.integers(4, 16)) if edges else int(rng.choice([-1, 1, 2, 3]))
+        ins, dele = float(rng.choice([0.0, 2.1e-5, 1e-3])), float(rng.choice([0.0, 5.9e-4, 1e-2]))
+        c.update(mode="profile", P=P, x=x, ins=ins, dele=dele, what="profile -X %d T>C %.2f ins %g del %g" % (x, P[3, 1], ins, dele))
+    if rng.random() < 0.3:                                # small tiers: exercise in-launch growth and the larger tiers
+        c["tiers"] = ([int(rng.choice([64, 512])), 4096, 2000064], [2, 64, 65536], 0)
+    return c
+
+
+def case_opt(c):
+    """the oracle's options of a drawn case"""
+    return orc.stock_opt(c["n"]) if c["mode"] == "stock" else orc.profile_opt(c["P"], c["ins"], c["dele"], c["x"])
+
+
+def run(n_cases, seed, ranges="default"):
     """returns the number of identical cases; raises SystemExit(1) at the first difference"""
     rng = np.random.default_rng(seed)
     work = tempfile.mkdtemp(prefix="psfuzz_")
     t0 = time.time()
     for case in range(n_cases):
-        kind = rng.choice(["plain", "repeats", "lowcomplexity", "tiny"], p=[0.35, 0.3, 0.2, 0.15])
-        g = genome(kind, rng)
-        fa = os.path.join(work, "g%d.fa" % case)
-        S.write_fasta(fa, g)
-        L = int(rng.choice([20, 28, 36, 50, 51, 64, 65, 75, 100, 150]))
-        L = min(L, min(a.size for _, a in g) - 4)
-        mixed = rng.random() < 0.25
-        n_reads = 1500 if L > 75 else 3000
-        P = S.EXAMPLE_PROFILE.copy()
-        if rng.random() < 0.7:
-            P[3, 1] = rng.choice([0.02, 0.12, 0.3]); P[3, 3] = 1.0 - P[3, 1] - P[3, 0] - P[3, 2]
-        sim = S.simulate_reads(g, n_reads=n_reads, read_len=L, min_len=max(17, L - 20) if mixed else None, seed=int(rng.integers(1 << 30)),
-                               bound=float(rng.choice([0.0, 0.6, 1.0])), profile=P, indel_scale=float(rng.choice([0, 30, 200])),
-                               n_frac=float(rng.choice([0, 0.002, 0.02])))
-        fq = os.path.join(work, "r%d.fq" % case)
-        S.write_fastq(fq, sim)
+        c = draw_case(rng, case, work, ranges)
+        fa, fq, kind, L, mixed, n_reads, what = c["fa"], c["fq"], c["kind"], c["L"], c["mixed"], c["n_reads"], c["what"]
         ctx = capi.Ctx.build(fa, device=0)
         oix = orc.Index.from_fasta(fa)
-        if rng.random() < 0.45:
-            n = str(rng.choice(["0.04", "0.02", "0", "1", "2", "4"]))
-            ctx.set_stock(n); opt = orc.stock_opt(n); what = "stock -n " + n
+        if c["mode"] == "stock":
+            ctx.set_stock(c["n"])
         else:
-            x = int(rng.choice([-1, 1, 2, 3]))
-            ins, dele = float(rng.choice([0.0, 2.1e-5, 1e-3])), float(rng.choice([0.0, 5.9e-4, 1e-2]))
-            ctx.set_profile(P, ins, dele, x); opt = orc.profile_opt(P, ins, dele, x); what = "profile -X %d T>C %.2f ins %g del %g" % (x, P[3, 1], ins, dele)
-        if rng.random() < 0.3:                                # small tiers: exercise in-launch growth and the larger tiers
-            ctx.set_tiers([int(rng.choice([64, 512])), 4096, 2000064], [2, 64, 65536], 0)
+            ctx.set_profile(c["P"], c["ins"], c["dele"], c["x"])
+        opt = case_opt(c)
+        if c["tiers"]:
+            ctx.set_tiers(*c["tiers"])
         b = ctx.batch_from_fastq(fq)
         b.run(threads=8)
         gsam, osam, osai = fq + ".g.sam", fq + ".o.sam", fq + ".o.sai"
@@ -101,4 +135,4 @@ def run(n_cases, seed):
 
 
 if __name__ == "__main__":
-    run(int(sys.argv[1]) if len(sys.argv) > 1 else 30, int(sys.argv[2]) if len(sys.argv) > 2 else 1)
+    run(int(sys.argv[1]) if len(sys.argv) > 1 else 30, int(sys.argv[2]) if len(sys.argv) > 2 else 1, sys.argv[3] if len(sys.argv) > 3 else "default")

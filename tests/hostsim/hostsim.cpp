@@ -221,6 +221,14 @@ int hs_model_profile(const double *P, double ins, double del, int x, int len, Mo
     Options o; std::string err; profile_costs(o, P, ins, del, x);
     return make_model(o, len, *out, err) ? 0 : -1;
 }
+// what a model decides about its launch: out = {n_buckets, max_units, c_min, wide (the product's rule, launch_is_wide),
+// the largest substitution cost}
+void hs_model_info(const Model *md, uint32_t pool_cap, int32_t out[5])
+{
+    out[0] = md->n_buckets; out[1] = md->max_units; out[2] = md->c_min; out[3] = launch_is_wide(*md, pool_cap) ? 1 : 0;
+    out[4] = 0;
+    for (int s = 0; s < 4; ++s) for (int c = 0; c < 4; ++c) if (md->u_mm[s][c] > out[4]) out[4] = md->u_mm[s][c];
+}
 // 33-bit rows: the packed representations must round-trip values above 2^32 (no genome that large fits a CPU test)
 int hs_unit_rows33(void)
 {

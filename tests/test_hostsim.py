@@ -37,6 +37,7 @@ def hs():
     H.hs_index_jump.argtypes = [C.c_void_p, C.c_int]
     H.hs_jump_slot.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.c_void_p]
     H.hs_banded.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    H.hs_model_info.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p]
     assert H.hs_sizeof_alnrec() == ALNREC.itemsize
     return H
 
@@ -127,10 +128,13 @@ def _run(hs, h, model, codes, n_lanes=64, pool_cap=4096, aln_cap=64, wide=0, n_b
     return alns, n_aln, status, ks
 
 
-def _compare(hs, h, ix, opt, model, codes, **kw):
+def _compare(hs, h, ix, opt, model, codes, oracle_out=None, **kw):
+    """oracle_out: a list that receives the oracle's hit list of every read"""
     alns, n_aln, status, ks = _run(hs, h, model, codes, **kw)
     for r in range(codes.shape[0]):
         n, ref = ix.aln_one(opt, codes[r], cap=64)
+        if oracle_out is not None:
+            oracle_out.append(ref)
         assert status[r] == 0
         got = [tuple(int(a[f]) for f in ("k", "l", "n_mm", "n_gapo", "n_gape", "n_ins", "n_del", "score", "units")) for a in alns[r, :n_aln[r]]]
         exp = [tuple(a[f] for f in ("k", "l", "n_mm", "n_gapo", "n_gape", "n_ins", "n_del", "score", "units")) for a in ref]
@@ -278,3 +282,95 @@ def test_estimated_best_score_never_shows_in_the_hits(hs, sim_index, example, x)
     if x == -1:                                  # a budget of several differences: room between the estimate and the budget (-X 1 has none)
         assert pushes["exact"] < 0.9 * int(ks0[3]), (pushes, int(ks0[3]))
         assert pushes["zero"] > pushes["exact"], pushes
+
+
+# ---- the edges of the option ranges (make_model in ps_model.h; the wide / narrow rule launch_is_wide) ----------------------
+# A profile model spends U = 8 units per average mismatch: -X x is a budget of 8x units and 8x + 1 score buckets.  Above 64
+# buckets every launch takes the wide stack (-X 8 and up); 129 buckets (-X 16) pass PS_MAX_BUCKETS = 128.  -X -1 takes BWA's
+# per-length budget cal_maxdiff(len, 0.02, 0.04): 7 differences up to 189 bp, 8 from 190 bp, 9 at 225-250 bp.  Stock -n INT
+# has 3n + 15 buckets (n mismatch scores of 3 less one, one gap open of 11, six extensions of 4): -n 16 is the last narrow
+# count, -n 37 the last accepted one.
+
+def _tc_profile(t2c=0.12):
+    P = S.EXAMPLE_PROFILE.copy()
+    P[3, 1], P[3, 3] = t2c, 1.0 - t2c - P[3, 0] - P[3, 2]
+    return P
+
+
+def _model_info(hs, model, pool_cap=4096):
+    out = np.zeros(5, dtype=np.int32)
+    hs.hs_model_info(model, pool_cap, out.ctypes.data)
+    return dict(n_buckets=int(out[0]), max_units=int(out[1]), c_min=int(out[2]), wide=bool(out[3]), max_sub=int(out[4]))
+
+
+def _edge_case(hs, sim_index, example, model, opt, n_buckets, wide, n_reads, L, seed):
+    """lane machine (on the stack the product's rule picks) == oracle, hit list for hit list, on PAR-CLIP reads (T->C 0.12,
+    indels, 0.2 % N); returns the model's facts and the oracle's hit lists.  The stacks hold 65,535 entries (the product's
+    second tier, the largest a narrow stack links): large budgets outgrow the first tier's 16,384, and a read that overflows
+    would be handed to the next tier instead of compared"""
+    info = _model_info(hs, model, 65535)
+    assert (info["n_buckets"], info["wide"]) == (n_buckets, wide), info
+    sim = S.simulate_reads(example["genome"], n_reads, L, seed=seed, profile=_tc_profile(), indel_scale=40, n_frac=0.002)
+    refs = []
+    _compare(hs, sim_index, example["orc_index"], opt, model, sim["codes"], oracle_out=refs, wide=int(wide), pool_cap=65535)
+    if info["max_units"] > 0:              # the budget was really used: most reads' best hit has a difference (counted on the oracle)
+        with_diff = sum(1 for ref in refs if ref and ref[0]["n_mm"] + ref[0]["n_gapo"] + ref[0]["n_gape"] > 0)
+        assert 3 * with_diff >= n_reads, (with_diff, n_reads)
+    return info, refs
+
+
+@pytest.mark.parametrize("x,L,n_buckets,wide", [(0, 50, 1, False), (7, 50, 57, False), (8, 50, 65, True), (9, 50, 73, True),
+                                                (10, 50, 81, True), (15, 50, 121, True),
+                                                (-1, 189, 57, False), (-1, 190, 65, True), (-1, 250, 73, True), (15, 250, 121, True)])
+def test_lane_machine_profile_budget_edges(hs, sim_index, example, x, L, n_buckets, wide):
+    """-X 0 (no difference affordable), the last narrow and the first wide budgets, -X 10 and up (whose launches could not run
+    the effort kernels), the largest budget -X 15, and -X -1 on both sides of its 190-bp step and at the longest read"""
+    P = _tc_profile()
+    model = (C.c_uint8 * hs.hs_sizeof_model())()
+    assert hs.hs_model_profile(np.ascontiguousarray(P.reshape(16)).ctypes.data, 2.1e-5, 5.9e-4, x, L, model) == 0
+    info, _ = _edge_case(hs, sim_index, example, model, orc.profile_opt(P, 2.1e-5, 5.9e-4, x), n_buckets, wide,
+                         100 if L <= 50 else 60, L, seed=1000 + 17 * x + L)
+    assert info["max_units"] == n_buckets - 1
+
+
+@pytest.mark.parametrize("n_arg,L,n_buckets,wide", [("16", 50, 63, False), ("17", 50, 66, True), ("37", 50, 126, True),
+                                                    ("0.001", 250, 54, False)])
+def test_lane_machine_stock_budget_edges(hs, sim_index, example, n_arg, L, n_buckets, wide):
+    """stock -n: the last narrow count (16), the first wide one (17), the largest accepted (37), and a false-negative rate that
+    gives a 250-bp read a budget of 13 differences"""
+    model = (C.c_uint8 * hs.hs_sizeof_model())()
+    assert hs.hs_model_stock(n_arg.encode(), L, model) == 0
+    _edge_case(hs, sim_index, example, model, orc.stock_opt(n_arg), n_buckets, wide, 100 if L <= 50 else 60, L, seed=2000 + L)
+
+
+def test_lane_machine_extreme_cost_tables(hs, sim_index, example):
+    """two cost tables at the ends of profile_costs: (a) an error profile with a zero entry, whose cost clamps at 4U = 32;
+    (b) a T->C rate of 0.6, which makes T->C cost one unit (c_min = 1, every budget test divides by it), with an insertion rate
+    of 0 and a deletion rate of 1 (both outside (0, 1): the stock gap ratio 11/3 of a mismatch)"""
+    P0 = np.full((4, 4), 0.03)
+    P0[0, 2] = 0.0
+    np.fill_diagonal(P0, 0.0)
+    np.fill_diagonal(P0, 1.0 - P0.sum(axis=1))
+    P1 = _tc_profile(0.6)
+    for tag, P, ins, dele, c_min, max_sub, seed in (("zero entry", P0, 2.1e-5, 5.9e-4, None, 32, 3001), ("T>C cost 1", P1, 0.0, 1.0, 1, None, 3002)):
+        model = (C.c_uint8 * hs.hs_sizeof_model())()
+        assert hs.hs_model_profile(np.ascontiguousarray(P.reshape(16)).ctypes.data, ins, dele, 5, 50, model) == 0, tag
+        info, _ = _edge_case(hs, sim_index, example, model, orc.profile_opt(P, ins, dele, 5), 41, False, 100, 50, seed=seed)
+        if c_min is not None:
+            assert info["c_min"] == c_min, (tag, info)
+        if max_sub is not None:
+            assert info["max_sub"] == max_sub, (tag, info)
+
+
+def test_models_outside_the_ranges_are_rejected(hs):
+    """-X 16 (129 score buckets), stock -n 38 (129 buckets) and a 251-bp read (PS_MAX_LEN = 250) have no model; their neighbours
+    inside the ranges do"""
+    Pc = np.ascontiguousarray(_tc_profile().reshape(16))
+    model = (C.c_uint8 * hs.hs_sizeof_model())()
+    assert hs.hs_model_profile(Pc.ctypes.data, 2.1e-5, 5.9e-4, 16, 50, model) != 0
+    assert hs.hs_model_profile(Pc.ctypes.data, 2.1e-5, 5.9e-4, 15, 50, model) == 0
+    assert hs.hs_model_profile(Pc.ctypes.data, 2.1e-5, 5.9e-4, -1, 251, model) != 0
+    assert hs.hs_model_profile(Pc.ctypes.data, 2.1e-5, 5.9e-4, -1, 250, model) == 0
+    assert hs.hs_model_stock(b"38", 50, model) != 0
+    assert hs.hs_model_stock(b"37", 50, model) == 0
+    assert hs.hs_model_stock(b"0.04", 251, model) != 0

@@ -85,6 +85,7 @@ int     ps_ctx_fetch(ps_ctx *, int which, void *host_dst, uint64_t bytes); /* D2
 int     ps_ctx_export_blob(ps_ctx *, int which, void *dev_dst, uint64_t bytes); /* D2D copy into caller memory (broadcast source) */
 int     ps_ctx_index_check(ps_ctx *, uint64_t out[4]);   /* every row of the index checked against the packed text along the LF cycle: rows visited (== seq_len + 1), BWT symbol mismatches, SA sample mismatches, longest arc */
 int     ps_ctx_sa_lookup(ps_ctx *, const uint64_t *rows, int64_t n, uint64_t *out); /* SA[row], rows in [1, seq_len]: index checks from the text */
+int     ps_ctx_order_sort(ps_ctx *, const uint8_t *keys, int64_t n, int32_t *order); /* the hand-out order of a search launch from its 8-bit keys: order[queue position] = read, a stable ascending sort (tests) */
 
 ps_batch *ps_batch_from_fastq(ps_ctx *, const char *fastq);
 ps_batch *ps_batch_from_codes(ps_ctx *, int64_t n, int len, const uint8_t *codes); /* [n][len], 0..3 ACGT, 4 N */

@@ -166,6 +166,24 @@ int ps_ctx_index_check(ps_ctx *x, uint64_t out[4])
         return 0;
     PS_CATCH_INT
 }
+int ps_ctx_order_sort(ps_ctx *x, const uint8_t *keys, int64_t n, int32_t *order)
+{
+    PS_TRY
+        Ctx &c = x->c;
+        require_device(c.device);
+        if (n < 0 || n > 0x7fffffff) throw Error("order sort: bad count");
+        if (n) {
+            DevBuf<uint8_t> d_k; DevBuf<int32_t> d_o; DevBuf<uint32_t> d_t;
+            d_k.alloc((size_t)n); d_o.alloc((size_t)n); d_t.alloc(order_sort_tmp_words((int)n));
+            d_k.upload(keys, (size_t)n, c.stream);
+            launch_order_sort(d_k.p, (int)n, d_t.p, d_o.p, c.stream);
+            PS_HIP(hipGetLastError());
+            d_o.download(order, (size_t)n, c.stream);
+            PS_HIP(hipStreamSynchronize(c.stream));
+        }
+        return 0;
+    PS_CATCH_INT
+}
 int ps_ctx_sa_lookup(ps_ctx *x, const uint64_t *rows, int64_t n, uint64_t *out)
 {
     PS_TRY

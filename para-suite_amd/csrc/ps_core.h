@@ -39,6 +39,17 @@ struct Blk { uint32_t x[16]; };  // cnt[4] + lo[6] + hi[6]
 typedef uint32_t ps_u32x4 __attribute__((ext_vector_type(4)));
 #endif
 
+// A per-lane index the optimiser may not fold into loop-invariant addresses.  The stage kernels that must start beside a
+// resident search launch (ps_budget.h) form the addresses of their read words where they load them: as 64-bit pointers per
+// lane carried across the loop of dependent Occ loads they cost the registers that were then spilled inside it.
+PS_HD int opaque_lane(int v)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    asm volatile("" : "+v"(v));
+#endif
+    return v;
+}
+
 PS_HD void load_blk(const OccBlock *blocks, uint32_t b, Blk &o)
 {
 #ifdef __HIP_DEVICE_COMPILE__

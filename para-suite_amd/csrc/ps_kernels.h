@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include "ps_types.h"
+#include "ps_budget.h"
 
 namespace ps {
 
@@ -54,7 +55,9 @@ struct RefineArgs {
     const RefineItem *items;
     uint32_t *cigar; int32_t *n_cigar;     // [n_items][PS_MAX_CIGAR]
     uint8_t *zbuf; size_t z_per_block;     // traceback scratch, 64 lanes interleaved per block
+    int32_t *hebuf; size_t he_per_block;   // H and E rows, [row][j][lane]: refine_he_words(len) words per block
 };
+inline size_t refine_he_words(int len) { return (size_t)(len + 2) * 64 * 2; }
 
 // dynamic LDS above the 48 KiB default needs the kernel's opt-in.  A request above a CU's 160 KiB, or one the runtime refuses,
 // throws here with the kernel's name and the byte count -- it must not fail the launch and surface at the next error check
@@ -73,5 +76,10 @@ bool launch_backtrack(const BtArgs &a, const BtArgs *d_args /* device copy, fill
 void launch_index_check(const IndexView &ix, unsigned long long *out /* device: rows visited, symbol mismatches, sample mismatches, longest arc */, hipStream_t s);
 void launch_sa2pos(const IndexView &ix, const bwtint *rows, bwtint *out, int n, KStats *stats, hipStream_t s);
 void launch_refine(const RefineArgs &a, int n_blocks, hipStream_t s);
+// ps_stage.hip: the hand-out order (order[queue position] = read, a STABLE sort of the 8-bit keys; tmp: order_sort_tmp_words(n) words) and
+// the tie-break stream's prefix counts (grp: the class-1 / class-2 reads in front of every group of 64 reads, from the host)
+size_t order_sort_tmp_words(int n);
+void launch_order_sort(const uint8_t *key, int n, uint32_t *tmp, int32_t *order, hipStream_t s);
+void launch_class_ranks(const uint8_t *cls, long long n, const uint32_t *grp, uint32_t *e_before, uint32_t *h_before, hipStream_t s);
 
 }  // namespace ps

@@ -40,46 +40,56 @@ __device__ __forceinline__ void flush_stats(KStats *ks, const LaneStats &st)
 }
 
 // ---- width stage: D(i) bounds for the read and for its seed ---------------
-__global__ void __launch_bounds__(256) k_width(WidthArgs a)
+// One chain per lane: in a launch with a seed rule (launch_width: twice the workgroups) the workgroups with an even index walk the
+// full-read chain of their 256 reads (w, cwb), those with an odd index the seed chain of the same reads (cswb); without one every
+// workgroup walks the read's chain.  A lane that stepped both chains kept four Occ blocks in registers (86 VGPRs);
+// one chain is two blocks, which leaves the kernel inside PS_STAGE_VGPRS (ps_budget.h): it starts beside a resident search
+// launch of the other batch instead of waiting for that launch to drain.  The two chains never shared anything but the read.
+__global__ void __launch_bounds__(256, 8) k_width(WidthArgs a)
 {
-    const int stride = gridDim.x * blockDim.x;
+    const int roles = a.use_seed ? 2 : 1;
+    const bool seed_role = roles == 2 && (blockIdx.x & 1) != 0;
+    const int stride = (gridDim.x / roles) * blockDim.x;
     LaneStats st = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < a.n_reads; r += stride) {
-        WChain A, B;
-        wchain_init(a.ix, A); wchain_init(a.ix, B);
+    for (int r = (blockIdx.x / roles) * blockDim.x + threadIdx.x; r < a.n_reads; r += stride) {
+        WChain C;
+        wchain_init(a.ix, C);
         const int len = a.lens ? a.lens[r] : a.len, seed_len = a.seed_len;
         const bool seeded = a.use_seed && len > seed_len;     // the seed rule is the read's own: a launch may hold reads on either side of the seed length
-        uint32_t bw = 0, mw = 0, sbw = 0, smw = 0;  // current base / N-mask words of the two chains
-        uint32_t cww = 0, csww = 0;                  // compact width bytes being assembled, 4 positions per word
-        for (int i = 0; i < len; ++i) {
-            int j = len - 1 - i;
-            if (i == 0 || (j & 15) == 15) bw = a.bases[(size_t)(j >> 4) * a.n_reads + r];
-            if (i == 0 || (j & 31) == 31) mw = a.nmask[(size_t)(j >> 5) * a.n_reads + r];
-            int base = ((mw >> (j & 31)) & 1u) ? 4 : (int)((bw >> (2 * (j & 15))) & 3u);
-            uint32_t wv; uint8_t cb;
-            if (seeded && i < seed_len) {
-                int js = seed_len - 1 - i;
-                if (i == 0 || (js & 15) == 15) sbw = a.bases[(size_t)(js >> 4) * a.n_reads + r];
-                if (i == 0 || (js & 31) == 31) smw = a.nmask[(size_t)(js >> 5) * a.n_reads + r];
-                int sbase = ((smw >> (js & 31)) & 1u) ? 4 : (int)((sbw >> (2 * (js & 15))) & 3u);
-                uint32_t swv; uint8_t scb;
-                wchain_step(a.ix, B, sbase, swv, scb, i == 0, st);
-                csww |= (uint32_t)scb << (8 * (i & 3));
-                if ((i & 3) == 3) { a.cswb[(size_t)(i >> 2) * a.n_reads + r] = csww; csww = 0; }
+        uint32_t bw = 0, mw = 0;                     // current base / N-mask words of the chain
+        uint32_t cww = 0;                            // compact width bytes being assembled, 4 positions per word
+        if (!seed_role) {
+#pragma unroll 1
+            for (int i = 0; i < len; ++i) {
+                int j = len - 1 - i;
+                if (i == 0 || (j & 15) == 15) bw = a.bases[(size_t)(j >> 4) * a.n_reads + opaque_lane(r)];
+                if (i == 0 || (j & 31) == 31) mw = a.nmask[(size_t)(j >> 5) * a.n_reads + opaque_lane(r)];
+                int base = ((mw >> (j & 31)) & 1u) ? 4 : (int)((bw >> (2 * (j & 15))) & 3u);
+                uint32_t wv; uint8_t cb;
+                wchain_step(a.ix, C, base, wv, cb, i == 0, st);
+                a.w[(size_t)i * a.n_reads + opaque_lane(r)] = wv;
+                cww |= (uint32_t)cb << (8 * (i & 3));
+                if ((i & 3) == 3) { a.cwb[(size_t)(i >> 2) * a.n_reads + opaque_lane(r)] = cww; cww = 0; }
             }
-            wchain_step(a.ix, A, base, wv, cb, i == 0, st);
-            a.w[(size_t)i * a.n_reads + r] = wv;
-            cww |= (uint32_t)cb << (8 * (i & 3));
-            if ((i & 3) == 3) { a.cwb[(size_t)(i >> 2) * a.n_reads + r] = cww; cww = 0; }
-        }
-        a.w[(size_t)len * a.n_reads + r] = 0;
-        cww |= (uint32_t)cw_pack(A.bid + 1, false) << (8 * (len & 3));
-        a.cwb[(size_t)(len >> 2) * a.n_reads + r] = cww;
-        if (seeded) {
-            csww |= (uint32_t)cw_pack(B.bid + 1, false) << (8 * (seed_len & 3));
-            a.cswb[(size_t)(seed_len >> 2) * a.n_reads + r] = csww;
+            a.w[(size_t)len * a.n_reads + opaque_lane(r)] = 0;
+            cww |= (uint32_t)cw_pack(C.bid + 1, false) << (8 * (len & 3));
+            a.cwb[(size_t)(len >> 2) * a.n_reads + opaque_lane(r)] = cww;
+        } else if (seeded) {
+#pragma unroll 1
+            for (int i = 0; i < seed_len; ++i) {
+                int js = seed_len - 1 - i;
+                if (i == 0 || (js & 15) == 15) bw = a.bases[(size_t)(js >> 4) * a.n_reads + opaque_lane(r)];
+                if (i == 0 || (js & 31) == 31) mw = a.nmask[(size_t)(js >> 5) * a.n_reads + opaque_lane(r)];
+                int sbase = ((mw >> (js & 31)) & 1u) ? 4 : (int)((bw >> (2 * (js & 15))) & 3u);
+                uint32_t swv; uint8_t scb;
+                wchain_step(a.ix, C, sbase, swv, scb, i == 0, st);
+                cww |= (uint32_t)scb << (8 * (i & 3));
+                if ((i & 3) == 3) { a.cswb[(size_t)(i >> 2) * a.n_reads + opaque_lane(r)] = cww; cww = 0; }
+            }
+            cww |= (uint32_t)cw_pack(C.bid + 1, false) << (8 * (seed_len & 3));
+            a.cswb[(size_t)(seed_len >> 2) * a.n_reads + opaque_lane(r)] = cww;
         } else if (a.use_seed) {                     // a read without a seed in a launch with one: its seed bounds are never looked at, but the lane loads the words
-            for (int p = 0; p <= (seed_len >> 2); ++p) a.cswb[(size_t)p * a.n_reads + r] = 0u;
+            for (int p = 0; p <= (seed_len >> 2); ++p) a.cswb[(size_t)p * a.n_reads + opaque_lane(r)] = 0u;
         }
     }
     flush_stats(a.stats, st);
@@ -369,11 +379,12 @@ void launch_index_check(const IndexView &ix, unsigned long long *out, hipStream_
 }
 
 // ---- banded global alignment of gapped hits ---------------------------------
-// One hit per lane, 64 lanes per block; H/E rows in LDS ([j][lane]), traceback bytes in global memory.
+// One hit per lane, 64 lanes per block; H/E rows ([j][lane]) and the traceback bytes lane-interleaved in global scratch.
+// (The rows used to be (len + 2) x 64 lanes x 8 B of LDS, 26.6 KB per block at 50 bp: with that the kernel could not start
+// beside a resident search launch, which leaves no LDS (ps_budget.h), and waited for it to drain.  A wave's rows stay in L2.)
 __global__ void __launch_bounds__(64) k_refine(RefineArgs a)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    int32_t *H = reinterpret_cast<int32_t *>(smem) + threadIdx.x;
+    int32_t *H = a.hebuf + (size_t)blockIdx.x * a.he_per_block + threadIdx.x;
     int32_t *E = H + (size_t)(a.len + 2) * 64;
     uint8_t *z = a.zbuf + (size_t)blockIdx.x * a.z_per_block + threadIdx.x;
     for (int it = blockIdx.x * 64 + threadIdx.x; it < a.n_items; it += gridDim.x * 64) {
@@ -400,7 +411,7 @@ void launch_width(const WidthArgs &a, hipStream_t s)
     int blocks = (a.n_reads + 255) / 256;
     if (blocks > 256 * 8) blocks = 256 * 8;
     if (blocks < 1) blocks = 1;
-    hipLaunchKernelGGL(k_width, dim3(blocks), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_width, dim3(a.use_seed ? 2 * blocks : blocks), dim3(256), 0, s, a);      // with a seed rule: even workgroups the read's chain, odd ones its seed chain
 }
 // ---- jump table (ps_core.h): one thread per string of level d, the levels one after the other ----
 __global__ void __launch_bounds__(256) k_jump_level(BtHot h, uint32_t *table, bwtint seq_len, int d)
@@ -453,9 +464,8 @@ void launch_sa2pos(const IndexView &ix, const bwtint *rows, bwtint *out, int n, 
 }
 void launch_refine(const RefineArgs &a, int n_blocks, hipStream_t s)
 {
-    size_t lds = (size_t)(a.len + 2) * 64 * 4 * 2;
-    set_dynamic_lds(reinterpret_cast<const void *>(k_refine), "k_refine", lds);
-    hipLaunchKernelGGL(k_refine, dim3(n_blocks), dim3(64), lds, s, a);
+    if (!a.hebuf || a.he_per_block < refine_he_words(a.len)) throw std::runtime_error("k_refine: H/E scratch missing or too small");
+    hipLaunchKernelGGL(k_refine, dim3(n_blocks), dim3(64), 0, s, a);
 }
 void set_dynamic_lds(const void *kernel, const char *name, size_t bytes)
 {

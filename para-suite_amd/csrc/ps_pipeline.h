@@ -144,8 +144,9 @@ struct Batch {
     std::vector<int32_t> read_bin, read_local;
     // samse stage: classes and device records in input order; the host-finished subset
     DevBuf<uint8_t> d_class; DevBuf<uint32_t> d_eb, d_hb; DevBuf<bwtint> d_rows, d_pos; DevBuf<SelRec> d_sel; DevBuf<FinRec> d_fin;
-    PinBuf p_class, p_sel, p_fin;
+    PinBuf p_class, p_sel, p_fin, p_grp;
     uint8_t *h_class = nullptr; SelRec *h_sel = nullptr; FinRec *h_fin = nullptr;
+    uint32_t *h_grp = nullptr;     // class-1 / class-2 reads in front of every group of 64 reads (input order), pairs
     std::vector<SubRead> sub; std::vector<Multi> multis; std::vector<DevCigar> dev_cigars;
     std::vector<std::unique_ptr<PinBuf>> sub_alns;   // per bin: hit lists of the host-finished reads (stride aln_cap)
     int64_t n_class1 = 0, n_hard = 0;

@@ -10,6 +10,7 @@
 // every entry point fails.
 #include <hip/hip_runtime.h>
 #include <mutex>
+#include <optional>
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
 #include <atomic>
@@ -614,20 +615,21 @@ __global__ void k_clip_counts(const int32_t *n_aln, int aln_cap, int n, uint32_t
 }
 
 // hand-out order of a search launch: queue position -> read, heaviest estimated search first, the given (leading-base) order inside a class
-__global__ void k_order_keys(const uint8_t *est, int n, int cap, uint8_t *key, int32_t *iota)
+__global__ void k_order_keys(const uint8_t *est, int n, int cap, uint8_t *key)
 {
     for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) {
         const int e = est[r] > cap ? cap : est[r];
-        key[r] = (uint8_t)(cap - e); iota[r] = r;
+        key[r] = (uint8_t)(cap - e);
     }
 }
-
-__global__ void k_iota(int n, int32_t *iota) { for (int r = blockIdx.x * blockDim.x + threadIdx.x; r < n; r += gridDim.x * blockDim.x) iota[r] = r; }
 
 struct EvTimer {
     hipEvent_t a, b; hipStream_t s;
     explicit EvTimer(hipStream_t st) : s(st) { PS_HIP(hipEventCreate(&a)); PS_HIP(hipEventCreate(&b)); PS_HIP(hipEventRecord(a, s)); }
-    double stop() { PS_HIP(hipEventRecord(b, s)); PS_HIP(hipEventSynchronize(b)); float ms = 0; PS_HIP(hipEventElapsedTime(&ms, a, b)); return ms; }
+    double stop() { mark(); return read(); }
+    // mark(): the end is recorded and the host goes on submitting; read(): the time, once the host has a reason to wait anyway
+    void mark() { PS_HIP(hipEventRecord(b, s)); }
+    double read() { PS_HIP(hipEventSynchronize(b)); float ms = 0; PS_HIP(hipEventElapsedTime(&ms, a, b)); return ms; }
     // begin / end on the context's clock (ms since its reference event): launches of two streams that overlap in time
     void span(hipEvent_t ref, double &t_begin, double &t_end) { float x = 0, y = 0; if (ref && hipEventElapsedTime(&x, ref, a) == hipSuccess && hipEventElapsedTime(&y, ref, b) == hipSuccess) { t_begin = x; t_end = y; } }
     ~EvTimer() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
@@ -646,12 +648,15 @@ static void run_search(Batch &b, const Model &md, int n, const uint32_t *d_bases
     WidthArgs wa;
     wa.ix = ctx->ix.view; wa.n_reads = n; wa.len = len; wa.lens = d_lens; wa.seed_len = seed_len; wa.use_seed = md.use_seed;
     wa.bases = d_bases; wa.nmask = d_nmask; wa.w = w; wa.cwb = cwb; wa.cswb = cswb; wa.stats = b.d_stats.p + 0;
-    { EvTimer t(s); launch_width(wa, s); PS_HIP(hipGetLastError()); b.tm.ms_width += t.stop(); ++b.tm.n_width_launches; }
+    // width -> effort -> model -> sort -> search launch go to the stream back to back: the host reads the stage times only after
+    // the search launch's own end (a wait after every stage put a host round trip, each behind a full machine, in front of the launch)
+    std::optional<EvTimer> t_width, t_order;
+    t_width.emplace(s); launch_width(wa, s); PS_HIP(hipGetLastError()); t_width->mark(); ++b.tm.n_width_launches;
     const bool wide = launch_is_wide(md, pool_cap);
     // ---- hand-out order: the reads with the heaviest predicted search first (ps_effort.hip), so that the launch does not end on
     // them.  PS_ORDER=0 switches it off, 2 orders by the estimated best score alone (A/B runs).  Narrow launches only: the wide
-    // stack takes its reads in queue order and never reads the estimate (its budget can also pass what k_effort_model's
-    // per-lane LDS holds: -X 10 and up)
+    // stack takes its reads in queue order and never reads the estimate (its budget can also pass the 63 units k_effort_model
+    // has lanes for: -X 10 and up)
     const int32_t *d_order = nullptr; const uint8_t *d_est = nullptr; const uint16_t *d_est_ab = nullptr;
     if (!wide) {
         const char *eo = std::getenv("PS_ORDER");
@@ -659,9 +664,9 @@ static void run_search(Batch &b, const Model &md, int n, const uint32_t *d_bases
         int min_n = 4096;                                     // below that every read has a lane to itself at once: no order to choose
         if (const char *e = std::getenv("PS_ORDER_MIN")) min_n = std::max(1, std::atoi(e));      // tests: the small launches of the fuzz sweep too
         if (mode > 0 && n >= min_n && md.max_units >= md.c_min) {      // a search that can afford no difference is ~len steps for every read: nothing to order
-            EvTimer t(s);
-            uint8_t *est = wk->ws_get<uint8_t>("est", (size_t)n), *key = wk->ws_get<uint8_t>("okey", (size_t)n), *key2 = wk->ws_get<uint8_t>("okey2", (size_t)n);
-            int32_t *iota = wk->ws_get<int32_t>("oiota", (size_t)n), *order = wk->ws_get<int32_t>("order", (size_t)n);
+            t_order.emplace(s);
+            uint8_t *est = wk->ws_get<uint8_t>("est", (size_t)n), *key = wk->ws_get<uint8_t>("okey", (size_t)n);
+            int32_t *order = wk->ws_get<int32_t>("order", (size_t)n);
             EffortArgs ea;
             ea.ix = ctx->ix.view; ea.n_reads = n; ea.len = len; ea.lens = d_lens; ea.bases = d_bases; ea.nmask = d_nmask; ea.est = est;
             // everything here is in BUDGET UNITS (what the search's limits are in): the profile model has units == score, stock counts
@@ -677,12 +682,10 @@ static void run_search(Batch &b, const Model &md, int n, const uint32_t *d_bases
             ea.est_ab = ctx->want_read_iters ? wk->ws_get<uint16_t>("est_ab", (size_t)n) : nullptr;
             launch_effort(ea, s);
             d_est_ab = ea.est_ab;
-            int bits = 8;
             if (mode == 2) {
                 int cap = 255;
                 if (const char *e = std::getenv("PS_ORDER_CAP")) cap = std::max(1, std::min(255, std::atoi(e)));
-                bits = 1; while ((1 << bits) <= cap) ++bits;
-                hipLaunchKernelGGL(k_order_keys, dim3(std::min((n + 255) / 256, 4096)), dim3(256), 0, s, est, n, cap, key, iota);
+                hipLaunchKernelGGL(k_order_keys, dim3(std::min((n + 255) / 256, 4096)), dim3(256), 0, s, est, n, cap, key);
             } else {
                 EffortModelArgs em;
                 em.n_reads = n; em.len = len; em.lens = d_lens; em.units_by_len = nullptr; em.bases = d_bases; em.nmask = d_nmask; em.cwb = cwb; em.est = est;
@@ -701,14 +704,12 @@ static void run_search(Batch &b, const Model &md, int n, const uint32_t *d_bases
                 }
                 em.key = key; em.pred = nullptr;
                 launch_effort_model(em, s);
-                hipLaunchKernelGGL(k_iota, dim3(std::min((n + 255) / 256, 4096)), dim3(256), 0, s, n, iota);
             }
-            size_t tb = 0;
-            PS_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tb, key, key2, iota, order, n, 0, bits, s));
-            uint8_t *tmp = wk->ws_get<uint8_t>("order_tmp", tb ? tb : 1);
-            PS_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tb, key, key2, iota, order, n, 0, bits, s));
+            // stable: the given (leading-base) order inside a class.  A counting sort of our own: the library's radix sort kernels (20 KB
+            // of LDS, 100 VGPRs) do not start beside the other batch's resident search launch (ps_budget.h)
+            launch_order_sort(key, n, wk->ws_get<uint32_t>("order_tmp", order_sort_tmp_words(n)), order, s);
             PS_HIP(hipGetLastError());
-            b.tm.ms_width += t.stop();                                        // reported with the width stage: both prepare the search
+            t_order->mark();
             d_order = order; d_est = est;
         }
     }
@@ -763,6 +764,8 @@ static void run_search(Batch &b, const Model &md, int n, const uint32_t *d_bases
       if (!launch_backtrack(a, wk->ws_get<BtArgs>("btargs", 1), wk->pin_get<BtArgs>("btargs_h", 1), blocks, lm, s, ctx->want_kstats || ctx->want_read_iters)) throw Error("cost model outside the ranges the search kernel packs (gap/score fields must fit a byte)");
       PS_HIP(hipGetLastError());
       const double ms = t.stop(); b.tm.ms_backtrack += ms; ++b.tm.n_backtrack_launches;
+      b.tm.ms_width += t_width->read();
+      if (t_order) b.tm.ms_width += t_order->read();                    // reported with the width stage: both prepare the search
       { double t0_ = 0, t1_ = 0; t.span(ctx->ref_event, t0_, t1_); if (b.tm.n_backtrack_launches == 1) b.tm.bt_begin_ms = t0_; b.tm.bt_end_ms = t1_; }
       if (std::getenv("PS_VERBOSE")) std::fprintf(stderr, "[parasuite-hip]   backtrack launch: %d reads x %d bp, stack %u%s, %d lanes, %.1f ms\n", n, len, pool_cap, wide ? " (wide)" : "", n_lanes, ms); }
     if (ctx->want_read_iters) { ctx->read_iters.resize((size_t)n * PS_RI_WORDS); PS_HIP(hipMemcpyAsync(ctx->read_iters.data(), riters, (size_t)n * PS_RI_WORDS * 4, hipMemcpyDeviceToHost, s)); PS_HIP(hipStreamSynchronize(s)); }
@@ -823,13 +826,6 @@ __global__ void k_classify(const AlnRec *alns, int aln_cap, const int32_t *n_aln
             }
         }
         cls_out[ids[r]] = c;
-    }
-}
-__global__ void k_class_flags(const uint8_t *cls, long long n, uint32_t *is1, uint32_t *is2)
-{
-    for (long long g = (long long)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (long long)gridDim.x * blockDim.x) {
-        const int c = cls[g] & 3;
-        is1[g] = c == 1; is2[g] = c == 2;
     }
 }
 __global__ void k_gather_sub(const AlnRec *alns, int aln_cap, const int32_t *n_aln, const int32_t *local, int m, AlnRec *out, int32_t *n_out)
@@ -1093,11 +1089,14 @@ void batch_search(Batch &b)
         for (int t = 0; t < nt; ++t) { ce[t + 1] += ce[t]; ch[t + 1] += ch[t]; cs[t + 1] += cs[t]; }
         b.n_class1 = ce[nt]; b.n_hard = ch[nt];
         b.sub.resize((size_t)cs[nt]);
-        // pass 2: the subset with its position in the tie-break stream
+        // pass 2: the subset with its position in the tie-break stream, and the two counts in front of every group of 64 reads
+        // (batch_select_easy: the device adds the rank inside a group)
+        b.h_grp = (uint32_t *)b.p_grp.get((((size_t)N + 63) / 64 * 2 + 2) * sizeof(uint32_t));
         par_for((size_t)N, ctx->host_threads, [&](size_t g0, size_t g1, int t) {
             int64_t e = ce[t], h = ch[t]; size_t q = (size_t)cs[t];
             for (size_t g = g0; g < g1; ++g) {
                 const uint8_t c = b.h_class[g];
+                if ((g & 63) == 0) { b.h_grp[2 * (g >> 6)] = (uint32_t)e; b.h_grp[2 * (g >> 6) + 1] = (uint32_t)h; }
                 if (c & PS_CLS_HOST) { SubRead &sr = b.sub[q++]; sr = SubRead(); sr.g = (int64_t)g; sr.cls = c & 3; sr.easy_before = e; sr.hard_before = h; }
                 e += (c & 3) == 1; h += (c & 3) == 2;
             }
@@ -1215,13 +1214,13 @@ void batch_select_easy(Batch &b, int threads)
     if (b.d_sel.n < (size_t)N) { b.d_sel.alloc((size_t)N); b.d_fin.alloc((size_t)N); b.d_rows.alloc((size_t)N + 1); b.d_pos.alloc((size_t)N + 1); b.d_eb.alloc((size_t)N); b.d_hb.alloc((size_t)N); }
     const double ms_alloc = ms_since(t0);
     {
-        uint32_t *f1 = wk->ws_get<uint32_t>("flag1", (size_t)N), *f2 = wk->ws_get<uint32_t>("flag2", (size_t)N);
-        hipLaunchKernelGGL(k_class_flags, dim3(2048), dim3(256), 0, s, b.d_class.p, (long long)N, f1, f2);
-        size_t tb = 0;
-        PS_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, tb, f1, b.d_eb.p, (size_t)N, s));
-        uint8_t *tmp = wk->ws_get<uint8_t>("scan_tmp", tb ? tb : 1);
-        PS_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, f1, b.d_eb.p, (size_t)N, s));
-        PS_HIP(hipcub::DeviceScan::ExclusiveSum(tmp, tb, f2, b.d_hb.p, (size_t)N, s));
+        // the counts in front of every group of 64 reads come from the host (batch_search, which has the classes in input order);
+        // the kernel adds the rank inside the group.  (Two library scans over 10 M flag words did this: their kernels keep 17 KB of
+        // LDS and waited for the other batch's resident search launch to drain, ps_budget.h.)
+        const size_t n_grp = ((size_t)N + 63) / 64;
+        uint32_t *d_grp = wk->ws_get<uint32_t>("class_grp", 2 * n_grp + 2);
+        PS_HIP(hipMemcpyAsync(d_grp, b.h_grp, 2 * n_grp * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        launch_class_ranks(b.d_class.p, (long long)N, d_grp, b.d_eb.p, b.d_hb.p, s);
     }
     unsigned long long *d_cum = wk->ws_get<unsigned long long>("hard_cum", (size_t)b.n_hard + 1);
     if (b.n_hard) PS_HIP(hipMemcpyAsync(d_cum, b.hard_draws_cum.data(), (size_t)b.n_hard * 8, hipMemcpyHostToDevice, s));
@@ -1319,11 +1318,14 @@ static void run_refine(Batch &b, Bin &bin, const RefineItem *d_items, int n_it, 
     ra.bases = bin.bases.p; ra.nmask = bin.nmask.p; ra.items = d_items; ra.cigar = d_cig; ra.n_cigar = d_nc;
     ra.z_per_block = (size_t)64 * tmax * (bin.len < 2 * tmax + 1 ? bin.len : 2 * tmax + 1);
     ra.zbuf = wk->ws_get<uint8_t>("rf_z", ra.z_per_block * blocks);
-    { EvTimer t(s); launch_refine(ra, blocks, s); PS_HIP(hipGetLastError()); b.tm.ms_refine += t.stop(); }
+    ra.he_per_block = refine_he_words(bin.len);
+    ra.hebuf = wk->ws_get<int32_t>("rf_he", ra.he_per_block * blocks);
+    EvTimer t(s); launch_refine(ra, blocks, s); PS_HIP(hipGetLastError()); t.mark();
     cig.resize((size_t)n_it * PS_MAX_CIGAR); nc.resize(n_it);
     PS_HIP(hipMemcpyAsync(cig.data(), d_cig, cig.size() * 4, hipMemcpyDeviceToHost, s));
     PS_HIP(hipMemcpyAsync(nc.data(), d_nc, (size_t)n_it * 4, hipMemcpyDeviceToHost, s));
     PS_HIP(hipStreamSynchronize(s));
+    b.tm.ms_refine += t.read();
 }
 
 void batch_locate(Batch &b)
@@ -1334,7 +1336,8 @@ void batch_locate(Batch &b)
     const int64_t N = b.rs.n, l_pac = ctx->ix.ref.l_pac;
     auto t0 = Clock::now();
     // ---- device-finished reads: SA walk, strand / MAPQ, queue of gapped hits ----
-    { EvTimer t(s); launch_sa2pos(ctx->ix.view, b.d_rows.p, b.d_pos.p, (int)N, b.d_stats.p + 2, s); PS_HIP(hipGetLastError()); b.tm.ms_sa2pos += t.stop(); }
+    // (the SA walk, k_post and the downloads go to the stream back to back; the walk's time is read after the one wait behind them)
+    EvTimer t_sa(s); launch_sa2pos(ctx->ix.view, b.d_rows.p, b.d_pos.p, (int)N, b.d_stats.p + 2, s); PS_HIP(hipGetLastError()); t_sa.mark();
     uint8_t logn[256];
     mapq_logn_table(logn);
     uint8_t *d_logn = wk->ws_get<uint8_t>("logn", 256);
@@ -1365,6 +1368,7 @@ void batch_locate(Batch &b)
     PS_HIP(hipMemcpyAsync(b.h_sel, b.d_sel.p, (size_t)N * sizeof(SelRec), hipMemcpyDeviceToHost, s));
     PS_HIP(hipMemcpyAsync(b.h_fin, b.d_fin.p, (size_t)N * sizeof(FinRec), hipMemcpyDeviceToHost, s));
     PS_HIP(hipStreamSynchronize(s));
+    b.tm.ms_sa2pos += t_sa.read();
     PS_HIP(hipMemcpy(&b.st_sa2pos, b.d_stats.p + 2, sizeof(KStats), hipMemcpyDeviceToHost));
     for (size_t bi = 0; bi < b.bins.size(); ++bi) {            // gapped device-finished hits: banded DP, CIGAR clean-up
         BinItems &it = bi_items[bi];

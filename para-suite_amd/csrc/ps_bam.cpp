@@ -18,11 +18,10 @@
 #include <thread>
 #include <vector>
 #include "ps_bam.h"
+#include "ps_error.h"
 
 namespace ps {
 namespace {
-
-struct Err : std::runtime_error { explicit Err(const std::string &m) : std::runtime_error(m) {} };
 
 inline void put32(std::string &o, uint32_t v) { char b[4] = {(char)(v & 0xff), (char)((v >> 8) & 0xff), (char)((v >> 16) & 0xff), (char)(v >> 24)}; o.append(b, 4); }
 inline void put16(std::string &o, uint16_t v) { char b[2] = {(char)(v & 0xff), (char)(v >> 8)}; o.append(b, 2); }
@@ -64,20 +63,20 @@ static bool encode_line(const char *line, size_t n, const std::map<std::string, 
         size_t j = e ? (size_t)(e - line) : n;
         f[k].p = line + i; f[k].n = j - i; ++k;
         i = j < n ? j + 1 : n;
-        if (!e && k < 11) throw Err("SAM line with fewer than 11 fields: " + std::string(line, std::min<size_t>(n, 80)));
+        if (!e && k < 11) throw Error("SAM line with fewer than 11 fields: " + std::string(line, std::min<size_t>(n, 80)));
     }
     const long flag = to_long(f[1]), pos1 = to_long(f[3]), mapq = to_long(f[4]), pnext1 = to_long(f[7]), tlen = to_long(f[8]);
     if (mapq < min_mapq) return false;
     int ref = -1, rnext = -1;
     if (!(f[2].n == 1 && f[2].p[0] == '*')) {
         auto it = ref_id.find(std::string(f[2].p, f[2].n));
-        if (it == ref_id.end()) throw Err("reference name not in the header: " + std::string(f[2].p, f[2].n));
+        if (it == ref_id.end()) throw Error("reference name not in the header: " + std::string(f[2].p, f[2].n));
         ref = it->second;
     }
     if (f[6].n == 1 && f[6].p[0] == '=') rnext = ref;
     else if (!(f[6].n == 1 && f[6].p[0] == '*')) {
         auto it = ref_id.find(std::string(f[6].p, f[6].n));
-        if (it == ref_id.end()) throw Err("mate reference name not in the header");
+        if (it == ref_id.end()) throw Error("mate reference name not in the header");
         rnext = it->second;
     }
     // CIGAR
@@ -90,7 +89,7 @@ static bool encode_line(const char *line, size_t n, const std::map<std::string, 
             if (ch >= '0' && ch <= '9') { num = num * 10 + (uint32_t)(ch - '0'); any = true; continue; }
             static const char ops[] = "MIDNSHP=X";
             const char *w = std::strchr(ops, ch);
-            if (!w || !any) throw Err("bad CIGAR: " + std::string(f[5].p, f[5].n));
+            if (!w || !any) throw Error("bad CIGAR: " + std::string(f[5].p, f[5].n));
             const int op = (int)(w - ops);
             cig.push_back((num << 4) | (uint32_t)op);
             if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += num;
@@ -101,23 +100,16 @@ static bool encode_line(const char *line, size_t n, const std::map<std::string, 
     const int64_t end = pos + (ref_len > 0 ? ref_len : 1);
     const bool has_seq = !(f[9].n == 1 && f[9].p[0] == '*');
     const uint32_t l_seq = has_seq ? (uint32_t)f[9].n : 0;
-    const size_t start = o.size();
-    put32(o, 0);                                            // block_size, patched below
-    put32(o, (uint32_t)ref); put32(o, (uint32_t)pos);
-    o.push_back((char)(uint8_t)(f[0].n + 1)); o.push_back((char)(uint8_t)mapq);
-    put16(o, (uint16_t)reg2bin(pos, end));
-    put16(o, (uint16_t)cig.size()); put16(o, (uint16_t)flag);
-    put32(o, l_seq); put32(o, (uint32_t)rnext); put32(o, (uint32_t)((int32_t)pnext1 - 1)); put32(o, (uint32_t)(int32_t)tlen);
-    if (f[0].n > 254) throw Err("read name longer than 254 characters");
-    o.append(f[0].p, f[0].n); o.push_back('\0');
-    for (uint32_t c : cig) put32(o, c);
+    BamCore core{ref, pos, end, (int)mapq, (int)flag, (uint32_t)cig.size(), l_seq, rnext, (int32_t)pnext1 - 1, (int32_t)tlen};
+    bam_rec_begin(o, core, f[0].p, f[0].n, r);
+    bam_rec_cigar(o, cig.data(), cig.size());
     for (uint32_t c = 0; c < l_seq; c += 2) {
         const int hi = base4(f[9].p[c]), lo = c + 1 < l_seq ? base4(f[9].p[c + 1]) : 0;
         o.push_back((char)(uint8_t)((hi << 4) | lo));
     }
     if (f[10].n == 1 && f[10].p[0] == '*') o.append((size_t)l_seq, (char)0xff);
     else {
-        if (f[10].n != l_seq) throw Err("SEQ and QUAL of different length");
+        if (f[10].n != l_seq) throw Error("SEQ and QUAL of different length");
         for (uint32_t c = 0; c < l_seq; ++c) o.push_back((char)(uint8_t)(f[10].p[c] - 33));
     }
     // optional fields TAG:TYPE:VALUE
@@ -127,28 +119,15 @@ static bool encode_line(const char *line, size_t n, const std::map<std::string, 
         const char *t = line + i; const size_t tn = j - i;
         i = j < n ? j + 1 : n;
         if (tn == 0) continue;
-        if (tn < 5 || t[2] != ':' || t[4] != ':') throw Err("bad optional field: " + std::string(t, tn));
-        o.push_back(t[0]); o.push_back(t[1]);
+        if (tn < 5 || t[2] != ':' || t[4] != ':') throw Error("bad optional field: " + std::string(t, tn));
         const char ty = t[3]; const char *v = t + 5; const size_t vn = tn - 5;
-        if (ty == 'A') { o.push_back('A'); o.push_back(vn ? v[0] : ' '); }
-        else if (ty == 'i') {
-            const long long x = std::strtoll(std::string(v, vn).c_str(), nullptr, 10);
-            if (x < 0) {
-                if (x >= -128) { o.push_back('c'); o.push_back((char)(int8_t)x); }
-                else if (x >= -32768) { o.push_back('s'); put16(o, (uint16_t)(int16_t)x); }
-                else { o.push_back('i'); put32(o, (uint32_t)(int32_t)x); }
-            } else {
-                if (x <= 255) { o.push_back('C'); o.push_back((char)(uint8_t)x); }
-                else if (x <= 65535) { o.push_back('S'); put16(o, (uint16_t)x); }
-                else { o.push_back('I'); put32(o, (uint32_t)x); }
-            }
-        } else if (ty == 'f') { o.push_back('f'); float fl = std::strtof(std::string(v, vn).c_str(), nullptr); uint32_t u; std::memcpy(&u, &fl, 4); put32(o, u); }
-        else if (ty == 'Z' || ty == 'H') { o.push_back(ty); o.append(v, vn); o.push_back('\0'); }
-        else throw Err(std::string("optional field type not supported: ") + ty);
+        if (ty == 'A') bam_tag_char(o, t, vn ? v[0] : ' ');
+        else if (ty == 'i') bam_tag_int(o, t, std::strtoll(std::string(v, vn).c_str(), nullptr, 10));
+        else if (ty == 'f') { o.append(t, 2); o.push_back('f'); float fl = std::strtof(std::string(v, vn).c_str(), nullptr); uint32_t u; std::memcpy(&u, &fl, 4); put32(o, u); }
+        else if (ty == 'Z' || ty == 'H') bam_tag_text(o, t, ty, v, vn);
+        else throw Error(std::string("optional field type not supported: ") + ty);
     }
-    const uint32_t bs = (uint32_t)(o.size() - start - 4);
-    o[start] = (char)(bs & 0xff); o[start + 1] = (char)((bs >> 8) & 0xff); o[start + 2] = (char)((bs >> 16) & 0xff); o[start + 3] = (char)(bs >> 24);
-    r.ref = ref; r.pos = pos; r.end = (int32_t)end; r.flag = (uint32_t)flag; r.off = start; r.len = o.size() - start;
+    bam_rec_end(o, r);
     return true;
 }
 
@@ -158,14 +137,14 @@ static void bgzf_block(const char *src, size_t n, int level, std::string &out)
     static const unsigned char head[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0};
     std::vector<unsigned char> buf(n + n / 100 + 64);
     z_stream zs; std::memset(&zs, 0, sizeof zs);
-    if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw Err("deflateInit2 failed");
+    if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw Error("deflateInit2 failed");
     zs.next_in = (Bytef *)const_cast<char *>(src); zs.avail_in = (uInt)n;
     zs.next_out = buf.data(); zs.avail_out = (uInt)buf.size();
-    if (deflate(&zs, Z_FINISH) != Z_STREAM_END) { deflateEnd(&zs); throw Err("deflate failed"); }
+    if (deflate(&zs, Z_FINISH) != Z_STREAM_END) { deflateEnd(&zs); throw Error("deflate failed"); }
     const size_t cn = zs.total_out;
     deflateEnd(&zs);
     const size_t total = 18 + cn + 8;
-    if (total > 65536) throw Err("BGZF block too large");
+    if (total > 65536) throw Error("BGZF block too large");
     out.append((const char *)head, 16);
     put16(out, (uint16_t)(total - 1));
     out.append((const char *)buf.data(), cn);
@@ -182,7 +161,7 @@ template <class F> static void par(int n, int threads, F f)
         for (int t = 0; t < threads && next < n; ++t, ++next) { const int id = next; th.emplace_back([&, id]() { try { f(id); } catch (const std::exception &e) { err[id] = e.what(); if (err[id].empty()) err[id] = "error"; } }); }
         for (auto &x : th) x.join();
     }
-    for (auto &e : err) if (!e.empty()) throw Err(e);
+    for (auto &e : err) if (!e.empty()) throw Error(e);
 }
 
 }  // namespace
@@ -210,10 +189,10 @@ static void header_sorted(std::string &text, const char *so)
 static void load_sam(const char *sam_path, int min_mapq, int threads, Data &d)
 {
     FILE *f = std::fopen(sam_path, "rb");
-    if (!f) throw Err(std::string("cannot open ") + sam_path);
+    if (!f) throw Error(std::string("cannot open ") + sam_path);
     std::fseek(f, 0, SEEK_END); const long sz = std::ftell(f); std::fseek(f, 0, SEEK_SET);
     std::vector<char> buf((size_t)sz + 1);
-    if (sz && std::fread(buf.data(), 1, (size_t)sz, f) != (size_t)sz) { std::fclose(f); throw Err(std::string("short read on ") + sam_path); }
+    if (sz && std::fread(buf.data(), 1, (size_t)sz, f) != (size_t)sz) { std::fclose(f); throw Error(std::string("short read on ") + sam_path); }
     std::fclose(f);
     const size_t n = (size_t)sz; const char *b = buf.data();
     std::map<std::string, int> ref_id;
@@ -231,7 +210,7 @@ static void load_sam(const char *sam_path, int min_mapq, int threads, Data &d)
                 else if (line.compare(p, 3, "LN:") == 0) ln = std::strtol(line.substr(p + 3, q - p - 3).c_str(), nullptr, 10);
                 p = q + 1;
             }
-            if (name.empty() || ln <= 0) throw Err("bad @SQ line: " + line);
+            if (name.empty() || ln <= 0) throw Error("bad @SQ line: " + line);
             ref_id[name] = (int)d.refs.size(); d.refs.emplace_back(name, (uint32_t)ln);
         }
         d.text += line; d.text.push_back('\n');
@@ -274,18 +253,18 @@ struct Blocks { std::string data; std::vector<std::pair<uint64_t, uint64_t>> sta
 static void inflate_bgzf(const char *path, int threads, Blocks &out)
 {
     FILE *f = std::fopen(path, "rb");
-    if (!f) throw Err(std::string("cannot open ") + path);
+    if (!f) throw Error(std::string("cannot open ") + path);
     std::fseek(f, 0, SEEK_END); const long sz = std::ftell(f); std::fseek(f, 0, SEEK_SET);
     std::vector<unsigned char> raw((size_t)sz);
-    if (sz && std::fread(raw.data(), 1, (size_t)sz, f) != (size_t)sz) { std::fclose(f); throw Err(std::string("short read on ") + path); }
+    if (sz && std::fread(raw.data(), 1, (size_t)sz, f) != (size_t)sz) { std::fclose(f); throw Error(std::string("short read on ") + path); }
     std::fclose(f);
     out.file_bytes = (uint64_t)sz;
     struct B { size_t at, bsize; uint32_t isize; uint64_t u; };
     std::vector<B> bl; size_t at = 0; uint64_t u = 0;
     while (at < raw.size()) {
-        if (at + 28 > raw.size() || raw[at] != 31 || raw[at + 1] != 139 || raw[at + 12] != 'B' || raw[at + 13] != 'C') throw Err(std::string("not a BGZF file: ") + path);
+        if (at + 28 > raw.size() || raw[at] != 31 || raw[at + 1] != 139 || raw[at + 12] != 'B' || raw[at + 13] != 'C') throw Error(std::string("not a BGZF file: ") + path);
         const size_t bsize = (size_t)(raw[at + 16] | (raw[at + 17] << 8)) + 1;
-        if (at + bsize > raw.size()) throw Err(std::string("truncated BGZF block in ") + path);
+        if (at + bsize > raw.size()) throw Error(std::string("truncated BGZF block in ") + path);
         const unsigned char *t = raw.data() + at + bsize - 4;
         const uint32_t isize = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
         bl.push_back(B{at, bsize, isize, u});
@@ -300,12 +279,12 @@ static void inflate_bgzf(const char *path, int threads, Blocks &out)
             const B &b = bl[k];
             if (!b.isize) continue;
             z_stream zs; std::memset(&zs, 0, sizeof zs);
-            if (inflateInit2(&zs, -15) != Z_OK) throw Err("inflateInit2 failed");
+            if (inflateInit2(&zs, -15) != Z_OK) throw Error("inflateInit2 failed");
             zs.next_in = raw.data() + b.at + 18; zs.avail_in = (uInt)(b.bsize - 26);
             zs.next_out = (Bytef *)&out.data[(size_t)b.u]; zs.avail_out = b.isize;
             const int rc = inflate(&zs, Z_FINISH);
             inflateEnd(&zs);
-            if (rc != Z_STREAM_END || zs.total_out != b.isize) throw Err(std::string("corrupt BGZF block in ") + path);
+            if (rc != Z_STREAM_END || zs.total_out != b.isize) throw Error(std::string("corrupt BGZF block in ") + path);
         }
     });
 }
@@ -317,7 +296,7 @@ static void load_bam(const char *path, int threads, Data &d, Blocks *keep_blocks
     Blocks local; Blocks &bk = keep_blocks ? *keep_blocks : local;
     inflate_bgzf(path, threads, bk);
     const std::string &s = bk.data;
-    if (s.size() < 12 || s.compare(0, 4, "BAM\1") != 0) throw Err(std::string("not a BAM file: ") + path);
+    if (s.size() < 12 || s.compare(0, 4, "BAM\1") != 0) throw Error(std::string("not a BAM file: ") + path);
     const uint32_t l_text = rd32(s, 4);
     d.text = s.substr(8, l_text);
     while (!d.text.empty() && d.text.back() == '\0') d.text.pop_back();
@@ -335,7 +314,7 @@ static void load_bam(const char *path, int threads, Data &d, Blocks *keep_blocks
     size_t p = 0;
     while (p + 4 <= e.size()) {
         const uint32_t bs = rd32(e, p);
-        if (bs < 32 || p + 4 + bs > e.size()) throw Err(std::string("corrupt BAM record in ") + path);
+        if (bs < 32 || p + 4 + bs > e.size()) throw Error(std::string("corrupt BAM record in ") + path);
         Rec r; r.part = 0; r.off = p; r.len = 4 + (size_t)bs;
         r.ref = (int32_t)rd32(e, p + 4); r.pos = (int32_t)rd32(e, p + 8);
         const uint32_t w = rd32(e, p + 12), fl = rd32(e, p + 16);
@@ -386,7 +365,7 @@ static void write_bai(const std::string &bai_path, const Data &d, const Layout &
     for (size_t i = 0; i < d.recs.size(); ++i) {
         const Rec &r = d.recs[i];
         if (r.ref < 0) { ++n_no_coor; continue; }
-        if ((size_t)r.ref >= idx.size()) throw Err("record refers to a reference that is not in the header");
+        if ((size_t)r.ref >= idx.size()) throw Error("record refers to a reference that is not in the header");
         RefIdx &x = idx[(size_t)r.ref];
         const uint64_t vb = lay.vbeg[i], ve = lay.vend[i];
         if (!x.any) { x.beg = vb; x.any = true; }
@@ -415,10 +394,10 @@ static void write_bai(const std::string &bai_path, const Data &d, const Layout &
     }
     put64(bai, n_no_coor);
     FILE *bi = std::fopen(bai_path.c_str(), "wb");
-    if (!bi) throw Err("cannot write " + bai_path);
+    if (!bi) throw Error("cannot write " + bai_path);
     bool ok = std::fwrite(bai.data(), 1, bai.size(), bi) == bai.size();
     ok = (std::fclose(bi) == 0) && ok;
-    if (!ok) throw Err("short write on " + bai_path);
+    if (!ok) throw Error("short write on " + bai_path);
 }
 
 // ---- Data (records in d.recs order) -> BGZF file (+ .bai)
@@ -455,12 +434,12 @@ static void write_bam(Data &d, const char *bam_path, bool write_index, int threa
     for (size_t k = 0; k < n_blocks; ++k) coff[k + 1] = coff[k] + comp[k].size();
     static const unsigned char eof_block[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     FILE *o = std::fopen(bam_path, "wb");
-    if (!o) throw Err(std::string("cannot write ") + bam_path);
+    if (!o) throw Error(std::string("cannot write ") + bam_path);
     bool ok = true;
     for (size_t k = 0; k < n_blocks && ok; ++k) ok = std::fwrite(comp[k].data(), 1, comp[k].size(), o) == comp[k].size();
     ok = ok && std::fwrite(eof_block, 1, 28, o) == 28;
     ok = (std::fclose(o) == 0) && ok;
-    if (!ok) throw Err(std::string("short write on ") + bam_path);
+    if (!ok) throw Error(std::string("short write on ") + bam_path);
     if (stats) { stats->n_in = d.n_in; stats->n_out = all.size(); stats->bam_bytes = coff[n_blocks] + 28; }
     if (!write_index) return;
     auto voff = [&](uint64_t u) -> uint64_t {           // virtual file offset of body byte u
@@ -491,7 +470,49 @@ static void sort_records(Data &d, bool by_name)
 
 static int clamp_threads(int t) { return t < 1 ? 1 : (t > 64 ? 64 : t); }
 
-int bam_reg2bin(int64_t beg, int64_t end) { return reg2bin(beg, end); }
+// these run once per field of every record of ps_map_to_bam: raw stores into storage grown once per call, no append per byte
+static inline void st16(char *d, uint32_t v) { d[0] = (char)(v & 0xff); d[1] = (char)((v >> 8) & 0xff); }
+static inline void st32(char *d, uint32_t v) { st16(d, v); st16(d + 2, v >> 16); }
+static inline char *grow(std::string &o, size_t n) { const size_t at = o.size(); o.resize(at + n); return &o[at]; }
+void bam_rec_begin(std::string &o, const BamCore &c, const char *name, size_t name_len, BamRec &r)
+{
+    if (name_len > 254) throw Error("read name longer than 254 characters");
+    r.ref = c.ref; r.pos = c.pos; r.end = (int32_t)c.end; r.flag = (uint32_t)c.flag; r.off = o.size(); r.len = 0;
+    char *d = grow(o, 36 + name_len + 1);
+    st32(d, 0);                                             // block_size: bam_rec_end
+    st32(d + 4, (uint32_t)c.ref); st32(d + 8, (uint32_t)c.pos);
+    d[12] = (char)(uint8_t)(name_len + 1); d[13] = (char)(uint8_t)c.mapq;
+    st16(d + 14, (uint32_t)reg2bin(c.pos, c.end));
+    st16(d + 16, c.n_cigar); st16(d + 18, (uint32_t)c.flag);
+    st32(d + 20, c.l_seq); st32(d + 24, (uint32_t)c.rnext); st32(d + 28, (uint32_t)c.pnext); st32(d + 32, (uint32_t)c.tlen);
+    std::memcpy(d + 36, name, name_len); d[36 + name_len] = '\0';
+}
+void bam_rec_cigar(std::string &o, const uint32_t *words, size_t n) { char *d = grow(o, 4 * n); for (size_t j = 0; j < n; ++j) st32(d + 4 * j, words[j]); }
+void bam_tag_int(std::string &o, const char *tag, long long v)
+{
+    char t[7] = {tag[0], tag[1]}; size_t n;
+    if (v < 0) {
+        if (v >= -128) { t[2] = 'c'; t[3] = (char)(int8_t)v; n = 4; }
+        else if (v >= -32768) { t[2] = 's'; st16(t + 3, (uint32_t)(uint16_t)(int16_t)v); n = 5; }
+        else { t[2] = 'i'; st32(t + 3, (uint32_t)(int32_t)v); n = 7; }
+    } else if (v <= 255) { t[2] = 'C'; t[3] = (char)(uint8_t)v; n = 4; }
+    else if (v <= 65535) { t[2] = 'S'; st16(t + 3, (uint32_t)v); n = 5; }
+    else { t[2] = 'I'; st32(t + 3, (uint32_t)v); n = 7; }
+    o.append(t, n);
+}
+void bam_tag_char(std::string &o, const char *tag, char v) { const char t[4] = {tag[0], tag[1], 'A', v}; o.append(t, 4); }
+void bam_tag_text_open(std::string &o, const char *tag, char type) { const char t[3] = {tag[0], tag[1], type}; o.append(t, 3); }
+void bam_tag_text_close(std::string &o) { o.push_back('\0'); }
+void bam_tag_text(std::string &o, const char *tag, char type, const char *v, size_t n)
+{
+    char *d = grow(o, 3 + n + 1);
+    d[0] = tag[0]; d[1] = tag[1]; d[2] = type; std::memcpy(d + 3, v, n); d[3 + n] = '\0';
+}
+void bam_rec_end(std::string &o, BamRec &r)
+{
+    r.len = o.size() - r.off;
+    st32(&o[r.off], (uint32_t)(r.len - 4));
+}
 
 // ---- records straight from memory (ps_map_to_bam)
 struct BamSink::Impl {
@@ -501,12 +522,12 @@ struct BamSink::Impl {
 BamSink::BamSink(const std::string &header_text, const std::vector<std::pair<std::string, uint32_t>> &refs, const char *bam_path,
                  bool sort_by_coordinate, bool write_index, int threads, int level) : p(new Impl())
 {
-    if (write_index && !sort_by_coordinate) { delete p; p = nullptr; throw Err("a .bai index needs coordinate-sorted output"); }
+    if (write_index && !sort_by_coordinate) { delete p; p = nullptr; throw Error("a .bai index needs coordinate-sorted output"); }
     p->d.text = header_text; p->d.refs = refs; p->path = bam_path; p->sort = sort_by_coordinate; p->index = write_index;
     p->threads = clamp_threads(threads); p->level = level < 0 ? 0 : (level > 9 ? 9 : level);
     if (p->sort) { header_sorted(p->d.text, "coordinate"); return; }
     p->f = std::fopen(bam_path, "wb");
-    if (!p->f) { const std::string m = std::string("cannot write ") + bam_path; delete p; p = nullptr; throw Err(m); }
+    if (!p->f) { const std::string m = std::string("cannot write ") + bam_path; delete p; p = nullptr; throw Error(m); }
     std::string head;
     head.append("BAM\1", 4); put32(head, (uint32_t)p->d.text.size()); head += p->d.text; put32(head, (uint32_t)p->d.refs.size());
     for (auto &r : p->d.refs) { put32(head, (uint32_t)r.first.size() + 1); head += r.first; head.push_back('\0'); put32(head, r.second); }
@@ -552,14 +573,14 @@ void BamSink::finish(BamStats *stats)
     bool ok = !p->failed && std::fwrite(eof_block, 1, 28, p->f) == 28;
     ok = (std::fclose(p->f) == 0) && ok;
     p->f = nullptr;
-    if (!ok) throw Err(std::string("short write on ") + p->path);
+    if (!ok) throw Error(std::string("short write on ") + p->path);
     if (stats) { stats->n_in = p->d.n_in; stats->n_out = p->n_out; stats->bam_bytes = p->bytes + 28; }
 }
 
 void sam_to_bam(const char *sam_path, const char *bam_path, int min_mapq, bool sort_by_coordinate, bool write_index, int threads, BamStats *stats)
 {
     threads = clamp_threads(threads);
-    if (write_index && !sort_by_coordinate) throw Err("a .bai index needs coordinate-sorted output");
+    if (write_index && !sort_by_coordinate) throw Error("a .bai index needs coordinate-sorted output");
     Data d;
     load_sam(sam_path, min_mapq, threads, d);
     if (sort_by_coordinate) { header_sorted(d.text, "coordinate"); sort_records(d, false); }
@@ -599,7 +620,7 @@ void bam_index(const char *bam, int threads)
     load_bam(bam, threads, d, &bk, &rec_u);
     for (size_t i = 1; i < d.recs.size(); ++i) {
         const uint32_t a = (uint32_t)d.recs[i - 1].ref, c = (uint32_t)d.recs[i].ref;
-        if (a > c || (a == c && d.recs[i - 1].pos > d.recs[i].pos)) throw Err(std::string("not sorted by coordinate: ") + bam);
+        if (a > c || (a == c && d.recs[i - 1].pos > d.recs[i].pos)) throw Error(std::string("not sorted by coordinate: ") + bam);
     }
     auto voff = [&](uint64_t u) -> uint64_t {           // uncompressed offset -> (compressed block start << 16) | offset inside
         size_t lo = 0, hi = bk.starts.size();
@@ -623,7 +644,7 @@ void load_alignments(const char *path, int threads, AlnTable &out, bool with_qua
 {
     threads = clamp_threads(threads);
     unsigned char mg[2] = {0, 0};
-    { FILE *f = std::fopen(path, "rb"); if (!f) throw Err(std::string("cannot open ") + path); const size_t g = std::fread(mg, 1, 2, f); (void)g; std::fclose(f); }
+    { FILE *f = std::fopen(path, "rb"); if (!f) throw Error(std::string("cannot open ") + path); const size_t g = std::fread(mg, 1, 2, f); (void)g; std::fclose(f); }
     Data d;
     if (mg[0] == 31 && mg[1] == 139) load_bam(path, threads, d, nullptr, nullptr); else load_sam(path, -1, threads, d);
     out = AlnTable();

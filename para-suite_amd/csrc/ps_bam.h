@@ -8,7 +8,17 @@ namespace ps {
 struct BamStats { uint64_t n_in = 0, n_out = 0, bam_bytes = 0; };
 // one encoded BAM record inside a buffer of records: reference id, 0-based position and end, flag, byte range [off, off + len)
 struct BamRec { int32_t ref; int32_t pos; int32_t end; uint32_t flag; size_t off, len; int part; };
-int bam_reg2bin(int64_t beg, int64_t end);                  // UCSC binning scheme (SAMv1 5.3)
+// The record layout (SAMv1 4.2), for every route that makes records -- SAM text (sam_to_bam) and the mapper's hits (ps_map_to_bam).
+// In this order: begin, CIGAR words, the caller's (l_seq + 1) / 2 bytes of base nibbles and l_seq bytes of Phred values, tags, end.
+struct BamCore { int32_t ref, pos; int64_t end; int mapq, flag; uint32_t n_cigar, l_seq; int32_t rnext = -1, pnext = -1, tlen = 0; };   // pos, pnext 0-based; end: pos + reference bases covered (at least 1)
+void bam_rec_begin(std::string &o, const BamCore &c, const char *name, size_t name_len, BamRec &r);   // fixed part (bin from pos / end) + name; r: all but len and part
+void bam_rec_cigar(std::string &o, const uint32_t *words, size_t n);
+void bam_tag_int(std::string &o, const char *tag, long long v);                                       // the smallest type that holds v, as htslib's SAM parser
+void bam_tag_char(std::string &o, const char *tag, char v);                                           // type A
+void bam_tag_text(std::string &o, const char *tag, char type /* Z or H */, const char *v, size_t n);
+void bam_tag_text_open(std::string &o, const char *tag, char type);                                  // the same tag with a value the caller appends to o itself,
+void bam_tag_text_close(std::string &o);                                                              // then closes
+void bam_rec_end(std::string &o, BamRec &r);                                                          // block_size and r.len
 // BAM records that were never SAM text (ps_map_to_bam: straight from the alignment records in memory): parts arrive in input
 // order.  Unsorted output: a part is cut into BGZF blocks, compressed on `threads` threads and appended to the file at once, so the
 // compression of one piece of the input runs while the next is searched.  Coordinate-sorted output (+ .bai): the parts are kept and

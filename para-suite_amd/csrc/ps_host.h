@@ -6,14 +6,13 @@
 #include <stdexcept>
 #include <string>
 #include <vector>
+#include "ps_error.h"
 #include "ps_types.h"
 #include "ps_model.h"
 #include "ps_kernels.h"
 #include "../../include/parasuite_hip.h"
 
 namespace ps {
-
-struct Error : std::runtime_error { using std::runtime_error::runtime_error; };
 
 #define PS_HIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) \
     throw ps::Error(std::string(#expr) + ": " + hipGetErrorString(e_)); } while (0)

@@ -15,17 +15,13 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
-#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <functional>
 #include <thread>
-#include <fcntl.h>
-#include <unistd.h>
-#include <sys/stat.h>
-#include <cerrno>
 #include "ps_pipeline.h"
+#include "ps_par.h"
 #include "ps_core.h"
 
 namespace ps {
@@ -120,343 +116,6 @@ void Batch::release_device()
     d_class.release(); d_eb.release(); d_hb.release(); d_rows.release(); d_pos.release(); d_sel.release(); d_fin.release(); d_stats.release();
     searched = false;              // the batch can be written, not searched again
 }
-
-// ------------------------------------------------------------- read input ----
-static inline uint8_t code_of(int ch)
-{
-    switch (ch) { case 'A': case 'a': return 0; case 'C': case 'c': return 1;
-                  case 'G': case 'g': return 2; case 'T': case 't': return 3; default: return 4; }
-}
-
-// FASTQ / FASTA; read name = header up to the first white space, a trailing /1 or /2 removed
-// one parser pass over buf[i0, i1): appends to rs (offsets relative to rs's own arrays)
-static void parse_reads_range(const char *buf, size_t i0, size_t i1, ReadSet &rs, bool &any_qual)
-{
-    struct Lut { uint8_t v[256]; Lut() { for (int c = 0; c < 256; ++c) v[c] = code_of(c); } };
-    static const Lut lut_obj;                       // initialised once, safely, however many parser threads arrive
-    const uint8_t *lut = lut_obj.v;
-    size_t i = i0;
-    const size_t n = i1;
-    while (i < n) {
-        while (i < n && buf[i] != '@' && buf[i] != '>') ++i;
-        if (i >= n) break;
-        const bool fq = buf[i] == '@';
-        size_t s = ++i;
-        while (i < n && !std::isspace((unsigned char)buf[i])) ++i;
-        size_t nl = i - s;
-        if (nl > 2 && buf[s + nl - 2] == '/' && (buf[s + nl - 1] == '1' || buf[s + nl - 1] == '2')) nl -= 2;
-        rs.names.insert(rs.names.end(), buf + s, buf + s + nl);
-        rs.name_off.push_back((int64_t)rs.names.size());
-        const char *eol = (const char *)std::memchr(buf + i, '\n', n - i);
-        i = eol ? (size_t)(eol - buf) + 1 : n;
-        const size_t before = rs.seq.size();
-        const char stop = fq ? '+' : '>';
-        while (i < n && buf[i] != stop) {                         // sequence lines
-            eol = (const char *)std::memchr(buf + i, '\n', n - i);
-            size_t e = eol ? (size_t)(eol - buf) : n, e2 = e;
-            while (e2 > i && !std::isgraph((unsigned char)buf[e2 - 1])) --e2;     // trailing CR / blanks
-            const size_t at = rs.seq.size();
-            rs.seq.resize(at + (e2 - i));
-            for (size_t j = i; j < e2; ++j) rs.seq[at + (j - i)] = lut[(unsigned char)buf[j]];
-            i = e < n ? e + 1 : n;
-        }
-        const int32_t len = (int32_t)(rs.seq.size() - before);
-        rs.len.push_back(len);
-        rs.off.push_back((int64_t)rs.seq.size());
-        const size_t qbefore = rs.qual.size();
-        if (fq && i < n) {
-            eol = (const char *)std::memchr(buf + i, '\n', n - i);
-            i = eol ? (size_t)(eol - buf) + 1 : n;
-            while (i < n && (int32_t)(rs.qual.size() - qbefore) < len) {           // quality lines
-                eol = (const char *)std::memchr(buf + i, '\n', n - i);
-                size_t e = eol ? (size_t)(eol - buf) : n, e2 = e;
-                while (e2 > i && !std::isgraph((unsigned char)buf[e2 - 1])) --e2;
-                size_t take = e2 - i, room = (size_t)len - (rs.qual.size() - qbefore);
-                if (take > room) take = room;
-                rs.qual.insert(rs.qual.end(), buf + i, buf + i + take);
-                i = e < n ? e + 1 : n;
-            }
-            any_qual = true;
-        }
-        rs.qual.resize(qbefore + (size_t)len, '!');
-        ++rs.n;
-    }
-}
-
-// ---- record boundaries ----------------------------------------------------------------------------------------
-// A piece of the input must begin at a record.  A line that starts with '@' need not be a header (a quality string may
-// start with '@'), so a candidate is VERIFIED by walking the record: header, sequence lines up to the '+' line, quality
-// lines holding exactly as many characters as the sequence -- and what follows must be the next header or the end.
-// Returns the index behind the record (the start of the next one); 0 if [i, n) does not hold a whole well-formed record
-// at i.  at_eof: n is the end of the input (the last line may lack its newline).
-static size_t record_end(const char *b, size_t i, size_t n, bool at_eof)
-{
-    if (i >= n) return 0;
-    auto line_end = [&](size_t p) { const char *e = (const char *)std::memchr(b + p, '\n', n - p); return e ? (size_t)(e - b) : n; };
-    auto graph_len = [&](size_t p, size_t e) { while (e > p && !std::isgraph((unsigned char)b[e - 1])) --e; return e - p; };
-    if (b[i] == '>') {                                   // FASTA: up to the next '>' at a line start
-        size_t p = line_end(i);
-        if (p >= n) return at_eof ? n : 0;
-        for (++p; p < n; ) { if (b[p] == '>') return p; const size_t e = line_end(p); if (e >= n) return at_eof ? n : 0; p = e + 1; }
-        return at_eof ? n : 0;
-    }
-    if (b[i] != '@') return 0;
-    size_t p = line_end(i);
-    if (p >= n) return 0;
-    ++p;
-    size_t S = 0, Q = 0;
-    for (;;) {                                           // sequence lines
-        if (p >= n) return 0;
-        if (b[p] == '+') break;
-        const size_t e = line_end(p);
-        if (e >= n) return 0;
-        S += graph_len(p, e); p = e + 1;
-    }
-    if (S == 0) return 0;                                // no boundary is placed on an empty record: a quality line '@..' followed by
-                                                         // one '+..' and one '@..' would verify as one
-    { const size_t e = line_end(p); if (e >= n) return 0; p = e + 1; }       // the '+' line
-    while (Q < S) {                                      // quality lines
-        if (p >= n) return 0;
-        const size_t e = line_end(p);
-        Q += graph_len(p, e);
-        if (e >= n) return (Q == S && at_eof) ? n : 0;
-        p = e + 1;
-    }
-    if (Q != S) return 0;
-    if (p < n && b[p] != '@') return 0;
-    return p;
-}
-// first verified record start at or behind `from` (a line start is looked for first), looking at no more than max_lines
-// lines; n if there is none.  One record can verify by coincidence when the candidate is a quality line (header and
-// sequence of the next record counted as "sequence", lengths happening to add up), so three records in a row must verify
-// -- or the input must end behind fewer (at_eof only: a window of a stream that ends earlier rejects the candidate).
-static size_t find_record_start(const char *b, size_t from, size_t n, bool at_eof, int max_lines, char mark /* '@' FASTQ, '>' FASTA: the input's first byte */)
-{
-    size_t i = from;
-    if (i > 0 && i < n && b[i - 1] != '\n') { const char *e = (const char *)std::memchr(b + i, '\n', n - i); i = e ? (size_t)(e - b) + 1 : n; }
-    for (int t = 0; t < max_lines && i < n; ++t) {
-        if (b[i] == mark) {                              // (a FASTQ quality line may start with '>' as well as with '@')
-            size_t p = i; int good = 0;
-            for (; good < 3 && p < n; ++good) { const size_t e = record_end(b, p, n, at_eof); if (!e) break; p = e; }
-            if (good == 3 || (good > 0 && p >= n && at_eof)) return i;
-        }
-        const char *e = (const char *)std::memchr(b + i, '\n', n - i);
-        i = e ? (size_t)(e - b) + 1 : n;
-    }
-    return n;
-}
-// record starts that split [lo, hi) of the file image into about `parts` pieces; a cut is made only where a record start
-// verifies -- otherwise that piece simply stays larger
-static std::vector<size_t> cut_records(const char *b, size_t lo, size_t hi, int parts)
-{
-    std::vector<size_t> cut(1, lo);
-    if (parts > 1 && hi - lo > (size_t)(1 << 20) && (b[lo] == '@' || b[lo] == '>')) {
-        for (int t = 1; t < parts; ++t) {
-            const size_t i = find_record_start(b, lo + (hi - lo) / (size_t)parts * (size_t)t, hi, true, 64, b[lo]);
-            if (i < hi && i > cut.back()) cut.push_back(i);
-        }
-    }
-    cut.push_back(hi);
-    return cut;
-}
-static double g_t_fread = 0, g_t_cut = 0, g_t_par = 0, g_t_merge = 0;   // PS_VERBOSE >= 2: where the parser's time goes
-// parse [lo, hi) of the file image on `threads` threads and APPEND the reads to rs.  Every thread parses its range into arrays of its
-// own; the ranges' sizes then give every range its place in rs, and the threads copy their parts there side by side (one thread
-// joining the parts cost more than the parsing: 0.5 s against 0.3 s per 5 M reads on 8 cores).
-static void parse_span(const char *b, size_t lo, size_t hi, int threads, ReadSet &rs)
-{
-    if (threads < 1) threads = 1;
-    if (threads > 64) threads = 64;
-    const auto tc0 = std::chrono::steady_clock::now();
-    const std::vector<size_t> cut = cut_records(b, lo, hi, threads);
-    const int parts = (int)cut.size() - 1;
-    const auto tc1 = std::chrono::steady_clock::now();
-    std::vector<ReadSet> piece((size_t)parts);
-    std::vector<char> anyq((size_t)parts, 0);
-    auto work = [&](int t) {
-        ReadSet &r = piece[t];
-        const size_t bytes = cut[t + 1] - cut[t];
-        r.seq.reserve(bytes / 2 + 64); r.qual.reserve(bytes / 2 + 64);          // a FASTQ record is at most half bases
-        r.off.push_back(0); r.name_off.push_back(0);
-        bool aq = false;
-        parse_reads_range(b, cut[t], cut[t + 1], r, aq);
-        anyq[t] = aq;
-    };
-    auto fan = [&](const std::function<void(int)> &f) { std::vector<std::thread> th; for (int t = 1; t < parts; ++t) th.emplace_back(f, t); f(0); for (auto &x : th) x.join(); };
-    fan(work);
-    const auto tc2 = std::chrono::steady_clock::now();
-    g_t_cut += std::chrono::duration<double>(tc1 - tc0).count(); g_t_par += std::chrono::duration<double>(tc2 - tc1).count();
-    if (rs.off.empty()) { rs.off.push_back(0); rs.name_off.push_back(0); }
-    std::vector<size_t> n0((size_t)parts + 1), s0((size_t)parts + 1), m0((size_t)parts + 1);
-    n0[0] = (size_t)rs.n; s0[0] = rs.seq.size(); m0[0] = rs.names.size();
-    bool any_qual = rs.has_qual;
-    for (int t = 0; t < parts; ++t) {
-        n0[t + 1] = n0[t] + (size_t)piece[t].n; s0[t + 1] = s0[t] + piece[t].seq.size(); m0[t + 1] = m0[t] + piece[t].names.size();
-        any_qual = any_qual || anyq[t];
-    }
-    const size_t tn = n0[parts], ts = s0[parts], tm = m0[parts];
-    auto grow = [](auto &v, size_t need) { if (v.capacity() < need) v.reserve(need + need / 2); v.resize(need); };     // in large steps: a piece is appended to window by window
-    grow(rs.len, tn); grow(rs.off, tn + 1); grow(rs.name_off, tn + 1); grow(rs.seq, ts); grow(rs.qual, ts); grow(rs.names, tm);
-    auto place = [&](int t) {
-        ReadSet &r = piece[t];
-        if (r.n == 0) return;
-        std::memcpy(rs.len.data() + n0[t], r.len.data(), (size_t)r.n * sizeof(int32_t));
-        int64_t *o = rs.off.data() + n0[t], *m = rs.name_off.data() + n0[t];
-        const int64_t so = (int64_t)s0[t], no = (int64_t)m0[t];
-        for (int64_t k = 1; k <= r.n; ++k) { o[k] = r.off[k] + so; m[k] = r.name_off[k] + no; }
-        std::memcpy(rs.seq.data() + s0[t], r.seq.data(), r.seq.size());
-        std::memcpy(rs.qual.data() + s0[t], r.qual.data(), r.qual.size());
-        std::memcpy(rs.names.data() + m0[t], r.names.data(), r.names.size());
-        r = ReadSet();
-    };
-    fan(place);
-    rs.n = (int64_t)tn; rs.has_qual = any_qual;
-    g_t_merge += std::chrono::duration<double>(std::chrono::steady_clock::now() - tc2).count();
-}
-static void parser_times(int threads)
-{
-    if (const char *e = std::getenv("PS_VERBOSE")) if (std::atoi(e) >= 2)
-        std::fprintf(stderr, "[parasuite-hip]     parser: reading %.0f ms, cutting %.0f ms, parsing on %d threads %.0f ms, placing the threads' parts %.0f ms (sums over the windows)\n", 1e3 * g_t_fread, 1e3 * g_t_cut, threads, 1e3 * g_t_par, 1e3 * g_t_merge);
-    g_t_fread = g_t_cut = g_t_par = g_t_merge = 0;
-}
-// `want` bytes at file offset `at` into dst, by a few threads side by side when the file is a regular one (one thread copies ~3 GB/s out
-// of the page cache); returns the bytes read (fewer than wanted: the input ends there)
-static size_t read_at(int fd, bool regular, off_t at, char *dst, size_t want, int threads)
-{
-    auto one = [&](size_t lo, size_t hi) -> size_t {
-        size_t have = lo;
-        while (have < hi) {
-            const ssize_t r = regular ? ::pread(fd, dst + have, hi - have, at + (off_t)have) : ::read(fd, dst + have, hi - have);
-            if (r < 0) { if (errno == EINTR) continue; throw Error("read error on the reads file"); }
-            if (r == 0) break;
-            have += (size_t)r;
-        }
-        return have - lo;
-    };
-    const int nt = regular ? (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(threads, 8), want >> 22)) : 1;      // >= 4 MB per thread
-    if (nt == 1) return one(0, want);
-    std::vector<size_t> got((size_t)nt, 0); std::vector<std::string> err((size_t)nt);
-    auto part = [&](int t) { try { got[t] = one(want * (size_t)t / nt, want * (size_t)(t + 1) / nt); } catch (const std::exception &e) { err[t] = e.what(); } };
-    { std::vector<std::thread> th; for (int t = 1; t < nt; ++t) th.emplace_back(part, t); part(0); for (auto &x : th) x.join(); }
-    size_t total = 0;
-    for (int t = 0; t < nt; ++t) {
-        if (!err[t].empty()) throw Error(err[t]);
-        total += got[t];
-        if (got[t] < want * (size_t)(t + 1) / nt - want * (size_t)t / nt) break;       // the input ended inside this part: what lies behind is not there
-    }
-    return total;
-}
-struct FdCloser { int fd; ~FdCloser() { if (fd >= 0) ::close(fd); } };
-
-void load_reads(const char *path, ReadSet &rs, int threads)
-{
-    rs = ReadSet();
-    load_reads_chunked(path, threads, ~(size_t)0 >> 2, [&](ReadSet &&piece) { rs = std::move(piece); });
-    if (rs.off.empty()) { rs.off.push_back(0); rs.name_off.push_back(0); }
-}
-
-void load_reads_chunked(const char *path, int threads, size_t chunk_bytes, const std::function<void(ReadSet &&)> &sink, size_t first_bytes,
-                        const std::function<bool()> *hungry, size_t hungry_min_bytes)
-{
-    const int fd = ::open(path, O_RDONLY);
-    if (fd < 0) throw Error(std::string("cannot open reads ") + path);
-    FdCloser closer{fd};
-    struct stat st;
-    const bool regular = ::fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
-    if (chunk_bytes < 4096) chunk_bytes = 4096;
-    size_t unit = (size_t)64 << 20;
-    if (const char *e = std::getenv("PS_UNIT_MB")) unit = (size_t)std::max(1, std::atoi(e)) << 20;
-    unit = std::min(unit, chunk_bytes);
-    // the first piece may be smaller (the stages behind the parser start sooner), the following ones double up to chunk_bytes
-    size_t cur = first_bytes && first_bytes < chunk_bytes ? std::max<size_t>(first_bytes, 4096) : chunk_bytes;
-    RawVec<char> buf; size_t have = 0; bool eof = false; char mark = 0; off_t file_at = 0;
-    ReadSet acc; size_t acc_bytes = 0;
-    auto flush = [&]() { if (acc.n) { sink(std::move(acc)); cur = std::min(chunk_bytes, cur * 2); } acc = ReadSet(); acc_bytes = 0; };
-    while (!eof || have) {
-        const size_t fine = std::min<size_t>((size_t)1 << 20, unit);                                  // a piece ends within this of its size
-        const size_t win = std::min(unit, cur > acc_bytes + fine ? cur - acc_bytes : unit);          // the last window of a piece is what is missing to its size (a piece already at its size is taking the end of the input along: whole windows)
-        const size_t want = win > have ? win : have + win;       // what is carried over from a window that could not be cut fills a window alone: it grows
-        if (buf.size() < want + 1) buf.resize(want + 1);
-        const auto tr0 = std::chrono::steady_clock::now();
-        if (!eof && have < want) {
-            const size_t got = read_at(fd, regular, file_at, buf.data() + have, want - have, threads);
-            if (got < want - have) eof = true;
-            have += got; file_at += (off_t)got;
-        }
-        g_t_fread += std::chrono::duration<double>(std::chrono::steady_clock::now() - tr0).count();
-        if (!mark && have) mark = buf[0];
-        size_t cut = have;
-        if (!eof) {
-            // the last record start that verifies: walk records from a start found in the window's last 256 KB
-            const size_t from = have > ((size_t)256 << 10) ? have - ((size_t)256 << 10) : 0;
-            size_t i = find_record_start(buf.data(), from, have, false, 4096, mark), last = 0;
-            while (i < have) { last = i; const size_t e = record_end(buf.data(), i, have, false); if (!e || e >= have) break; i = e; }
-            if (last == 0) continue;                                               // nothing to cut at: the window grows
-            cut = last;
-        }
-        if (cut) {
-            const size_t tiny = cur / 8;                                                                        // an end of the input not worth a launch of its own
-            const bool to_the_end = regular && (size_t)std::max<off_t>(0, st.st_size - file_at) + have <= tiny;  // this window and all behind it
-            if (acc_bytes && acc_bytes + cut > cur + fine && !to_the_end) flush();    // this window would take the piece well over its size (a window that had to grow)
-            const bool first_window = acc.n == 0;
-            parse_span(buf.data(), 0, cut, threads, acc);
-            if (first_window && acc.n && cur > cut && cur < (~(size_t)0 >> 3)) {     // a piece's arrays are sized once, from what its first window held
-                const double f = 1.05 * (double)cur / (double)cut;
-                acc.len.reserve((size_t)(f * (double)acc.n) + 64); acc.off.reserve((size_t)(f * (double)acc.n) + 65); acc.name_off.reserve((size_t)(f * (double)acc.n) + 65);
-                acc.seq.reserve((size_t)(f * (double)acc.seq.size()) + 64); acc.qual.reserve((size_t)(f * (double)acc.seq.size()) + 64);
-                acc.names.reserve((size_t)(f * (double)acc.names.size()) + 64);
-            }
-            acc_bytes += cut;
-            // no piece is cut off just in front of the end of the input: what is left would be a launch of its own (>= 0.3 s for 0.6 M reads,
-            // measured) -- the piece takes it along, up to an eighth over its size
-            const size_t rest = regular ? (size_t)std::max<off_t>(0, st.st_size - file_at) + (have - cut) : ~(size_t)0;
-            const bool tiny_rest = !eof && rest <= tiny;
-            if (!tiny_rest && (acc_bytes + fine > cur || (hungry && acc_bytes >= hungry_min_bytes && (*hungry)()))) flush();
-        }
-        std::memmove(buf.data(), buf.data() + cut, have - cut);
-        have -= cut;
-        if (eof && cut == 0) break;
-    }
-    flush();
-    parser_times(threads);
-}
-
-void reads_from_codes(int64_t n, int len, const uint8_t *codes, ReadSet &rs)
-{
-    rs = ReadSet();
-    rs.n = n; rs.len.assign((size_t)n, len); rs.off.resize((size_t)n + 1); rs.name_off.resize((size_t)n + 1);
-    rs.seq.assign(codes, codes + (size_t)n * len);
-    for (auto &c : rs.seq) if (c > 4) c = 4;
-    char nm[32];
-    rs.name_off[0] = 0;
-    for (int64_t i = 0; i < n; ++i) {
-        rs.off[i] = i * len;
-        int l = std::snprintf(nm, sizeof nm, "r%lld", (long long)i);
-        rs.names.insert(rs.names.end(), nm, nm + l);
-        rs.name_off[i + 1] = (int64_t)rs.names.size();
-    }
-    rs.off[n] = n * (int64_t)len;
-    rs.has_qual = false;
-}
-
-// host loops over millions of reads: contiguous ranges on a few threads; f(begin, end, thread)
-template <class F> static void par_for(size_t n, int threads, F f)
-{
-    size_t nt = (size_t)std::max(1, threads);
-    if (nt > n / 8192 + 1) nt = n / 8192 + 1;
-    if (nt <= 1) { if (n) f((size_t)0, n, 0); return; }
-    std::vector<std::thread> th;
-    std::vector<std::exception_ptr> err(nt);
-    const size_t per = (n + nt - 1) / nt;
-    for (size_t t = 0; t < nt; ++t)
-        th.emplace_back([&, t]() {
-            const size_t a0 = t * per, b0 = std::min(n, a0 + per);
-            try { if (a0 < b0) f(a0, b0, (int)t); } catch (...) { err[t] = std::current_exception(); }
-        });
-    for (auto &x : th) x.join();
-    for (auto &e : err) if (e) std::rethrow_exception(e);
-}
-static int par_threads(size_t n, int threads) { size_t nt = (size_t)std::max(1, threads); if (nt > n / 8192 + 1) nt = n / 8192 + 1; return (int)std::max<size_t>(1, nt); }
 
 // ------------------------------------------------------------ batch set-up ---
 // host half of batch_create: bins, order inside the bins, 2-bit packing -- no device call, so the parser thread of
@@ -804,10 +463,8 @@ static void download_alns(Work *wk, int n, int aln_cap, const AlnRec *d_alns, co
 // ------------------------------------------------- samse stage on the device --------
 // Read classes for the tie-break stream (one drand48 stream over all reads in input order):
 //   0 no hit (no draw) | 1 exactly one best-score SA interval (always two draws) | 2 several (data dependent)
-// bit 2 (PS_CLS_HOST): the read is finished on the host -- class 2 (sequential chain), reads that list
+// bit 2 (PS_CLS_HOST, ps_pipeline.h): the read is finished on the host -- class 2 (sequential chain), reads that list
 // alternative hits (XA), reads that needed a larger search tier.  Everything else never leaves the GPU.
-static const uint8_t PS_CLS_HOST = 4;
-
 __global__ void k_classify(const AlnRec *alns, int aln_cap, const int32_t *n_aln, const uint8_t *status, const int32_t *ids,
                            int n, int n_occ, uint8_t *cls_out)
 {
@@ -1484,429 +1141,6 @@ void batch_locate(Batch &b)
     b.tm.ms_host_post += ms_since(t1);
     b.located = true;
     b.tm.ms_total += ms_since(t0);
-}
-
-// one read's alignment record: from the host-finished subset, else assembled from the device records
-void Batch::hit_of(int64_t g, Hit &h) const
-{
-    if (h_class[g] & PS_CLS_HOST) {
-        auto it = std::lower_bound(sub.begin(), sub.end(), g, [](const SubRead &s, int64_t v) { return s.g < v; });
-        h = it->hit;
-        return;
-    }
-    const SelRec &s = h_sel[g]; const FinRec &f = h_fin[g];
-    h = Hit();
-    h.sa = s.sa; h.type = f.type; h.pos = f.type ? f.pos : -1; h.strand = f.strand; h.mapq = f.mapq;
-    h.n_mm = s.n_mm; h.n_gapo = s.n_gapo; h.n_gape = s.n_gape; h.ref_shift = s.ref_shift; h.score = s.score; h.c1 = s.c1; h.c2 = s.c2;
-    if (s.n_gapo && s.type) {
-        auto it = std::lower_bound(dev_cigars.begin(), dev_cigars.end(), g, [](const DevCigar &c, int64_t v) { return c.g < v; });
-        if (it != dev_cigars.end() && it->g == g) { h.n_cigar = it->n; std::memcpy(h.cigar, it->c, sizeof h.cigar); }
-    }
-}
-
-// ------------------------------------------------------------------ SAM -------
-static inline int host_pac(const uint8_t *pac, int64_t p) { return (pac[(size_t)p >> 2] >> ((~p & 3) << 1)) & 3; }
-static void put_int(std::string &o, long v)            // a dozen numbers per SAM line: no snprintf
-{
-    char b[24]; int n = 24;
-    unsigned long u = v < 0 ? 0ul - (unsigned long)v : (unsigned long)v;
-    do { b[--n] = (char)('0' + u % 10); u /= 10; } while (u);
-    if (v < 0) b[--n] = '-';
-    o.append(b + n, (size_t)(24 - n));
-}
-static int64_t ref_span(int n, const uint32_t *c, int len)
-{
-    if (!n) return len;
-    int64_t x = 0;
-    for (int j = 0; j < n; ++j) { int op = c[j] & 0xf; if (op == 0 || op == 2) x += c[j] >> 4; }
-    return x;
-}
-// MD string and edit distance by direct comparison with the reference
-static void cal_md(const RefSeq &ref, int n_cigar, const uint32_t *cigar, int len, int64_t pos, const uint8_t *seq, std::string &md, int &nm)
-{
-    int64_t x = pos, y = 0; int u = 0; nm = 0; md.clear();
-    const uint8_t *pac = ref.pac_data();
-    auto cmp = [&](int l) {
-        for (int z = 0; z < l && x + z < ref.l_pac; ++z) {
-            int c = host_pac(pac, x + z);
-            if (seq[y + z] > 3 || c != seq[y + z]) { put_int(md, u); md.push_back("ACGTN"[c]); ++nm; u = 0; } else ++u;
-        }
-    };
-    if (n_cigar) {
-        for (int k = 0; k < n_cigar; ++k) {
-            int l = (int)(cigar[k] >> 4), op = (int)(cigar[k] & 0xf);
-            if (op == 0) { cmp(l); x += l; y += l; }
-            else if (op == 1 || op == 3) { y += l; if (op == 1) nm += l; }
-            else if (op == 2) {
-                put_int(md, u); md.push_back('^');
-                for (int z = 0; z < l && x + z < ref.l_pac; ++z) md.push_back("ACGT"[host_pac(pac, x + z)]);
-                u = 0; x += l; nm += l;
-            }
-        }
-    } else cmp(len);
-    put_int(md, u);
-}
-
-// SAM text goes through a raw cursor into storage the caller has made large enough (Room): a line is ~35 small pieces, and one
-// std::string append per piece was most of the 1.3 us per read and thread that the writer -- the last stage of ps_map -- spent.
-namespace {
-struct Cur {
-    char *p;
-    inline void ch(char c) { *p++ = c; }
-    inline void mem(const char *s, size_t n) { std::memcpy(p, s, n); p += n; }
-    template <size_t N> inline void lit(const char (&s)[N]) { std::memcpy(p, s, N - 1); p += N - 1; }
-    inline void num(long v)
-    {
-        static const char D2[] = "00010203040506070809101112131415161718192021222324252627282930313233343536373839404142434445464748495051525354555657585960616263646566676869707172737475767778798081828384858687888990919293949596979899";
-        unsigned long u = (unsigned long)v;
-        if (v < 0) { *p++ = '-'; u = 0ul - u; }
-        if (u < 10) { *p++ = (char)('0' + u); return; }
-        if (u < 100) { std::memcpy(p, D2 + 2 * u, 2); p += 2; return; }
-        char b[24]; int n = 24;
-        while (u >= 100) { const unsigned long r = u % 100; u /= 100; n -= 2; std::memcpy(b + n, D2 + 2 * r, 2); }
-        if (u >= 10) { n -= 2; std::memcpy(b + n, D2 + 2 * u, 2); } else b[--n] = (char)('0' + u);
-        std::memcpy(p, b + n, (size_t)(24 - n)); p += 24 - n;
-    }
-    inline void cigar(int n, const uint32_t *c, int len)
-    {
-        if (n) for (int j = 0; j < n; ++j) { num((long)(c[j] >> 4)); ch("MIDS"[c[j] & 0xf]); }
-        else { num(len); ch('M'); }
-    }
-};
-// storage with `used` bytes taken: at least `need` more, the string's size being the storage (grown in large steps, never shrunk here)
-inline char *room(std::string &o, size_t used, size_t need)
-{
-    if (o.size() < used + need) o.resize(std::max(o.size() + o.size() / 2, used + need + ((size_t)1 << 16)));
-    return &o[0] + used;
-}
-}
-// the XA list of a read (alternative hits, `samse -n 3`): chr,(+|-)pos,CIGAR,NM;
-static void xa_cur(const Batch &b, const Hit &h, int len, std::string &o, size_t &used)
-{
-    const RefSeq &ref = b.ctx->ix.ref;
-    for (int j = 0; j < h.n_multi; ++j) {
-        const Multi &m = b.multis[h.multi_begin + j];
-        int sid = 0;
-        ref.cnt_ambi(m.pos, (int)ref_span(m.n_cigar, m.cigar, len), &sid);
-        const Contig &mc = ref.contigs[sid];
-        Cur c{room(o, used, mc.name.size() + 64 + 12 * (size_t)PS_MAX_CIGAR)};
-        char *const c0 = c.p;
-        c.mem(mc.name.data(), mc.name.size()); c.ch(','); c.ch(m.strand ? '-' : '+'); c.num((long)(m.pos - mc.offset + 1)); c.ch(',');
-        c.cigar(m.n_cigar, m.cigar, len);
-        c.ch(','); c.num(m.gap + m.mm); c.ch(';');
-        used += (size_t)(c.p - c0);
-    }
-}
-static void xa_text(const Batch &b, const Hit &h, int len, std::string &o)        // appended to a string (the BAM route)
-{
-    size_t used = o.size();
-    xa_cur(b, h, len, o, used);
-    o.resize(used);
-}
-
-// one line at o[used...]; `used` moves on.  o.size() is storage, not content (room()).
-static void sam_line(const Batch &b, int64_t g, std::string &o, size_t &used)
-{
-    const ReadSet &rs = b.rs; const RefSeq &ref = b.ctx->ix.ref; const Options &opt = b.ctx->opt;
-    Hit h; b.hit_of(g, h);
-    const int len = rs.len[g];
-    const uint8_t *seq = rs.seq.data() + rs.off[g];
-    const char *qual = rs.has_qual ? rs.qual.data() + rs.off[g] : nullptr;
-    size_t nl; const char *nm_ = rs.name(g, nl);
-    int seqid = 0, nn = 0, span = 0;
-    const Contig *ct = nullptr;
-    if (h.type != 0) {
-        span = (int)ref_span(h.n_cigar, h.cigar, len);
-        nn = ref.cnt_ambi(h.pos, span, &seqid);
-        ct = &ref.contigs[seqid];
-    }
-    // oriented read for MD/NM
-    static thread_local std::string md; int nm = 0;
-    if (h.type != 0) {
-        uint8_t tmp_small[256]; std::vector<uint8_t> tmp_big;
-        uint8_t *tmp = tmp_small;
-        if (len > 256) { tmp_big.resize((size_t)len); tmp = tmp_big.data(); }
-        const uint8_t *oriented = seq;
-        if (h.strand) { for (int i = 0; i < len; ++i) { uint8_t c = seq[len - 1 - i]; tmp[i] = c > 3 ? c : (uint8_t)(3 - c); } oriented = tmp; }
-        md.clear();
-        cal_md(ref, h.n_cigar, h.cigar, len, h.pos, oriented, md, nm);
-    }
-    // everything but the XA list: name, 11 columns (two of them the read), at most 9 tags of <= 26 characters, MD
-    Cur c{room(o, used, nl + 2 * (size_t)len + (ct ? ct->name.size() + md.size() : 0) + 12 * (size_t)PS_MAX_CIGAR + 384)};
-    char *const c0 = c.p;
-    c.mem(nm_, nl);
-    auto put_seq = [&](int strand) {
-        char *d = c.p;
-        if (!strand) for (int i = 0; i < len; ++i) d[i] = "ACGTN"[seq[i]];
-        else for (int i = 0; i < len; ++i) d[i] = "TGCAN"[seq[len - 1 - i]];
-        d[len] = '\t';
-        d += len + 1;
-        if (qual) { if (!strand) std::memcpy(d, qual, (size_t)len); else for (int i = 0; i < len; ++i) d[i] = qual[len - 1 - i]; d += len; }
-        else *d++ = '*';
-        c.p = d;
-    };
-    if (h.type == 0) { c.lit("\t4\t*\t0\t0\t*\t*\t0\t0\t"); put_seq(h.strand); c.ch('\n'); used += (size_t)(c.p - c0); return; }
-    int flag = 0;
-    if (h.pos + span - ct->offset > ct->len) flag |= 4;      // bridges two reference sequences
-    if (h.strand) flag |= 16;
-    c.ch('\t'); c.num(flag); c.ch('\t'); c.mem(ct->name.data(), ct->name.size()); c.ch('\t');
-    c.num((long)(h.pos - ct->offset + 1)); c.ch('\t'); c.num(h.mapq); c.ch('\t');
-    c.cigar(h.n_cigar, h.cigar, len);
-    c.lit("\t*\t0\t0\t");
-    put_seq(h.strand);
-    char XT = "NURM"[h.type];
-    if (nn > 10) XT = 'N';
-    c.lit("\tXT:A:"); c.ch(XT); c.lit("\tNM:i:"); c.num(nm);
-    if (nn) { c.lit("\tXN:i:"); c.num(nn); }
-    c.lit("\tX0:i:"); c.num(h.c1);
-    if (h.c1 <= opt.max_top2) { c.lit("\tX1:i:"); c.num(h.c2); }
-    c.lit("\tXM:i:"); c.num(h.n_mm); c.lit("\tXO:i:"); c.num(h.n_gapo); c.lit("\tXG:i:"); c.num(h.n_gapo + h.n_gape);
-    c.lit("\tMD:Z:"); c.mem(md.data(), md.size());
-    if (h.n_multi) c.lit("\tXA:Z:");
-    used += (size_t)(c.p - c0);
-    if (h.n_multi) xa_cur(b, h, len, o, used);
-    *room(o, used, 1) = '\n'; ++used;
-}
-
-// ---- the same record as a BAM record (ps_map_to_bam: no SAM text in between).  Field for field what sam_line prints and
-// ps_bam.cpp's encode_line would make of it: tests/test_bam.py compares the two routes record by record.
-static inline void b_put32(std::string &o, uint32_t v) { char c[4] = {(char)(v & 0xff), (char)((v >> 8) & 0xff), (char)((v >> 16) & 0xff), (char)(v >> 24)}; o.append(c, 4); }
-static inline void b_put16(std::string &o, uint32_t v) { char c[2] = {(char)(v & 0xff), (char)((v >> 8) & 0xff)}; o.append(c, 2); }
-static inline void b_tag_int(std::string &o, const char *tag, long v)          // the smallest type that holds it, as htslib / encode_line
-{
-    o.push_back(tag[0]); o.push_back(tag[1]);
-    if (v < 0) {
-        if (v >= -128) { o.push_back('c'); o.push_back((char)(int8_t)v); }
-        else if (v >= -32768) { o.push_back('s'); b_put16(o, (uint32_t)(uint16_t)(int16_t)v); }
-        else { o.push_back('i'); b_put32(o, (uint32_t)(int32_t)v); }
-    } else if (v <= 255) { o.push_back('C'); o.push_back((char)(uint8_t)v); }
-    else if (v <= 65535) { o.push_back('S'); b_put16(o, (uint32_t)v); }
-    else { o.push_back('I'); b_put32(o, (uint32_t)v); }
-}
-// false: below the MAPQ filter (not stored)
-static bool bam_record(const Batch &b, int64_t g, int min_mapq, std::string &o, BamRec &r)
-{
-    const ReadSet &rs = b.rs; const RefSeq &ref = b.ctx->ix.ref; const Options &opt = b.ctx->opt;
-    Hit h; b.hit_of(g, h);
-    const int mapq = h.type == 0 ? 0 : h.mapq;
-    if (mapq < min_mapq) return false;
-    const int len = rs.len[g];
-    const uint8_t *seq = rs.seq.data() + rs.off[g];
-    const char *qual = rs.has_qual ? rs.qual.data() + rs.off[g] : nullptr;
-    size_t nl; const char *nm_ = rs.name(g, nl);
-    if (nl > 254) throw Error("read name longer than 254 characters");
-    int seqid = -1, flag = 4, nn = 0, n_cig = 0; int64_t pos = -1, end = 0;
-    uint32_t cig[PS_MAX_CIGAR + 1];
-    if (h.type != 0) {
-        const int span = (int)ref_span(h.n_cigar, h.cigar, len);
-        nn = ref.cnt_ambi(h.pos, span, &seqid);
-        const Contig &ct = ref.contigs[seqid];
-        flag = (h.pos + span - ct.offset > ct.len ? 4 : 0) | (h.strand ? 16 : 0);
-        pos = h.pos - ct.offset;
-        if (h.n_cigar) { for (int j = 0; j < h.n_cigar; ++j) { const uint32_t op = h.cigar[j] & 0xfu; cig[j] = (h.cigar[j] & ~0xfu) | (op == 3 ? 4u : op); } n_cig = h.n_cigar; }
-        else { cig[0] = (uint32_t)len << 4; n_cig = 1; }
-        end = pos + (span > 0 ? span : 1);
-    }
-    const size_t start = o.size();
-    b_put32(o, 0);
-    b_put32(o, (uint32_t)seqid); b_put32(o, (uint32_t)(int32_t)pos);
-    o.push_back((char)(uint8_t)(nl + 1)); o.push_back((char)(uint8_t)mapq);
-    b_put16(o, (uint32_t)bam_reg2bin(pos, end));
-    b_put16(o, (uint32_t)n_cig); b_put16(o, (uint32_t)flag);
-    b_put32(o, (uint32_t)len); b_put32(o, 0xFFFFFFFFu); b_put32(o, 0xFFFFFFFFu); b_put32(o, 0);
-    o.append(nm_, nl); o.push_back('\0');
-    for (int j = 0; j < n_cig; ++j) b_put32(o, cig[j]);
-    static const uint8_t NIB[5] = {1, 2, 4, 8, 15}, NIB_RC[5] = {8, 4, 2, 1, 15};
-    const bool rc = h.strand != 0;
-    {
-        const size_t at = o.size(), nb = (size_t)(len + 1) / 2;
-        o.resize(at + nb + (size_t)len);
-        uint8_t *d = reinterpret_cast<uint8_t *>(&o[at]);
-        for (int i = 0; i < len; i += 2) {
-            const uint8_t hi = rc ? NIB_RC[seq[len - 1 - i]] : NIB[seq[i]];
-            const uint8_t lo = i + 1 < len ? (rc ? NIB_RC[seq[len - 2 - i]] : NIB[seq[i + 1]]) : 0;
-            d[i >> 1] = (uint8_t)(hi << 4 | lo);
-        }
-        d += nb;
-        if (!qual) std::memset(d, 0xff, (size_t)len);
-        else if (!rc) for (int i = 0; i < len; ++i) d[i] = (uint8_t)(qual[i] - 33);
-        else for (int i = 0; i < len; ++i) d[i] = (uint8_t)(qual[len - 1 - i] - 33);
-    }
-    if (h.type != 0) {
-        uint8_t tmp_small[256]; std::vector<uint8_t> tmp_big;
-        uint8_t *tmp = tmp_small;
-        if (len > 256) { tmp_big.resize((size_t)len); tmp = tmp_big.data(); }
-        const uint8_t *oriented = seq;
-        if (rc) { for (int i = 0; i < len; ++i) { uint8_t c = seq[len - 1 - i]; tmp[i] = c > 3 ? c : (uint8_t)(3 - c); } oriented = tmp; }
-        static thread_local std::string md; md.clear(); int nm = 0;
-        cal_md(ref, h.n_cigar, h.cigar, len, h.pos, oriented, md, nm);
-        char XT = "NURM"[h.type];
-        if (nn > 10) XT = 'N';
-        o.append("XTA", 3); o.push_back(XT);
-        b_tag_int(o, "NM", nm);
-        if (nn) b_tag_int(o, "XN", nn);
-        b_tag_int(o, "X0", h.c1);
-        if (h.c1 <= opt.max_top2) b_tag_int(o, "X1", h.c2);
-        b_tag_int(o, "XM", h.n_mm); b_tag_int(o, "XO", h.n_gapo); b_tag_int(o, "XG", h.n_gapo + h.n_gape);
-        o.append("MDZ", 3); o.append(md); o.push_back('\0');
-        if (h.n_multi) { o.append("XAZ", 3); xa_text(b, h, len, o); o.push_back('\0'); }
-    }
-    const uint32_t bs = (uint32_t)(o.size() - start - 4);
-    o[start] = (char)(bs & 0xff); o[start + 1] = (char)((bs >> 8) & 0xff); o[start + 2] = (char)((bs >> 16) & 0xff); o[start + 3] = (char)(bs >> 24);
-    r.ref = seqid; r.pos = (int32_t)pos; r.end = (int32_t)end; r.flag = (uint32_t)flag; r.off = start; r.len = o.size() - start; r.part = 0;
-    return true;
-}
-// the records of a located batch that pass the MAPQ filter as BAM records: one buffer per host thread, the buffers in input order
-void batch_bam_records(const Batch &b, int min_mapq, int threads, std::vector<std::string> &enc, std::vector<std::vector<BamRec>> &recs)
-{
-    if (!b.located) throw Error("BAM records before locate");
-    const size_t N = (size_t)b.rs.n;
-    const int nt = par_threads(N, threads);
-    enc.assign((size_t)nt, std::string()); recs.assign((size_t)nt, std::vector<BamRec>());
-    par_for(N, threads, [&](size_t g0, size_t g1, int t) {
-        std::string &o = enc[t]; o.reserve((g1 - g0) * 176);
-        const uint8_t *pac = b.ctx->ix.ref.pac_data();
-        for (size_t g = g0; g < g1; ++g) {
-            if (g + 8 < g1 && !(b.h_class[g + 8] & PS_CLS_HOST) && b.h_fin[g + 8].type) __builtin_prefetch(pac + ((size_t)b.h_fin[g + 8].pos >> 2));   // as batch_write_sam
-            BamRec r; if (bam_record(b, (int64_t)g, min_mapq, o, r)) recs[t].push_back(r);
-        }
-    });
-}
-
-void batch_profile_records(const Batch &b, int min_mapq, int threads, ProfRecords &out)
-{
-    if (!b.located) throw Error("profile records before locate");
-    const ReadSet &rs = b.rs; const RefSeq &ref = b.ctx->ix.ref;
-    const size_t N = (size_t)rs.n;
-    const int nt = par_threads(N, threads);
-    // pass 1: which reads are in the filtered file, and how much they hold
-    std::vector<uint8_t> keep(N, 0);
-    std::vector<size_t> t_rec(nt + 1, 0), t_cig(nt + 1, 0), t_base(nt + 1, 0);
-    par_for(N, threads, [&](size_t g0, size_t g1, int t) {
-        size_t nr = 0, nc = 0, nb = 0;
-        for (size_t g = g0; g < g1; ++g) {
-            Hit h; b.hit_of((int64_t)g, h);
-            if (h.type == 0 || h.mapq < min_mapq) continue;
-            const int len = rs.len[g];
-            int seqid = 0;
-            const int span = (int)ref_span(h.n_cigar, h.cigar, len);
-            ref.cnt_ambi(h.pos, span, &seqid);
-            const Contig &ct = ref.contigs[seqid];
-            if (h.pos + span - ct.offset > ct.len) continue;          // bridges two sequences: the SAM line carries flag 4 (sam_line)
-            keep[g] = 1; ++nr; nc += h.n_cigar ? (size_t)h.n_cigar : 1; nb += (size_t)len + ((size_t)len & 1);
-        }
-        t_rec[t] = nr; t_cig[t] = nc; t_base[t] = nb;
-    });
-    size_t r0 = out.n(), c0 = out.cigar.size(), b0 = out.seq.size() * 2;     // every record starts on a whole byte
-    std::vector<size_t> br(nt + 1), bc(nt + 1), bb(nt + 1);
-    br[0] = r0; bc[0] = c0; bb[0] = b0;
-    for (int t = 0; t < nt; ++t) { br[t + 1] = br[t] + t_rec[t]; bc[t + 1] = bc[t] + t_cig[t]; bb[t + 1] = bb[t] + t_base[t]; }
-    out.gpos.resize(br[nt]); out.l_seq.resize(br[nt]); out.flag.resize(br[nt]); out.cig_off.resize(br[nt]); out.n_cig.resize(br[nt]); out.seq_off.resize(br[nt]);
-    out.cigar.resize(bc[nt]); out.seq.resize(bb[nt] / 2);
-    // pass 2: fill, every thread its own range
-    static const uint8_t NIB[5] = {1, 2, 4, 8, 15}, NIB_RC[5] = {8, 4, 2, 1, 15};
-    par_for(N, threads, [&](size_t g0, size_t g1, int t) {          // the same ranges as in pass 1
-        size_t r = br[t], c = bc[t], bs = bb[t];
-        for (size_t g = g0; g < g1; ++g) {
-            if (!keep[g]) continue;
-            Hit h; b.hit_of((int64_t)g, h);
-            const int len = rs.len[g];
-            const uint8_t *seq = rs.seq.data() + rs.off[g];
-            out.gpos[r] = h.pos; out.l_seq[r] = len; out.flag[r] = h.strand ? 16u : 0u;
-            out.cig_off[r] = (uint32_t)c; out.seq_off[r] = (uint64_t)bs;
-            if (h.n_cigar) { for (int j = 0; j < h.n_cigar; ++j) { const uint32_t op = h.cigar[j] & 0xfu; out.cigar[c++] = (h.cigar[j] & ~0xfu) | (op == 3 ? 4u : op); } out.n_cig[r] = (uint32_t)h.n_cigar; }
-            else { out.cigar[c++] = (uint32_t)len << 4; out.n_cig[r] = 1; }
-            uint8_t *d = out.seq.data() + bs / 2;
-            for (int i = 0; i < len; i += 2) {
-                const uint8_t hi = h.strand ? NIB_RC[seq[len - 1 - i]] : NIB[seq[i]];
-                const uint8_t lo = i + 1 < len ? (h.strand ? NIB_RC[seq[len - 2 - i]] : NIB[seq[i + 1]]) : 0;
-                d[i >> 1] = (uint8_t)(hi << 4 | lo);
-            }
-            bs += (size_t)len + ((size_t)len & 1);
-            ++r;
-        }
-    });
-}
-
-// @SQ per reference sequence in FASTA order, then our @PG: what upstream's samse prints before the first record -- also when
-// there is no record at all (bwa_print_sam_SQ runs before the read loop)
-std::string sam_header(const RefSeq &ref, const char *pg_line)
-{
-    std::string h;
-    for (const Contig &c : ref.contigs) { h += "@SQ\tSN:"; h += c.name; h += "\tLN:"; put_int(h, c.len); h.push_back('\n'); }
-    if (pg_line && pg_line[0]) { h += pg_line; h += "\n"; }
-    return h;
-}
-
-void batch_write_sam(Batch &b, const char *path, bool header, const char *pg_line, int threads, bool append, SamScratch *scratch)
-{
-    if (!b.located) throw Error("write_sam before locate");
-    const int fd = ::open(path, O_WRONLY | O_CREAT | (append ? 0 : O_TRUNC), 0644);
-    if (fd < 0) throw Error(std::string("cannot write ") + path);
-    struct Closer { int fd; bool done = false; ~Closer() { if (!done) ::close(fd); } } closer{fd};
-    off_t at = append ? ::lseek(fd, 0, SEEK_END) : 0;
-    if (at < 0) throw Error(std::string("cannot seek in ") + path);
-    auto put = [&](const char *p, size_t n, off_t where) {           // the whole buffer at its place in the file
-        while (n) { const ssize_t w = ::pwrite(fd, p, n, where); if (w <= 0) return false; p += w; n -= (size_t)w; where += w; }
-        return true;
-    };
-    if (header) {
-        const std::string h = sam_header(b.ctx->ix.ref, pg_line);
-        if (!put(h.data(), h.size(), at)) throw Error(std::string("short write on ") + path);
-        at += (off_t)h.size();
-    }
-    const int64_t N = b.rs.n;
-    if (threads < 1) threads = 1;
-    if (threads > 64) threads = 64;
-    // rounds of threads x 64k reads: every thread formats its range; the text of a round is then written -- each buffer at its
-    // own offset (pwrite), by a few I/O threads side by side -- while the next round is formatted.  (One writer thread managed
-    // ~1 GB/s and was the slowest stage of ps_map at 2 GB of SAM per 10 M reads.)
-    const int64_t chunk = 1 << 16;
-    SamScratch own;
-    std::vector<std::string> *bufs = scratch ? scratch->bufs : own.bufs;
-    for (int k = 0; k < 2; ++k) if (bufs[k].size() < (size_t)threads) bufs[k].resize((size_t)threads);
-    std::vector<off_t> where[2] = {std::vector<off_t>((size_t)threads, 0), std::vector<off_t>((size_t)threads, 0)};
-    std::vector<size_t> lens[2] = {std::vector<size_t>((size_t)threads, 0), std::vector<size_t>((size_t)threads, 0)};
-    std::thread io; std::atomic<bool> io_ok{true};
-    const int n_io = std::max(1, std::min(8, threads));
-    int which = 0;
-    static const bool verbose = std::getenv("PS_VERBOSE") != nullptr && std::atoi(std::getenv("PS_VERBOSE")) >= 2;
-    double t_fmt = 0, t_wait = 0; const auto tw0 = std::chrono::steady_clock::now();
-    for (int64_t base = 0; base < N; base += chunk * threads, which ^= 1) {
-        const auto tf0 = std::chrono::steady_clock::now();
-        std::vector<std::string> &out = bufs[which];          // the I/O threads may still hold the other set
-        std::vector<size_t> &used = lens[which];
-        auto fmt = [&](int t) {
-            int64_t g0 = base + chunk * t, g1 = std::min(N, g0 + chunk);
-            std::string &o = out[t];                           // storage: its size is what it can hold, used[t] what it does hold
-            size_t u = 0;
-            if (g0 < g1) room(o, 0, (size_t)(g1 - g0) * 224);
-            const uint8_t *pac = b.ctx->ix.ref.pac_data();
-            for (int64_t g = g0; g < g1; ++g) {
-                if (g + 8 < g1 && !(b.h_class[g + 8] & PS_CLS_HOST) && b.h_fin[g + 8].type) __builtin_prefetch(pac + ((size_t)b.h_fin[g + 8].pos >> 2));   // the reference bases of a read further on (MD tag): a cache miss each
-                sam_line(b, g, o, u);
-            }
-            used[t] = u;
-        };
-        { std::vector<std::thread> th; for (int t = 1; t < threads; ++t) th.emplace_back(fmt, t); fmt(0); for (auto &x : th) x.join(); }
-        const auto tf1 = std::chrono::steady_clock::now();
-        if (io.joinable()) io.join();
-        t_fmt += std::chrono::duration<double>(tf1 - tf0).count(); t_wait += std::chrono::duration<double>(std::chrono::steady_clock::now() - tf1).count();
-        if (!io_ok) break;
-        std::vector<off_t> &wh = where[which];
-        for (int t = 0; t < threads; ++t) { wh[t] = at; at += (off_t)used[t]; }
-        io = std::thread([&out, &wh, &used, &put, &io_ok, n_io, threads]() {
-            auto part = [&](int k) { for (int t = k; t < threads; t += n_io) if (used[t] && !put(out[t].data(), used[t], wh[t])) io_ok = false; };
-            std::vector<std::thread> th; for (int k = 1; k < n_io; ++k) th.emplace_back(part, k); part(0); for (auto &x : th) x.join();
-        });
-    }
-    const auto tl0 = std::chrono::steady_clock::now();
-    if (io.joinable()) io.join();
-    if (verbose) std::fprintf(stderr, "[parasuite-hip]     SAM text of %lld reads: %.0f ms (formatting on %d threads %.0f ms, waiting for the previous round's pwrite %.0f ms, last round's pwrite %.0f ms), %.0f MB\n", (long long)N,
-                              1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tw0).count(), threads, 1e3 * t_fmt, 1e3 * t_wait, 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - tl0).count(), at / 1048576.0);
-    if (!io_ok) throw Error(std::string("short write on ") + path);
-    closer.done = true;
-    if (::close(fd) != 0) throw Error(std::string("cannot close ") + path);
 }
 
 }  // namespace ps

@@ -215,6 +215,60 @@ typedef struct { uint64_t n_records, n_unmapped, n_skipped_indel, n_kept, n_clus
                  n_order_unmodelled; } ps_cluster_stats;
 int     ps_pileup_clusters(const char *mapping_sam_or_bam, const char *ref_fa, const char *out_file, const char *snp_vcf,
                            int min_read_coverage, const char *site_prefix, ps_cluster_stats *stats /* may be NULL */);
+/* ---- the transcript route of `map -t TRANSCRIPTS.fa` (Main.java:363-416) ----------------------------------------------
+ * Step 2, `new ExtractWeakMappingReads().extractReads(mapping, mappingNew, fastq, 10)` (ExtractWeakMappingReads.java:40-94):
+ * the records of a SAM or BAM file in file order; one with MAPQ < mapq_threshold becomes four FASTQ lines "@QNAME", SEQ, "+",
+ * QUAL ('\n' line ends; with flag 16 SEQ is reverse-complemented as SequenceUtil.reverseComplement does -- A C G T swapped,
+ * every other base code kept -- and QUAL reversed, i.e. the read as it was sequenced), every other record goes to out_bam
+ * unchanged under the input's header and reference table (what ps_bam_view keeps at that threshold).  Host code (zlib);
+ * needs no GPU.  out_bam and out_fastq may not be the input file: the caller renames, as Main.java:376-377 does.
+ * Deviations: a weak record with SEQ '*' or without QUAL is an error naming the record (the Java writes a FASTQ no parser
+ * takes), and nothing is left behind then; SEQ comes out in upper case (BAM's 4-bit codes). */
+typedef struct { uint64_t n_records, n_weak, n_kept, bam_bytes; } ps_extract_stats;
+int     ps_extract_weak_reads(const char *mapping_sam_or_bam, const char *out_bam, const char *out_fastq,
+                              int mapq_threshold, int threads, ps_extract_stats *stats /* may be NULL */);
+/* Step 5 and the toolkit's `comb -g GENOMIC -t TRANSCRIPT -o OUT` mode (Main.java:438-488),
+ * `new CombineGenomeTranscript().combine(genome, transcript, out)` (CombineGenomeTranscript.java:36-666): out_bam holds all
+ * genomic records in file order, then the transcript hits lifted to genome coordinates in transcript-file order, under the
+ * genomic file's header and reference table.  Both inputs are SAM or BAM.  The lift runs on the GPU; the rules are those of
+ * the Java as it is written, restated in plain Python in tests/java_combine.py (no JVM is at hand to pin it to the jar):
+ *   - the transcript file must be SO:queryname by its header, else an error and nothing is written (the Java logs, exits 0);
+ *   - records with RNAME '*' are passed over (n_unplaced); they neither break nor start a name group;
+ *   - the transcript's name is split on '|': field 2 chromosome without "chr", 3 exon starts and 4 exon ends (';'-separated,
+ *     EACH SORTED AS STRINGS -- Arrays.sort(String[]), so "100000" sorts before "99990"), 5 strand; parsed once per transcript
+ *     that a record names.  Fewer than six fields, an exon that is not an int, or unequal counts: an error naming the transcript;
+ *   - strand "1" (:211-390) walks the exons upwards, "-1" (:391-518) downwards: start = exonStart + (alnStart - passedBefore) - 1,
+ *     on -1 the end is exonEnd - (alnStart - passedBefore) + 1.  A read inside one exon keeps its own CIGAR (on -1 its start is
+ *     end - READ LENGTH + 1, not the reference span); a read across junctions gets xM yN ... zM.  An intron of length <= 0 or a
+ *     run past the last exon ends the walk with what was built.  A read across a junction with I or D in its CIGAR is counted in
+ *     n_missed_indel_splice: on "1" it is still emitted with the CIGAR built so far (possibly none: '*'), on "-1" its start is
+ *     still -1 and it is dropped.  Any other strand string locates nothing.  Records without a start: n_unlocated;
+ *   - this library's rule for getAlignmentEnd: alignment start + reference length of the CIGAR - 1, and 0 for a record with
+ *     flag 4 (bwa's bridging records keep RNAME, POS and CIGAR; htsjdk 1.128 answers 0 for an unmapped record, as far as the
+ *     maintainers remember it).  Worked cases, exons 1000-1099 and 2000-2099, strand "1": a flag-4 record at POS 91 with 20M
+ *     lies in exon 0, 0 <= 100 ends the walk there and it is located at 1090 with its own 20M, not 10M1900N10M; the same
+ *     record at POS 150 finds no start in exon 0 (150 > 100), 0 <= 100 ends the walk and it stays unlocated;
+ *   - a group is a maximal run of equal QNAME among the records with a reference.  Its located records, in file order, form a
+ *     list; unequal lifted starts: the group emits nothing (n_groups_ambiguous); else ONE record is emitted, the list entry
+ *     whose index was last stored by a record without flag 0x100 (entry 0 if there was none), with its own start and CIGAR;
+ *   - the contig is "chr" + field 2; absent from the genomic header: nothing emitted (n_no_contig).  "MT" is looked up as
+ *     "chrMT" FIRST (the Java's order), then placed on "chrM"; without chrM the record is written with reference id -1 and its
+ *     lifted position (n_mt_unplaced);
+ *   - the emitted record: new reference id, POS, CIGAR, bin, MAPQ 10; for strand "-1" flag 16 toggled and SEQ
+ *     reverse-complemented, QUAL NOT reversed (as in the Java); name, other flags, mate fields and tags unchanged.
+ * n_spliced counts located records (emitted or not) whose lifted CIGAR holds an N (:539-541); n_groups the name groups.
+ * Deviations: (1) htsjdk's writer would always sort here (the header says coordinate, presorted is false); the unsorted form
+ * (sort_by_coordinate 0) is this library's own; it carries the genomic header as it is, @HD SO: NOT rewritten, so a genomic
+ * file that says SO:coordinate yields an unsorted output that still says so -- sort it (or ask for the sorted form) before a
+ * tool that trusts @HD reads it.  With sort_by_coordinate the sequence above is sorted stably, byte for byte
+ * what ps_bam_sort makes of the unsorted output; write_index adds <out_bam>.bai.  (2) A lifted start below base 1 other
+ * than -1 (a flag-4 record beyond the last exon of a "-1" transcript gets -READ LENGTH) is treated like -1: the Java would
+ * hand htsjdk a record before its contig's first base.  (3) Errors where the Java throws (above) write nothing.
+ * Without a HIP device the call fails. */
+typedef struct { uint64_t n_genome, n_transcript, n_unplaced, n_unlocated, n_missed_indel_splice, n_groups,
+                 n_groups_ambiguous, n_no_contig, n_mt_unplaced, n_lifted, n_spliced, n_strand_flipped, bam_bytes; } ps_combine_stats;
+int     ps_combine_genome_transcript(const char *genome_bam, const char *transcript_bam, const char *out_bam,
+                                     int sort_by_coordinate, int write_index, int threads, ps_combine_stats *stats /* may be NULL */);
 /* The first pass and its error profile in one call -- "fed directly from alignment results" (SURVEY.md §8f rank 4): ps_map, and
  * while the SAM is written the same records, straight from memory, go through the counting kernel: the alignments with
  * MAPQ >= min_mapq, i.e. what the pass's filtered BAM holds (samtools view -q, PARAsuiteMapping.java:124-133 /

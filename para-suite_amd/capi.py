@@ -44,7 +44,7 @@ EXPORTS = ["ps_version", "ps_last_error", "ps_index", "ps_map", "ps_ctx_open", "
            "ps_ctx_blob", "ps_ctx_meta", "ps_ctx_from_blobs", "ps_ctx_clone", "ps_ctx_fetch", "ps_ctx_export_blob", "ps_ctx_sa_lookup", "ps_ctx_order_sort", "ps_ctx_index_check", "ps_sam_to_bam", "ps_map_to_bam", "ps_bam_view", "ps_bam_sort", "ps_bam_index", "ps_batch_from_fastq",
            "ps_batch_from_codes", "ps_batch_free", "ps_batch_n", "ps_batch_search", "ps_batch_select_hard",
            "ps_batch_select_easy", "ps_batch_locate", "ps_batch_run", "ps_batch_write_sam", "ps_batch_n_aln",
-           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_map_profiled", "ps_release_host_cache"]
+           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache"]
 
 _LIB = None
 
@@ -384,6 +384,35 @@ def ps_pileup_clusters(mapping, ref_fa, out_file, snp_vcf=None, min_read_coverag
     st = ClusterStats()
     _chk(L.ps_pileup_clusters(enc(mapping), enc(ref_fa), enc(out_file), enc(snp_vcf), int(min_read_coverage), enc(site_prefix), C.byref(st)))
     return {f: int(getattr(st, f)) for f, _ in ClusterStats._fields_}
+
+
+class ExtractStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_records", "n_weak", "n_kept", "bam_bytes")]
+
+
+def ps_extract_weak_reads(mapping, out_bam, out_fastq, mapq_threshold=10, threads=8):
+    """ExtractWeakMappingReads.extractReads: records with MAPQ < mapq_threshold -> out_fastq (read orientation restored), the
+    others -> out_bam under the input's header (host code, needs no GPU); returns the counters"""
+    L = lib(); L.ps_extract_weak_reads.argtypes = [C.c_char_p] * 3 + [C.c_int, C.c_int, C.POINTER(ExtractStats)]
+    st = ExtractStats()
+    _chk(L.ps_extract_weak_reads(mapping.encode(), out_bam.encode(), out_fastq.encode(), int(mapq_threshold), int(threads), C.byref(st)))
+    return {f: int(getattr(st, f)) for f, _ in ExtractStats._fields_}
+
+
+class CombineStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_genome", "n_transcript", "n_unplaced", "n_unlocated", "n_missed_indel_splice", "n_groups",
+                                          "n_groups_ambiguous", "n_no_contig", "n_mt_unplaced", "n_lifted", "n_spliced",
+                                          "n_strand_flipped", "bam_bytes")]
+
+
+def ps_combine_genome_transcript(genome_bam, transcript_bam, out_bam, sort_by_coordinate=False, write_index=False, threads=8):
+    """CombineGenomeTranscript.combine: the genomic records, then the transcript hits lifted to genome coordinates (on the GPU),
+    optionally coordinate-sorted with <out_bam>.bai; returns the counters"""
+    L = lib(); L.ps_combine_genome_transcript.argtypes = [C.c_char_p] * 3 + [C.c_int] * 3 + [C.POINTER(CombineStats)]
+    st = CombineStats()
+    _chk(L.ps_combine_genome_transcript(genome_bam.encode(), transcript_bam.encode(), out_bam.encode(), int(bool(sort_by_coordinate)),
+                                        int(bool(write_index)), int(threads), C.byref(st)))
+    return {f: int(getattr(st, f)) for f, _ in CombineStats._fields_}
 
 
 def ps_map_profiled(threads, mm, error_profile, indel_profile, ref_fa, reads, out_sam, min_mapq, max_read_len, profile_prefix):

@@ -5,6 +5,7 @@
 // processes and three rewrites of the data for.  Formats follow the public SAM/BAM specification (SAMv1:
 // BGZF blocks of at most 64 KiB with the BC extra field, BAM records, binning index with 16 kb linear index);
 // integer tags take the smallest type as htslib's SAM parser does.  Host code only (zlib), no device work.
+#include <sys/stat.h>
 #include <zlib.h>
 #include <algorithm>
 #include <cctype>
@@ -677,6 +678,91 @@ void load_alignments(const char *path, int threads, AlnTable &out, bool with_qua
             if (with_qual) std::memcpy(&out.qual[(size_t)out.seq_off[i]], e.data() + seq_at + (out.l_seq[i] + 1) / 2, (size_t)out.l_seq[i]);
         }
     });
+}
+
+static std::string header_sort_order(const std::string &text)
+{
+    if (text.compare(0, 3, "@HD") != 0) return std::string();
+    const std::string hd = text.substr(0, text.find('\n'));
+    const size_t at = hd.find("\tSO:");
+    if (at == std::string::npos) return std::string();
+    const size_t e = hd.find('\t', at + 1);
+    return hd.substr(at + 4, e == std::string::npos ? e : e - at - 4);
+}
+static void load_any(const char *path, int threads, Data &d)
+{
+    unsigned char mg[2] = {0, 0};
+    { FILE *f = std::fopen(path, "rb"); if (!f) throw Error(std::string("cannot open ") + path); const size_t g = std::fread(mg, 1, 2, f); (void)g; std::fclose(f); }
+    if (mg[0] == 31 && mg[1] == 139) load_bam(path, threads, d, nullptr, nullptr); else load_sam(path, -1, threads, d);
+}
+
+void load_records(const char *path, int threads, BamFile &out)
+{
+    threads = clamp_threads(threads);
+    Data d;
+    load_any(path, threads, d);
+    out = BamFile();
+    out.sort_order = header_sort_order(d.text);
+    out.text.swap(d.text); out.refs.swap(d.refs); out.enc.swap(d.enc); out.recs.swap(d.recs);
+}
+
+bool same_file(const char *a, const char *b)
+{
+    if (!std::strcmp(a, b)) return true;
+    struct stat sa, sb;
+    return stat(a, &sa) == 0 && stat(b, &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
+}
+
+// ExtractWeakMappingReads.java:40-94.  The FASTQ text and the list of kept records are complete before either file is opened, so
+// an error (a weak record without SEQ or QUAL) leaves nothing behind.  The price is a second copy in memory of every weak read's
+// bases and qualities next to the encoded records; if that ever matters, check the error conditions in a first pass over the
+// records and stream the text in a second.
+void extract_weak_reads(const char *path, const char *out_bam, const char *out_fastq, int mapq_threshold, int threads, ExtractStats *stats)
+{
+    threads = clamp_threads(threads);
+    if (!path || !out_bam || !out_fastq || !out_bam[0] || !out_fastq[0]) throw Error("ps_extract_weak_reads: mapping file, output BAM and output FASTQ are required");
+    if (same_file(path, out_bam) || same_file(path, out_fastq)) throw Error(std::string("ps_extract_weak_reads: the output may not be the input file ") + path + " (write to a new name and rename)");
+    if (same_file(out_bam, out_fastq)) throw Error("ps_extract_weak_reads: the BAM and the FASTQ output are the same file");
+    Data d;
+    load_any(path, threads, d);
+    static const char nt16[] = "=ACMGRSVTWYHKDBN";
+    std::string fq; std::vector<Rec> keep; keep.reserve(d.recs.size());
+    uint64_t n_weak = 0;
+    for (const Rec &r : d.recs) {
+        if (rec_mapq(d, r) >= mapq_threshold) { keep.push_back(r); continue; }
+        const std::string &e = d.enc[r.part];
+        const uint32_t l_name = rd32(e, r.off + 12) & 0xff, n_cig = rd32(e, r.off + 16) & 0xffff, l_seq = rd32(e, r.off + 20);
+        const unsigned char *sq = (const unsigned char *)e.data() + r.off + 36 + l_name + 4 * (size_t)n_cig, *ql = sq + (l_seq + 1) / 2;
+        const char *name = rec_name(d, r);
+        if (l_seq == 0) throw Error(std::string("ps_extract_weak_reads: record ") + name + " has MAPQ below " + std::to_string(mapq_threshold) + " and no SEQ ('*'): it cannot be written as FASTQ");
+        if (ql[0] == 0xff) throw Error(std::string("ps_extract_weak_reads: record ") + name + " has MAPQ below " + std::to_string(mapq_threshold) + " and no QUAL ('*'): it cannot be written as FASTQ");
+        ++n_weak;
+        fq.push_back('@'); fq.append(name); fq.push_back('\n');
+        const size_t at = fq.size();
+        fq.resize(at + 2 * (size_t)l_seq + 3);
+        char *s = &fq[at], *q = s + l_seq + 3;
+        s[l_seq] = '\n'; s[l_seq + 1] = '+'; s[l_seq + 2] = '\n';
+        const bool rev = (r.flag & 16u) != 0;
+        for (uint32_t i = 0; i < l_seq; ++i) {
+            char c = nt16[(sq[i >> 1] >> ((~i & 1u) << 2)) & 15];
+            if (rev) switch (c) { case 'A': c = 'T'; break; case 'C': c = 'G'; break; case 'G': c = 'C'; break; case 'T': c = 'A'; break; default: break; }
+            const uint32_t to = rev ? l_seq - 1 - i : i;
+            s[to] = c; q[to] = (char)(ql[i] + 33);
+        }
+        fq.push_back('\n');
+    }
+    const uint64_t n_records = d.recs.size();
+    d.recs.swap(keep);
+    BamStats bs;
+    try {
+        write_bam(d, out_bam, false, threads, &bs);
+        FILE *f = std::fopen(out_fastq, "wb");
+        if (!f) throw Error(std::string("cannot write ") + out_fastq);
+        bool ok = std::fwrite(fq.data(), 1, fq.size(), f) == fq.size();
+        ok = (std::fclose(f) == 0) && ok;
+        if (!ok) throw Error(std::string("short write on ") + out_fastq);
+    } catch (...) { std::remove(out_bam); std::remove(out_fastq); throw; }
+    if (stats) { stats->n_records = n_records; stats->n_weak = n_weak; stats->n_kept = bs.n_out; stats->bam_bytes = bs.bam_bytes; }
 }
 
 }  // namespace ps

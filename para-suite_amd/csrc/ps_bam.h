@@ -51,4 +51,20 @@ struct AlnTable {
     size_t n() const { return ref.size(); }
 };
 void load_alignments(const char *sam_or_bam, int threads, AlnTable &out, bool with_qual = false);                                                          // samtools index -> <bam>.bai
+// the records of a SAM or BAM file as they are encoded (SAMv1 4.2), for the steps that pass records on: name, MAPQ, mate fields,
+// QUAL and the raw tag bytes are all in rec(i); recs[i] carries reference id, position, end and flag.  Records in file order;
+// the records of part k are one run of recs, parts in order.
+struct BamFile {
+    std::string text; std::vector<std::pair<std::string, uint32_t>> refs;   // header text, @SQ name and length
+    std::vector<std::string> enc; std::vector<BamRec> recs;
+    std::string sort_order;                                                 // SO: of the @HD line ("" when there is none)
+    size_t n() const { return recs.size(); }
+    const uint8_t *rec(size_t i) const { return (const uint8_t *)enc[(size_t)recs[i].part].data() + recs[i].off; }   // block_size first
+};
+void load_records(const char *sam_or_bam, int threads, BamFile &out);
+bool same_file(const char *a, const char *b);   // the same path, or two paths to one file (device and inode)
+struct ExtractStats { uint64_t n_records = 0, n_weak = 0, n_kept = 0, bam_bytes = 0; };
+// ExtractWeakMappingReads.extractReads: records with MAPQ < mapq_threshold -> four FASTQ lines each (read orientation restored),
+// the others -> out_bam with the input's header
+void extract_weak_reads(const char *sam_or_bam, const char *out_bam, const char *out_fastq, int mapq_threshold, int threads, ExtractStats *stats);
 }

@@ -805,6 +805,31 @@ int ps_pileup_clusters(const char *mapping_sam_or_bam, const char *ref_fa, const
     PS_CATCH_INT
 }
 
+// Step 2 of `map -t` (Main.java:363-377): ExtractWeakMappingReads.extractReads.  Host code.
+int ps_extract_weak_reads(const char *mapping_sam_or_bam, const char *out_bam, const char *out_fastq, int mapq_threshold, int threads,
+                          ps_extract_stats *stats)
+{
+    PS_TRY
+        ExtractStats s;
+        extract_weak_reads(mapping_sam_or_bam, out_bam, out_fastq, mapq_threshold, threads, &s);
+        if (stats) { stats->n_records = s.n_records; stats->n_weak = s.n_weak; stats->n_kept = s.n_kept; stats->bam_bytes = s.bam_bytes; }
+        return 0;
+    PS_CATCH_INT
+}
+
+// Step 5 of `map -t` and the `comb` mode (Main.java:438-488): CombineGenomeTranscript.combine.  The output is opened only after
+// every device stage has completed and every lifted record is built: an error before that leaves no file.
+int ps_combine_genome_transcript(const char *genome_bam, const char *transcript_bam, const char *out_bam, int sort_by_coordinate,
+                                 int write_index, int threads, ps_combine_stats *stats)
+{
+    PS_TRY
+        int dev = 0;
+        if (const char *e = std::getenv("PARASUITE_GPU_IDS")) dev = std::atoi(e);
+        combine_run(genome_bam, transcript_bam, out_bam, sort_by_coordinate != 0, write_index != 0, threads, dev, stats);
+        return 0;
+    PS_CATCH_INT
+}
+
 int ps_sam_to_bam(const char *sam, const char *bam, int min_mapq, int sort_by_coordinate, int write_index, int threads, ps_bam_stats *st)
 {
     PS_TRY

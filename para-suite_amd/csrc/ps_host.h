@@ -133,4 +133,8 @@ std::string java_double_to_string(double v);                                    
 void pileup_clusters_run(const char *mapping_sam_or_bam, const char *ref_fa, const char *out_file, const char *snp_vcf, int min_cov,
                          const char *site_prefix, int device, ps_cluster_stats *stats);
 
+// ---- transcript hits lifted onto the genome and appended to the genomic mapping (ps_combine.hip; CombineGenomeTranscript.combine) ----
+void combine_run(const char *genome_sam_or_bam, const char *transcript_sam_or_bam, const char *out_bam, bool sort_by_coordinate, bool write_index,
+                 int threads, int device, ps_combine_stats *stats);
+
 }  // namespace ps

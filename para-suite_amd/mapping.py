@@ -178,3 +178,30 @@ class PileupClusters:
             return capi.ps_pileup_clusters(alignmentFile, referenceFile, outputFile, snpVcfFile, int(minReadCoverage))
         except capi.PsError as e:
             raise ExternalCallErrorException("PileupClusters %s: %s" % (alignmentFile, e))
+
+
+class ExtractWeakMappingReads:
+    """mirror of utils.postprocessing.ExtractWeakMappingReads (ExtractWeakMappingReads.java:40-94), step 2 of `map -t`
+    (Main.java:363-377): `new ExtractWeakMappingReads().extractReads(mappingFileName, mappingFileNameNew, unalignedReadFileName,
+    mapqThreshold)` moves the reads with MAPQ < mapqThreshold into a FASTQ file and writes the BAM without them
+    (`ps_extract_weak_reads`, host code).  The caller renames mappingFileNameNew, as Main does.  Returns the stats dict."""
+
+    def extractReads(self, mappingFileName, mappingFileNameNew, unalignedReadFileName, mapqThreshold):
+        try:
+            return capi.ps_extract_weak_reads(mappingFileName, mappingFileNameNew, unalignedReadFileName, int(mapqThreshold))
+        except capi.PsError as e:
+            raise ExternalCallErrorException("ExtractWeakMappingReads %s: %s" % (mappingFileName, e))
+
+
+class CombineGenomeTranscript:
+    """mirror of utils.postprocessing.CombineGenomeTranscript (CombineGenomeTranscript.java:36-666), step 5 of `map -t` and the
+    `comb` mode (Main.java:400-404, 438-488): `new CombineGenomeTranscript().combine(genomeMappingFileName,
+    transcriptMappingFileName, combinedFileName)` appends the transcript hits, lifted to genome coordinates on the GPU, to the
+    genomic records (`ps_combine_genome_transcript`).  htsjdk's writer sorts the result by coordinate, so this does too; the
+    index is left to Mapping.sortByCoordinateAndIndex's mirror (`capi.ps_bam_index`).  Returns the stats dict."""
+
+    def combine(self, genomeMappingFileName, transcriptMappingFileName, combinedFileName):
+        try:
+            return capi.ps_combine_genome_transcript(genomeMappingFileName, transcriptMappingFileName, combinedFileName, True, False)
+        except capi.PsError as e:
+            raise ExternalCallErrorException("CombineGenomeTranscript %s %s: %s" % (genomeMappingFileName, transcriptMappingFileName, e))

@@ -278,6 +278,52 @@ int     ps_map_profiled(int threads, const char *mm, const char *error_profile, 
                         const char *ref_fa, const char *reads_fq, const char *out_sam,
                         int min_mapq, int max_read_len, const char *profile_prefix);
 
+/* ---- the whole `map` mode in one call (Main.java:249-420, BWA and PARA-suite mappers) -----------------------------------------
+ * `-q READS -r REF [-t TRANSCRIPTS] -o PREFIX [--refine]`: the stock pass, the error profile of its records, the profile pass,
+ * the weak-read extraction, the transcript pass, the name sort, the lift and the coordinate sorts with their indexes, leaving
+ * the files Main.java names (<P> = out_prefix; "sorted" = by coordinate with a .bai next to it):
+ *   no refine, no transcripts   <P>.BWA-genomic.bam sorted (MAPQ >= mapq_genomic)
+ *   no refine, transcripts      <P>.BWA-genomic.bam sorted (the records the extraction keeps), <P>.BWA-transcript.bam sorted by name
+ *                               (MAPQ >= mapq_transcript), <P>.combined.bam sorted
+ *   refine                      <P>.BWA-genomic.bam sorted, <P>.BWA-genomic.bam.errorprofile / .indelprofile, <P>.PARAsuite-genomic.bam
+ *                               sorted; with transcripts also <P>.PARAsuite-transcript.bam and <P>.combined.bam
+ *   refine with error_profile   no first pass and no profile files of its own; the rest as the refine rows
+ * Every file holds what the calls above write under that name when issued one by one (ps_map_to_bam; ps_error_profile on the
+ * filtered first-pass BAM; ps_map_to_bam with the two profile files; ps_extract_weak_reads and the rename; ps_bam_sort and
+ * ps_bam_index; ps_map_to_bam on the weak FASTQ against the transcripts; ps_bam_sort -n; ps_combine_genome_transcript sorted and
+ * indexed): BAMs record for record, header included, profile files byte for byte.  Inside the call the reads file is parsed once
+ * (the parsed pieces stay in host memory for the profile pass, up to PS_ROUTE_KEEP_MB megabytes -- default 8192; a
+ * larger input is parsed again, with the same output), each index is loaded once and stays in HBM with its lanes of work until the
+ * call returns (the transcript pass takes over the genome passes' lanes), the weak reads go to the transcript pass from memory
+ * (names as a second parse leaves them: one more trailing /1 or /2 removed), and no BAM is written to be read back.  Each pass is
+ * a samse run of its own (its tie-break stream starts at 0).  ps_index runs for a reference whose .bwt is missing.  Nothing stays
+ * resident when the call returns.
+ * Errors before anything is touched: error_profile without refine (nothing to map), a missing reads_fq / ref_fa / out_prefix, an
+ * output name that is one of the inputs, no HIP device.  FASTA reads with a transcript route fail as ps_extract_weak_reads does on
+ * records without QUAL.  On any error ps_last_error() names the step ("first pass", "profile", "refine pass", "transcript pass",
+ * "combine") and every file the call created is removed -- outputs are written under <name>.route-tmp and renamed when their
+ * step is done -- except index files that ps_index wrote.  "Created" goes by name: a file of an output's name left by an earlier
+ * run is overwritten when its step is done and removed with the rest when a later step fails.  An indel_profile without an
+ * error_profile is refused too, and an output's temporary name counts as the output where the inputs are compared.
+ * stats: first / refine / transcript are the stats of the BAM each pass left (zeros for a pass that did not run; bam_bytes of the
+ * file as written here); extract.bam_bytes is 0 (no intermediate BAM exists); n_index_loads_*: how often an index was read from its
+ * files (1 per reference used); n_fastq_parses: 1, or 2 when the input exceeded PS_ROUTE_KEEP_MB.  PS_VERBOSE=1 prints the stage times. */
+typedef struct {
+    const char *reads_fq, *ref_fa, *out_prefix;      /* -q -r -o : required */
+    const char *transcripts_fa;                      /* -t ; NULL or "": no transcript route */
+    const char *bwa_mm, *parasuite_mm;               /* --bwa-mm ("2"), --parasuite-mm ("-1"); NULL: those defaults */
+    const char *error_profile, *indel_profile;       /* --parasuite-ep / --parasuite-indel: given => no first pass (Main.java:193-203) */
+    int32_t threads, refine, max_read_len, mapq_genomic, mapq_transcript;   /* -p, --refine, -l (101), --gm (10), --tm (1); <= 0 where a default exists: the default */
+} ps_route_opts;
+typedef struct {
+    uint64_t n_reads;
+    ps_bam_stats first, refine, transcript;          /* the BAM each pass left; zeros for a pass that did not run */
+    ps_extract_stats extract; ps_combine_stats combine;
+    double s_total, s_parse, s_index_genome, s_index_transcripts, s_first, s_profile, s_refine, s_transcript, s_combine;
+    uint32_t n_index_loads_genome, n_index_loads_transcripts, n_fastq_parses, pad_;
+} ps_route_stats;
+int     ps_map_route(const ps_route_opts *opts, ps_route_stats *stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,7 +44,7 @@ EXPORTS = ["ps_version", "ps_last_error", "ps_index", "ps_map", "ps_ctx_open", "
            "ps_ctx_blob", "ps_ctx_meta", "ps_ctx_from_blobs", "ps_ctx_clone", "ps_ctx_fetch", "ps_ctx_export_blob", "ps_ctx_sa_lookup", "ps_ctx_order_sort", "ps_ctx_index_check", "ps_sam_to_bam", "ps_map_to_bam", "ps_bam_view", "ps_bam_sort", "ps_bam_index", "ps_batch_from_fastq",
            "ps_batch_from_codes", "ps_batch_free", "ps_batch_n", "ps_batch_search", "ps_batch_select_hard",
            "ps_batch_select_easy", "ps_batch_locate", "ps_batch_run", "ps_batch_write_sam", "ps_batch_n_aln",
-           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache"]
+           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route"]
 
 _LIB = None
 
@@ -477,3 +477,35 @@ def ps_bam_sort(in_bam, out_bam, by_name=False, threads=8):
 def ps_bam_index(bam, threads=8):
     L = lib(); L.ps_bam_index.argtypes = [C.c_char_p, C.c_int]
     _chk(L.ps_bam_index(bam.encode(), int(threads)))
+
+
+class RouteOpts(C.Structure):
+    _fields_ = [(k, C.c_char_p) for k in ("reads_fq", "ref_fa", "out_prefix", "transcripts_fa", "bwa_mm", "parasuite_mm",
+                                          "error_profile", "indel_profile")] + \
+               [(k, C.c_int32) for k in ("threads", "refine", "max_read_len", "mapq_genomic", "mapq_transcript")]
+
+
+class RouteStats(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("first", BamStats), ("refine", BamStats), ("transcript", BamStats),
+                ("extract", ExtractStats), ("combine", CombineStats)] + \
+               [(k, C.c_double) for k in ("s_total", "s_parse", "s_index_genome", "s_index_transcripts", "s_first", "s_profile",
+                                          "s_refine", "s_transcript", "s_combine")] + \
+               [(k, C.c_uint32) for k in ("n_index_loads_genome", "n_index_loads_transcripts", "n_fastq_parses", "pad_")]
+
+
+def _struct_dict(st):
+    return {f: (_struct_dict(getattr(st, f)) if isinstance(getattr(st, f), C.Structure) else getattr(st, f)) for f, _ in st._fields_}
+
+
+def ps_map_route(reads_fq, ref_fa, out_prefix, transcripts_fa=None, threads=8, refine=False, max_read_len=101, mapq_genomic=10,
+                 mapq_transcript=1, bwa_mm=None, parasuite_mm=None, error_profile=None, indel_profile=None):
+    """the toolkit's whole `map` mode (Main.java:249-420) in one call: the passes, the error profile, the weak-read extraction, the
+    lift and the sorts with the reads parsed once, each index loaded once and everything between the passes handed over in memory;
+    leaves the files Main.java names under out_prefix and returns ps_route_stats as nested dicts"""
+    enc = lambda v: str(v).encode() if v not in (None, "") else None
+    L = lib(); L.ps_map_route.argtypes = [C.POINTER(RouteOpts), C.POINTER(RouteStats)]
+    o = RouteOpts(enc(reads_fq), enc(ref_fa), enc(out_prefix), enc(transcripts_fa), enc(bwa_mm), enc(parasuite_mm), enc(error_profile),
+                  enc(indel_profile), int(threads), int(bool(refine)), int(max_read_len), int(mapq_genomic), int(mapq_transcript))
+    st = RouteStats()
+    _chk(L.ps_map_route(C.byref(o), C.byref(st)))
+    return _struct_dict(st)

@@ -402,7 +402,7 @@ static void write_bai(const std::string &bai_path, const Data &d, const Layout &
 }
 
 // ---- Data (records in d.recs order) -> BGZF file (+ .bai)
-static void write_bam(Data &d, const char *bam_path, bool write_index, int threads, BamStats *stats, int level = 6)
+static void write_bam(Data &d, const char *bam_path, bool write_index, int threads, BamStats *stats, int level = 6, bool keep_enc = false)
 {
     std::string head;
     head.append("BAM\1", 4); put32(head, (uint32_t)d.text.size()); head += d.text; put32(head, (uint32_t)d.refs.size());
@@ -419,7 +419,7 @@ static void write_bam(Data &d, const char *bam_path, bool write_index, int threa
         const int T = threads; const size_t per = (all.size() + (size_t)T - 1) / (size_t)T;
         par(T, T, [&](int t) { const size_t a0 = (size_t)t * per, a1 = std::min(all.size(), a0 + per); for (size_t i = a0; i < a1; ++i) std::memcpy(&stream[(size_t)uoff[i]], d.enc[all[i].part].data() + all[i].off, all[i].len); });
     }
-    for (auto &e : d.enc) { e.clear(); e.shrink_to_fit(); }
+    if (!keep_enc) for (auto &e : d.enc) { e.clear(); e.shrink_to_fit(); }
     const size_t n_blocks = head_blocks + body_blocks;
     std::vector<std::string> comp(n_blocks);
     {
@@ -517,15 +517,17 @@ void bam_rec_end(std::string &o, BamRec &r)
 
 // ---- records straight from memory (ps_map_to_bam)
 struct BamSink::Impl {
-    Data d; std::string path; bool sort = false, index = false; int threads = 1, level = 6;
+    Data d; std::string path; bool sort = false, index = false, by_name = false; int threads = 1, level = 6;
     FILE *f = nullptr; uint64_t bytes = 0, n_out = 0; bool failed = false;
 };
 BamSink::BamSink(const std::string &header_text, const std::vector<std::pair<std::string, uint32_t>> &refs, const char *bam_path,
-                 bool sort_by_coordinate, bool write_index, int threads, int level) : p(new Impl())
+                 bool sort_by_coordinate, bool write_index, int threads, int level, bool sort_by_name) : p(new Impl())
 {
+    if (sort_by_name && (sort_by_coordinate || write_index)) { delete p; p = nullptr; throw Error("a name-sorted BAM is neither coordinate-sorted nor indexed"); }
     if (write_index && !sort_by_coordinate) { delete p; p = nullptr; throw Error("a .bai index needs coordinate-sorted output"); }
     p->d.text = header_text; p->d.refs = refs; p->path = bam_path; p->sort = sort_by_coordinate; p->index = write_index;
     p->threads = clamp_threads(threads); p->level = level < 0 ? 0 : (level > 9 ? 9 : level);
+    if (sort_by_name) { p->sort = p->by_name = true; header_sorted(p->d.text, "queryname"); return; }
     if (p->sort) { header_sorted(p->d.text, "coordinate"); return; }
     p->f = std::fopen(bam_path, "wb");
     if (!p->f) { const std::string m = std::string("cannot write ") + bam_path; delete p; p = nullptr; throw Error(m); }
@@ -563,11 +565,17 @@ void BamSink::add(std::vector<std::string> &records, std::vector<std::vector<Bam
     for (size_t j = 0; j < comp.size(); ++j) { if (std::fwrite(comp[j].data(), 1, comp[j].size(), p->f) != comp[j].size()) p->failed = true; p->bytes += comp[j].size(); }
     records.clear(); recs.clear();
 }
-void BamSink::finish(BamStats *stats)
+void BamSink::finish(BamStats *stats, BamFile *keep)
 {
+    if (keep && !p->sort) throw Error("internal: only a sorted BAM is kept in memory");
     if (p->sort) {
-        sort_records(p->d, false);
-        write_bam(p->d, p->path.c_str(), p->index, p->threads, stats, p->level);
+        sort_records(p->d, p->by_name);
+        write_bam(p->d, p->path.c_str(), p->index, p->threads, stats, p->level, keep != nullptr);
+        if (keep) {                                             // the file's records, in file order, for the step that would read it back
+            *keep = BamFile();
+            keep->sort_order = p->by_name ? "queryname" : "coordinate";
+            keep->text.swap(p->d.text); keep->refs.swap(p->d.refs); keep->enc.swap(p->d.enc); keep->recs.swap(p->d.recs);
+        }
         return;
     }
     static const unsigned char eof_block[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};

@@ -22,15 +22,18 @@ void bam_rec_end(std::string &o, BamRec &r);                                    
 // BAM records that were never SAM text (ps_map_to_bam: straight from the alignment records in memory): parts arrive in input
 // order.  Unsorted output: a part is cut into BGZF blocks, compressed on `threads` threads and appended to the file at once, so the
 // compression of one piece of the input runs while the next is searched.  Coordinate-sorted output (+ .bai): the parts are kept and
-// sorted, compressed and written by finish().
+// sorted, compressed and written by finish().  sort_by_name: the same with the names ordered as `samtools sort -n` orders them
+// (ps_bam_sort's rule) under @HD SO:queryname.  finish(.., keep): the records of the sorted file stay in memory, in file order, as
+// load_records() would return them (ps_map_route hands them to the lift instead of reading the file back).
+struct BamFile;
 class BamSink {
 public:
     BamSink(const std::string &header_text, const std::vector<std::pair<std::string, uint32_t>> &refs, const char *bam_path,
-            bool sort_by_coordinate, bool write_index, int threads, int level);
+            bool sort_by_coordinate, bool write_index, int threads, int level, bool sort_by_name = false);
     ~BamSink();
     // buffers of records in input order (one per encoding thread); recs[k][i].off/len index into records[k]; both are consumed
     void add(std::vector<std::string> &records, std::vector<std::vector<BamRec>> &recs, uint64_t n_in);
-    void finish(BamStats *stats);
+    void finish(BamStats *stats, BamFile *keep = nullptr);
 private:
     struct Impl; Impl *p;
 };

@@ -16,6 +16,7 @@
 #include "../../include/parasuite_hip.h"
 #include "ps_pipeline.h"
 #include "ps_bam.h"
+#include "ps_host.h"
 
 using namespace ps;
 
@@ -410,10 +411,19 @@ int ps_batch_kstats(ps_batch *b, int which, ps_kstats *o)
 static const char *const PS_PG_LINE = "@PG\tID:parasuite-hip\tPN:parasuite-hip\tVN:0.1";
 namespace {
 struct ProfileSink { int min_mapq = 0, max_len = 0; std::string prefix; };    // ps_map_profiled: the first pass also counts its error profile
-struct BamOut { int min_mapq = 0; bool sort = false, index = false; int level = 1; BamStats *stats = nullptr; };   // ps_map_to_bam: out_sam names a BAM file
+struct BamOut { int min_mapq = 0; bool sort = false, index = false; int level = 1; BamStats *stats = nullptr;     // ps_map_to_bam: out_sam names a BAM file
+                bool by_name = false; BamFile *keep = nullptr; };                                                   // ps_map_route: sorted by read name; the sorted records also stay in memory
+// ps_map_route: what outlives one pass over a reference -- a context per device with its index, jump table and lanes of work
+struct Resident { std::vector<ps_ctx *> xs; bool loaded = false; int n_index_loads = 0; };
+// ps_map_route: a pass that is one of several.  res: the contexts are taken from there (made and loaded by the first pass that finds none) and
+// left open; reads: the input, already parsed, instead of the file (consumed); after_piece: called by the writer for every piece in input
+// order once its records are built, before the piece is let go; lanes_from: the lanes of work (streams, search workspace) of these contexts,
+// which search no more, move to this pass's contexts on the same devices
+struct PassIO { Resident *res = nullptr; std::vector<ReadSet> *reads = nullptr; std::function<void(Batch &)> after_piece; Resident *lanes_from = nullptr;
+                int64_t n_reads = 0; double s_parse = 0, s_index = 0; };
 }
 static int map_core(int threads, const char *mm, const char *error_profile, const char *indel_profile,
-                    const char *ref_fa, const char *fastq, const char *out_sam, const ProfileSink *sink, const BamOut *bam = nullptr)
+                    const char *ref_fa, const char *fastq, const char *out_sam, const ProfileSink *sink, const BamOut *bam = nullptr, PassIO *io = nullptr)
 {
     PS_TRY
         const bool verbose = std::getenv("PS_VERBOSE") != nullptr;
@@ -452,7 +462,7 @@ static int map_core(int threads, const char *mm, const char *error_profile, cons
         size_t chunk_bytes = (size_t)1 << 30, first_bytes = 0, hungry_min = (size_t)128 << 20;
         if (const char *e = std::getenv("PS_CHUNK_MB")) { chunk_bytes = (size_t)std::max(1, std::atoi(e)) << 20; hungry_min = chunk_bytes; }   // stated: taken as it is
         else {
-            FILE *f = std::fopen(fastq, "rb");
+            FILE *f = io && io->reads ? nullptr : std::fopen(fastq, "rb");
             if (f) {
                 if (fseeko(f, 0, SEEK_END) == 0) {
                     const off_t sz = ftello(f);
@@ -474,21 +484,32 @@ static int map_core(int threads, const char *mm, const char *error_profile, cons
         parsed.cap = (size_t)std::max(2, n_workers);
         // the contexts (stream, options) exist before any index is loaded: the parser stage needs the cost model to bin
         // and pack the reads, not the index
+        Resident *const res = io ? io->res : nullptr;      // contexts that outlive this pass: closed by their owner, never here
+        const bool preloaded = res && res->loaded;
         std::vector<ps_ctx *> xs((size_t)G, nullptr);
-        auto close_all = [&]() { for (ps_ctx *c : xs) if (c) ps_ctx_close(c); };
+        if (res && !res->xs.empty()) { if (res->xs.size() != (size_t)G) return fail("internal: the resident contexts do not match the devices"); xs = res->xs; }
+        auto close_all = [&]() { if (res) { res->xs = xs; return; } for (ps_ctx *c : xs) if (c) ps_ctx_close(c); };
         for (int g = 0; g < G; ++g) {
-            xs[g] = new_ctx(devs[g], false);               // the device side is attached by the device's first worker, beside the parser
+            if (!xs[g]) xs[g] = new_ctx(devs[g], false);   // the device side is attached by the device's first worker, beside the parser
             if (error_profile && error_profile[0] ? ps_ctx_set_profile(xs[g], error_profile, indel_profile, mm)
                                                    : ps_ctx_set_stock(xs[g], mm && mm[0] ? mm : "0.04")) { const std::string m = g_err; close_all(); return fail(m); }
             xs[g]->c.host_threads = nthr;
             xs[g]->c.n_work = dev_workers[g];
         }
+        if (res) res->xs = xs;
+        if (io && io->lanes_from && io->lanes_from->xs.size() == (size_t)G)
+            for (int g = 0; g < G; ++g) {
+                Ctx &from = io->lanes_from->xs[g]->c, &to = xs[g]->c;
+                if (from.device != to.device) continue;
+                std::lock_guard<std::mutex> l1(from.work_mu), l2(to.work_mu);
+                for (int w = 0; w < (int)Ctx::N_WORK; ++w) if (from.work[w] && !to.work[w]) to.work[w] = std::move(from.work[w]);
+            }
         std::mutex mu; std::condition_variable cv;       // guards: failure, the tie-break chain, the finished pieces, index hand-out
         bool failed = false; std::string msg;
         int64_t next_select = 0, write_next = 0; uint64_t draws = 0;
         std::map<int64_t, std::unique_ptr<Batch>> done; int workers_left = n_workers;
         const size_t done_cap = (size_t)n_workers + 2;   // finished pieces that may wait for the writer
-        std::vector<int> index_state((size_t)G, 0);      // 0 not there, 1 resident
+        std::vector<int> index_state((size_t)G, preloaded ? 1 : 0);      // 0 not there, 1 resident
         std::vector<int> attached((size_t)G, 0);         // the device side of the context exists (made by the device's first worker)
         auto fail_all = [&](const std::string &m) { { std::lock_guard<std::mutex> l(mu); if (!failed) { failed = true; msg = m; } } cv.notify_all(); parsed.abort(); };
         double t_parse = 0, t_write = 0, t_release = 0, t_index = 0, t_index_all = 0, t_profile = 0; std::vector<double> t_gpu((size_t)n_workers, 0.0);
@@ -501,6 +522,10 @@ static int map_core(int threads, const char *mm, const char *error_profile, cons
                 int pthr = nthr;                                       // all of them: the GPU waits for the first piece, and sharing the cores with the writer later cost nothing measurable (2.78-2.90 -> 2.67-2.80 s per 10 M reads against half of them)
                 if (const char *e = std::getenv("PS_PARSE_THREADS")) pthr = std::max(1, std::atoi(e));
                 const std::function<bool()> hungry = [&]() { return parsed.hungry(); };
+                if (io && io->reads) {                                 // parsed by an earlier pass: binned and packed again under this pass's cost model
+                    for (ReadSet &rs : *io->reads) { if (rs.n == 0) continue; Piece p; p.seq = seq++; p.b = batch_prepare(&xs[0]->c, std::move(rs), pthr); parsed.push(std::move(p)); }
+                    io->reads->clear();
+                } else
                 load_reads_chunked(fastq, pthr, chunk_bytes, [&](ReadSet &&rs) {
                     Piece p; p.seq = seq++; p.b = batch_prepare(&xs[0]->c, std::move(rs), pthr);     // host only
                     parsed.push(std::move(p));
@@ -532,7 +557,7 @@ static int map_core(int threads, const char *mm, const char *error_profile, cons
                         if (!bsink) {
                             std::vector<std::pair<std::string, uint32_t>> refs;
                             for (const Contig &ct : b->ctx->ix.ref.contigs) refs.emplace_back(ct.name, (uint32_t)ct.len);
-                            bsink.reset(new BamSink(sam_header(b->ctx->ix.ref, PS_PG_LINE), refs, out_sam, bam->sort, bam->index, nthr, bam->level));
+                            bsink.reset(new BamSink(sam_header(b->ctx->ix.ref, PS_PG_LINE), refs, out_sam, bam->sort, bam->index, nthr, bam->level, bam->by_name));
                         }
                         std::vector<std::string> enc; std::vector<std::vector<BamRec>> recs;
                         batch_bam_records(*b, bam->min_mapq, nthr, enc, recs);
@@ -547,6 +572,7 @@ static int map_core(int threads, const char *mm, const char *error_profile, cons
                         accum->add(pr);
                         t_profile += std::chrono::duration<double>(std::chrono::steady_clock::now() - tp).count();
                     }
+                    if (io && io->after_piece) io->after_piece(*b);
                     first = false;
                     { std::lock_guard<std::mutex> l(mu); ++write_next; }
                     cv.notify_all();
@@ -560,7 +586,7 @@ static int map_core(int threads, const char *mm, const char *error_profile, cons
                     if (bam) {
                         std::vector<std::pair<std::string, uint32_t>> refs;
                         for (const Contig &ct : xs[0]->c.ix.ref.contigs) refs.emplace_back(ct.name, (uint32_t)ct.len);
-                        bsink.reset(new BamSink(h, refs, out_sam, bam->sort, bam->index, nthr, bam->level));
+                        bsink.reset(new BamSink(h, refs, out_sam, bam->sort, bam->index, nthr, bam->level, bam->by_name));
                     }
                     FILE *f = bam ? nullptr : std::fopen(out_sam, "wb");
                     if (bam) { /* the header-only BAM is written by finish() below */ } else {
@@ -569,7 +595,7 @@ static int map_core(int threads, const char *mm, const char *error_profile, cons
                     if (std::fclose(f) != 0 || !ok) throw Error(std::string("short write on ") + out_sam);
                     }
                 }
-                if (bsink) { const auto t0 = std::chrono::steady_clock::now(); bsink->finish(bam->stats); bsink.reset(); t_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
+                if (bsink) { const auto t0 = std::chrono::steady_clock::now(); bsink->finish(bam->stats, bam->keep); bsink.reset(); t_write += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
                 if (sink) {
                     ProfileCounts pc;
                     if (accum) accum->finish(pc);
@@ -593,8 +619,9 @@ static int map_core(int threads, const char *mm, const char *error_profile, cons
                 // several workers on one device it also keeps a worker's allocation from waiting for another worker's running kernel.
                 std::thread reserve([&c, j]() { try { reserve_search_workspace(&c, j); } catch (...) {} });
                 struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } reserve_joiner{reserve};
-                if (j == 0) {                                          // this device's index: from the files, or from the first device
-                    if (g == 0) { index_load(ref_fa, c.ix, c.stream); t_index = since(); }
+                if (j == 0 && preloaded) { /* resident since an earlier pass of the call */ }
+                else if (j == 0) {                                     // this device's index: from the files, or from the first device
+                    if (g == 0) { index_load(ref_fa, c.ix, c.stream); t_index = since(); if (res) ++res->n_index_loads; }
                     else {
                         { std::unique_lock<std::mutex> l(mu); cv.wait(l, [&] { return failed || index_state[0] == 1; }); if (failed) return; }
                         index_clone(xs[0]->c.ix, xs[0]->c.device, c.ix, c.device, c.stream);
@@ -662,14 +689,16 @@ static int map_core(int threads, const char *mm, const char *error_profile, cons
         // reads host memory only; the error-profile pass keeps its device (ProfileAccum counts on it until the writer is done).
         std::thread early_release;
         double t_release_dev = 0;
-        if (!sink) early_release = std::thread([&]() { for (ps_ctx *c : xs) if (c) { try { ctx_release_device(c->c); } catch (...) {} } t_release_dev = since(); });
+        if (!sink && !res) early_release = std::thread([&]() { for (ps_ctx *c : xs) if (c) { try { ctx_release_device(c->c); } catch (...) {} } t_release_dev = since(); });
         parser.join(); writer.join();
         const double t_written = since();
         if (early_release.joinable()) early_release.join();
         done.clear();
         // what is left of the contexts (streams, events, the mapped packed text: 0.05 s) goes the way of the written pieces when the
         // device memory has been given back already; a failed call and the error-profile pass close them here
-        if (!failed && !sink) { std::vector<ps_ctx *> gone(xs); for (auto &c : xs) c = nullptr; Trash::trash().add(std::thread([gone]() { for (ps_ctx *c : gone) if (c) ps_ctx_close(c); })); }
+        if (io) { io->n_reads = n_reads; io->s_parse = t_parse; io->s_index = t_index_all; }
+        if (res) res->loaded = res->loaded || !failed;
+        else if (!failed && !sink) { std::vector<ps_ctx *> gone(xs); for (auto &c : xs) c = nullptr; Trash::trash().add(std::thread([gone]() { for (ps_ctx *c : gone) if (c) ps_ctx_close(c); })); }
         else close_all();
         const double t_closed = since();
         if (failed) return fail(msg);
@@ -714,6 +743,182 @@ int ps_map_to_bam(int threads, const char *mm, const char *error_profile, const 
     const int rc = map_core(threads, mm, error_profile, indel_profile, ref_fa, fastq, out_bam, nullptr, &bo);
     if (rc == 0 && st) { st->n_in = s.n_in; st->n_out = s.n_out; st->bam_bytes = s.bam_bytes; }
     return rc;
+}
+
+// ---- the whole `map` mode (Main.java:249-420) in one call ---------------------------------------------------------------------
+// The passes are map_core's, over contexts that stay open from pass to pass: the genome's index is loaded once and keeps its lanes of
+// work; the reads are parsed once and kept (up to PS_ROUTE_KEEP_MB of host memory) for the profile pass; the first pass's profile is
+// counted from its records in memory (ps_map_profiled's path); the weak reads of the last genomic pass go to the transcript pass as a
+// ReadSet, not as FASTQ text; the sorted records of the last genomic pass and of the transcript pass stay in memory for the lift.
+namespace {
+struct RouteFiles {                    // outputs are written under a temporary name and renamed when their step is done; a failed call removes both kinds
+    std::vector<std::string> tmp, made;
+    static std::string tmp_name(const std::string &name) { return name + ".route-tmp"; }
+    std::string open(const std::string &name) { const std::string t = tmp_name(name); tmp.push_back(t); return t; }
+    void publish(const std::string &t, const std::string &name)
+    {
+        if (std::rename(t.c_str(), name.c_str()) != 0) throw Error("cannot rename " + t + " to " + name);
+        made.push_back(name);
+    }
+    void drop() { for (const std::string &f : tmp) std::remove(f.c_str()); for (const std::string &f : made) std::remove(f.c_str()); }
+};
+size_t readset_bytes(const ReadSet &rs)
+{
+    return rs.len.size() * 4 + rs.off.size() * 8 + rs.name_off.size() * 8 + rs.seq.size() + rs.qual.size() + rs.names.size();
+}
+// ExtractWeakMappingReads on a located piece: the reads whose record has MAPQ < threshold, as a second parse of their FASTQ text would return
+// them (the read as it was sequenced is what the ReadSet holds; the parser takes one more trailing /1 or /2 off the name)
+void gather_weak(const Batch &b, int threshold, ReadSet &w, uint64_t &n_weak)
+{
+    const ReadSet &rs = b.rs;
+    if (w.off.empty()) { w.off.push_back(0); w.name_off.push_back(0); }
+    for (int64_t g = 0; g < rs.n; ++g) {
+        Hit h; b.hit_of(g, h);
+        if ((h.type ? h.mapq : 0) >= threshold) continue;
+        size_t nl; const char *nm = rs.name(g, nl);
+        if (rs.len[g] == 0) throw Error("extract: record " + std::string(nm, nl) + " has MAPQ below " + std::to_string(threshold) + " and no SEQ ('*'): it cannot be mapped again");
+        if (!rs.has_qual) throw Error("extract: record " + std::string(nm, nl) + " has MAPQ below " + std::to_string(threshold) + " and no QUAL ('*'): it cannot be written as FASTQ");
+        if (nl > 2 && nm[nl - 2] == '/' && (nm[nl - 1] == '1' || nm[nl - 1] == '2')) nl -= 2;
+        w.names.insert(w.names.end(), nm, nm + nl); w.name_off.push_back((int64_t)w.names.size());
+        w.seq.insert(w.seq.end(), rs.seq.data() + rs.off[g], rs.seq.data() + rs.off[g + 1]);
+        w.qual.insert(w.qual.end(), rs.qual.data() + rs.off[g], rs.qual.data() + rs.off[g + 1]);
+        w.len.push_back(rs.len[g]); w.off.push_back((int64_t)w.seq.size());
+        ++w.n; ++n_weak;
+    }
+    w.has_qual = true;
+}
+}
+
+int ps_map_route(const ps_route_opts *o, ps_route_stats *stats_out)
+{
+    auto has = [](const char *s) { return s && s[0]; };
+    if (!o) return fail("ps_map_route: no options");
+    if (!has(o->reads_fq)) return fail("ps_map_route: the reads file (-q) is required");
+    if (!has(o->ref_fa)) return fail("ps_map_route: the reference (-r) is required");
+    if (!has(o->out_prefix)) return fail("ps_map_route: the output prefix (-o) is required");
+    const bool refine = o->refine != 0, with_t = has(o->transcripts_fa), given = has(o->error_profile);
+    if (given && !refine) return fail("ps_map_route: an error profile without refine: nothing to map");
+    if (has(o->indel_profile) && !given) return fail("ps_map_route: an indel profile without an error profile");
+    const int threads = o->threads > 0 ? o->threads : 1, max_len = o->max_read_len > 0 ? o->max_read_len : 101;
+    const int gm = o->mapq_genomic > 0 ? o->mapq_genomic : 10, tm = o->mapq_transcript > 0 ? o->mapq_transcript : 1;
+    const char *bwa_mm = has(o->bwa_mm) ? o->bwa_mm : "2", *para_mm = has(o->parasuite_mm) ? o->parasuite_mm : "-1";
+    if (max_len > 4096) return fail("ps_map_route: maximum read length out of range");
+    const std::string P = o->out_prefix;
+    const bool first_pass = !given;
+    const std::string f_bwa = P + ".BWA-genomic.bam", f_para = P + ".PARAsuite-genomic.bam", f_comb = P + ".combined.bam";
+    const std::string f_tr = P + (refine ? ".PARAsuite-transcript.bam" : ".BWA-transcript.bam");
+    const std::string f_ep = f_bwa + ".errorprofile", f_ip = f_bwa + ".indelprofile";
+    {
+        // every name the call writes: the outputs, and the temporary name each is written under (RouteFiles::open)
+        std::vector<std::string> outs;
+        auto bam = [&](const std::string &f, bool index) { outs.push_back(f); outs.push_back(RouteFiles::tmp_name(f)); if (index) { outs.push_back(f + ".bai"); outs.push_back(RouteFiles::tmp_name(f) + ".bai"); } };
+        if (first_pass) {
+            bam(f_bwa, true);
+            if (refine) for (const char *x : {".errorprofile", ".indelprofile"}) { outs.push_back(f_bwa + x); outs.push_back(RouteFiles::tmp_name(f_bwa + ".profile") + x); }
+        }
+        if (refine) bam(f_para, true);
+        if (with_t) { bam(f_tr, false); bam(f_comb, true); }
+        const char *ins[] = {o->reads_fq, o->ref_fa, o->transcripts_fa, o->error_profile, o->indel_profile};
+        for (const std::string &f : outs) for (const char *in : ins)
+            if (has(in) && same_file(f.c_str(), in)) return fail("ps_map_route: the output " + f + " would overwrite the input " + in);
+    }
+    { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return fail("ps_map_route: no HIP device available: parasuite-hip has no CPU path"); }
+
+    using clk = std::chrono::steady_clock;
+    const auto t_begin = clk::now();
+    auto secs = [](clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); };
+    ps_route_stats st; std::memset(&st, 0, sizeof st);
+    RouteFiles files; Resident genome, transcripts;
+    std::vector<ReadSet> kept, weak; size_t kept_bytes = 0; bool kept_all = true;
+    size_t keep_bound = (size_t)8192 << 20;
+    if (const char *e = std::getenv("PS_ROUTE_KEEP_MB")) keep_bound = (size_t)std::max(0, std::atoi(e)) << 20;
+    uint64_t n_weak = 0;
+    BamFile G, T;
+    std::string step = "first pass";
+    bool printed = false;                  // the failing pass has put its message on stderr: ps_last_error() gets the step in front, stderr no second line
+    auto close_ctxs = [&]() { for (Resident *r : {&transcripts, &genome}) { for (ps_ctx *c : r->xs) if (c) ps_ctx_close(c); r->xs.clear(); } };
+    int bam_level = 1;
+    if (const char *e = std::getenv("PS_BAM_LEVEL")) bam_level = std::atoi(e);
+    // one pass: a sorted BAM (+ index, or by name) under its temporary name, published when the pass is done
+    auto run_pass = [&](const char *mm, const char *ep, const char *ip, const char *ref, const std::string &out, int min_mapq, bool by_name,
+                        BamFile *keep, const ProfileSink *prof, PassIO &io, ps_bam_stats &bs_out) {
+        BamStats bs; BamOut bo; bo.min_mapq = min_mapq; bo.sort = !by_name; bo.index = !by_name; bo.by_name = by_name; bo.keep = keep; bo.stats = &bs; bo.level = bam_level;
+        const std::string t = files.open(out); if (!by_name) files.tmp.push_back(t + ".bai");
+        if (map_core(threads, mm, ep, ip, ref, o->reads_fq, t.c_str(), prof, &bo, &io)) { printed = true; throw Error(g_err); }
+        files.publish(t, out); if (!by_name) files.publish(t + ".bai", out + ".bai");
+        bs_out.n_in = bs.n_in; bs_out.n_out = bs.n_out; bs_out.bam_bytes = bs.bam_bytes;
+    };
+    try {
+        const bool weak_after_first = with_t && !refine;
+        std::string ep = given ? o->error_profile : "", ip = has(o->indel_profile) ? o->indel_profile : "";
+        if (first_pass) {
+            const auto t0 = clk::now();
+            PassIO io; io.res = &genome;
+            io.after_piece = [&](Batch &b) {
+                if (weak_after_first) { weak.emplace_back(); gather_weak(b, gm, weak.back(), n_weak); return; }
+                if (!refine || !kept_all) return;
+                const size_t bytes = readset_bytes(b.rs);                  // the parsed piece stays for the profile pass, within the bound
+                if (kept_bytes + bytes > keep_bound) { kept_all = false; kept.clear(); kept.shrink_to_fit(); kept_bytes = 0; return; }
+                kept_bytes += bytes; kept.push_back(std::move(b.rs));
+            };
+            ProfileSink prof; prof.min_mapq = gm; prof.max_len = max_len;
+            if (refine) { prof.prefix = files.open(f_bwa + ".profile"); files.tmp.push_back(prof.prefix + ".errorprofile"); files.tmp.push_back(prof.prefix + ".indelprofile"); }
+            run_pass(bwa_mm, nullptr, nullptr, o->ref_fa, f_bwa, gm, false, weak_after_first ? &G : nullptr, refine ? &prof : nullptr, io, st.first);
+            st.n_reads = (uint64_t)io.n_reads; st.s_parse = io.s_parse; st.s_index_genome = io.s_index; st.n_fastq_parses = 1;
+            st.s_first = secs(t0);
+            if (refine) {
+                step = "profile";
+                const auto t1 = clk::now();
+                files.publish(prof.prefix + ".errorprofile", f_ep); files.publish(prof.prefix + ".indelprofile", f_ip);
+                ep = f_ep; ip = f_ip;
+                st.s_profile = secs(t1);
+            }
+        }
+        if (refine) {
+            step = "refine pass";
+            const auto t0 = clk::now();
+            PassIO io; io.res = &genome;
+            const bool from_memory = first_pass && kept_all;
+            if (from_memory) io.reads = &kept; else ++st.n_fastq_parses;
+            if (with_t) io.after_piece = [&](Batch &b) { weak.emplace_back(); gather_weak(b, gm, weak.back(), n_weak); };
+            run_pass(para_mm, ep.c_str(), ip.empty() ? nullptr : ip.c_str(), o->ref_fa, f_para, gm, false, with_t ? &G : nullptr, nullptr, io, st.refine);
+            if (!first_pass) { st.n_reads = (uint64_t)io.n_reads; st.s_parse = io.s_parse; st.s_index_genome = io.s_index; }
+            st.s_refine = secs(t0);
+        }
+        kept.clear();
+        if (with_t) {
+            step = "transcript pass";
+            const auto t0 = clk::now();
+            st.extract.n_records = st.n_reads; st.extract.n_weak = n_weak; st.extract.n_kept = st.n_reads - n_weak;
+            PassIO io; io.res = &transcripts; io.reads = &weak; io.lanes_from = &genome;
+            run_pass(refine ? para_mm : bwa_mm, refine ? ep.c_str() : nullptr, refine && !ip.empty() ? ip.c_str() : nullptr, o->transcripts_fa, f_tr, tm, true, &T, nullptr, io, st.transcript);
+            st.s_index_transcripts = io.s_index; st.s_transcript = secs(t0);
+            step = "combine";
+            const auto t1 = clk::now();
+            const int dev = genome.xs[0]->c.device;                    // the first device of the passes
+            const std::string t = files.open(f_comb); files.tmp.push_back(t + ".bai");
+            combine_records(G, T, f_tr.c_str(), t.c_str(), true, true, threads, dev, &st.combine);
+            files.publish(t, f_comb); files.publish(t + ".bai", f_comb + ".bai");
+            st.s_combine = secs(t1);
+        }
+        step = "closing";
+        st.n_index_loads_genome = (uint32_t)genome.n_index_loads; st.n_index_loads_transcripts = (uint32_t)transcripts.n_index_loads;
+        close_ctxs();
+    } catch (const std::exception &e) {
+        const std::string m = e.what();
+        try { close_ctxs(); } catch (...) {}
+        files.drop();
+        if (printed) { g_err = "ps_map_route: " + step + ": " + m; return 1; }
+        return fail("ps_map_route: " + step + ": " + m);
+    } catch (...) { try { close_ctxs(); } catch (...) {} files.drop(); return fail("ps_map_route: " + step + ": unknown error"); }
+    st.s_total = secs(t_begin);
+    if (stats_out) *stats_out = st;
+    if (std::getenv("PS_VERBOSE"))
+        std::fprintf(stderr, "[parasuite-hip] ps_map_route: %llu reads, %.3f s: parse %.3f s (the file was parsed %u time(s)), genome index resident after %.3f s (%u load(s)), first pass %.3f s, "
+                             "profile files %.3f s, refine pass %.3f s, %llu weak reads, transcript index after %.3f s (%u load(s)), transcript pass %.3f s, combine %.3f s\n",
+                     (unsigned long long)st.n_reads, st.s_total, st.s_parse, st.n_fastq_parses, st.s_index_genome, st.n_index_loads_genome, st.s_first, st.s_profile, st.s_refine,
+                     (unsigned long long)st.extract.n_weak, st.s_index_transcripts, st.n_index_loads_transcripts, st.s_transcript, st.s_combine);
+    return 0;
 }
 
 // page-locked host buffers the library keeps between calls (ps_pipeline.h, PinBuf): given back to the system

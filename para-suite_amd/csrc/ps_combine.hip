@@ -221,14 +221,11 @@ void combine_run(const char *genome_path, const char *transcript_path, const cha
                  int threads, int device, ps_combine_stats *stats)
 {
     using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
     if (!genome_path || !transcript_path || !out_bam || !out_bam[0]) throw Error("ps_combine_genome_transcript: genomic mapping, transcript mapping and output file are required");
     if (same_file(out_bam, genome_path) || same_file(out_bam, transcript_path)) throw Error("ps_combine_genome_transcript: the output may not be one of the inputs");
     if (write_index && !sort_by_coordinate) throw Error("a .bai index needs coordinate-sorted output");
-    threads = threads < 1 ? 1 : (threads > 64 ? 64 : threads);
-    require_device(device);
-    CbTimes tm; ps_combine_stats st{};
-    auto t0 = clk::now();
+    require_device(device);                                                // before the files are read
+    const auto t0 = clk::now();
     BamFile G, T;
     {
         std::string err;
@@ -237,12 +234,28 @@ void combine_run(const char *genome_path, const char *transcript_path, const cha
         other.join();
         if (!err.empty()) throw Error(err);
     }
+    combine_records(G, T, transcript_path, out_bam, sort_by_coordinate, write_index, threads, device, stats,
+                    std::chrono::duration<double, std::milli>(clk::now() - t0).count());
+}
+
+// the same on records in memory (both are consumed): the files' loader above, or ps_map_route's passes, which hand over what they
+// have just written.  transcript_path: what the error messages call the transcript mapping.  The caller has checked the
+// arguments (combine_run above; ps_map_route always asks for the sorted, indexed form on a device it has used).
+void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const char *out_bam, bool sort_by_coordinate, bool write_index,
+                     int threads, int device, ps_combine_stats *stats, double parse_ms)
+{
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+    threads = threads < 1 ? 1 : (threads > 64 ? 64 : threads);
+    PS_HIP(hipSetDevice(device));
+    CbTimes tm; ps_combine_stats st{};
+    auto t0 = clk::now();
     if (T.sort_order != "queryname")                                       // :85-94 (the Java logs this and exits with status 0)
         throw Error(std::string("ps_combine_genome_transcript: ") + transcript_path + " is not sorted by read name: its header says SO:" +
                     (T.sort_order.empty() ? "(none)" : T.sort_order) + ", SO:queryname is required");
     if (T.n() > (size_t)INT_MAX) throw Error("ps_combine_genome_transcript: more than 2^31 transcript records");
     st.n_genome = G.n(); st.n_transcript = T.n();
-    tm.parse = ms_since(t0);
+    tm.parse = parse_ms;
 
     // placed records (RNAME not '*', :105-107) as flat arrays; exon tables of the transcripts they name, parsed once each
     t0 = clk::now();

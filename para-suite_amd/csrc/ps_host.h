@@ -136,5 +136,8 @@ void pileup_clusters_run(const char *mapping_sam_or_bam, const char *ref_fa, con
 // ---- transcript hits lifted onto the genome and appended to the genomic mapping (ps_combine.hip; CombineGenomeTranscript.combine) ----
 void combine_run(const char *genome_sam_or_bam, const char *transcript_sam_or_bam, const char *out_bam, bool sort_by_coordinate, bool write_index,
                  int threads, int device, ps_combine_stats *stats);
+struct BamFile;
+void combine_records(BamFile &genome, BamFile &transcript, const char *transcript_path, const char *out_bam, bool sort_by_coordinate, bool write_index,
+                     int threads, int device, ps_combine_stats *stats, double parse_ms = 0);   // the same on loaded records, which it consumes
 
 }  // namespace ps

@@ -205,3 +205,32 @@ class CombineGenomeTranscript:
             return capi.ps_combine_genome_transcript(genomeMappingFileName, transcriptMappingFileName, combinedFileName, True, False)
         except capi.PsError as e:
             raise ExternalCallErrorException("CombineGenomeTranscript %s %s: %s" % (genomeMappingFileName, transcriptMappingFileName, e))
+
+
+class Main:
+    """mirror of main.Main's `map` mode (Main.java:249-420) for the BWA and PARA-suite mappers, as ONE library call
+    (`ps_map_route`): `-q readFileName -r referenceFileName -o outputPrefix [-t transcriptFileName] [-p threads] [-l maxReadLength]
+    [--gm ..] [--tm ..] [--refine] [--bwa-mm ..] [--parasuite-mm ..] [--parasuite-ep profileFileName --parasuite-indel
+    indelFileName]`.  Leaves the files Main.java names and returns what the Java calls mappingFileName: <prefix>.combined.bam with
+    a transcript file, else the last genomic mapping.  `stats` holds the call's ps_route_stats afterwards."""
+
+    stats = None
+
+    @staticmethod
+    def mappingFileName(outputPrefix, transcriptFileName=None, refine=False):
+        if transcriptFileName:
+            return outputPrefix + ".combined.bam"
+        return outputPrefix + (".PARAsuite-genomic.bam" if refine else ".BWA-genomic.bam")
+
+    def map(self, readFileName, referenceFileName, outputPrefix, transcriptFileName=None, threads=1, maxReadLength=101,
+            mappingQualityFilterGenomic=10, mappingQualityFilterTranscript=1, refine=False, bwaMismatches="2",
+            parasuiteMismatches="-1", profileFileName=None, indelFileName=None):
+        try:
+            self.stats = capi.ps_map_route(readFileName, referenceFileName, outputPrefix, transcripts_fa=transcriptFileName,
+                                           threads=threads, refine=refine, max_read_len=maxReadLength,
+                                           mapq_genomic=mappingQualityFilterGenomic, mapq_transcript=mappingQualityFilterTranscript,
+                                           bwa_mm=bwaMismatches, parasuite_mm=parasuiteMismatches, error_profile=profileFileName,
+                                           indel_profile=indelFileName)
+        except capi.PsError as e:
+            raise ExternalCallErrorException("map -q %s -r %s -o %s: %s" % (readFileName, referenceFileName, outputPrefix, e))
+        return self.mappingFileName(outputPrefix, transcriptFileName, refine)

@@ -1,0 +1,22 @@
+// ps_map.h -- the whole `map` step behind one call (ps_map.hip): the streaming pass and the route made of several.  Everything
+// here throws ps::Error; the status codes are ps_capi.hip's.
+#pragma once
+#include <thread>
+#include "ps_pipeline.h"
+
+namespace ps {
+
+// Threads that free what a call leaves behind (written pieces, closed contexts): the call does not wait for the last of them.
+// They are joined by the next pass, by ps_release_host_cache and when the process exits.
+void trash_add(std::thread &&t);
+void trash_collect();
+
+static const char *const PS_PG_LINE = "@PG\tID:parasuite-hip\tPN:parasuite-hip\tVN:0.1";
+
+struct MapArgs { int threads; const char *mm, *error_profile, *indel_profile, *ref_fa, *reads; };    // what every mapping call is given
+void map_to_sam(const MapArgs &a, const char *out_sam);
+void map_profiled(const MapArgs &a, const char *out_sam, int min_mapq, int max_read_len, const char *profile_prefix);
+void map_to_bam(const MapArgs &a, const char *out_bam, int min_mapq, bool sort_by_coordinate, bool write_index, BamStats *stats);
+void map_route(const ps_route_opts *o, ps_route_stats *stats_out);
+
+}  // namespace ps

@@ -1,0 +1,600 @@
+// ps_map.hip -- the whole `map` step behind one call: the streaming pass, its outputs, and ps_map_route's sequence of passes.
+//
+// Stages run side by side on pieces of the input (whole records; the file is streamed, a window at a time): a parser thread
+// (parse, bin, 2-bit pack), GPU workers (upload, search, samse stage) and a writer thread that hands every piece, in input order,
+// to the outputs of the pass (SAM text, BAM records, the error profile, the route's own consumers).
+// Devices: the first PARASUITE_GPUS devices (default 1), or the list in PARASUITE_GPU_IDS.  Every device holds ONE copy of
+// the index: the first loads the files, the others receive the three blobs from it over xGMI (hipMemcpyPeerAsync).  Every
+// device has PS_WORKERS_PER_GPU workers (default 1; 2 is allowed, and a device named twice in PARASUITE_GPU_IDS gets two), each
+// with its own stream and workspace.  Two workers on one device were measured SLOWER end to end (4.6 s against 4.2 s for
+// 10 M reads): two persistent search kernels share the CUs evenly instead of one refilling the other's tail, the later
+// stages of one piece starve under the other's kernel, and the second 69 GB workspace costs its allocation.  The piece size
+// follows from the input (ps_map_plan.h); PS_CHUNK_MB states a fixed size.
+// Pieces go to whichever worker is free; the one sequential thing, the tie-break stream, is handed from piece to piece in
+// input order (only the reads whose draw count is data dependent sit on that chain), so the SAM does not depend on the cut,
+// on the number of workers or on the number of devices.  A finished piece gives its device memory back at once and at most
+// a few finished pieces wait for the writer: memory does not grow with the input.
+#include <hip/hip_runtime.h>
+#include <chrono>
+#include <condition_variable>
+#include <functional>
+#include <map>
+#include <mutex>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <fcntl.h>
+#include <sys/stat.h>
+#include <unistd.h>
+#include "ps_map.h"
+#include "ps_map_plan.h"
+
+namespace ps {
+namespace {
+
+typedef std::chrono::steady_clock clk;
+double secs_since(clk::time_point t) { return std::chrono::duration<double>(clk::now() - t).count(); }
+struct Charge { double &to; const clk::time_point t0 = clk::now(); ~Charge() { to += secs_since(t0); } };   // the time of a scope, added to a counter
+
+// Written pieces of ps_map are freed by threads of their own (gigabytes of host memory per piece: 0.18 s for 7.7 M reads), and the call
+// does not wait for the last of them: they are joined by the next call, by ps_release_host_cache and when the process exits.
+struct Trash { std::mutex mu; std::vector<std::thread> th; bool hooked = false; };
+Trash &trash() { static Trash *t = new Trash(); return *t; }       // never destroyed: a thread may still run at exit
+
+// ---- what a pass produces ---------------------------------------------------------------------------------------------------
+// The writer hands every located piece, in input order, to each output of the pass in the order of its list (records, then
+// the profile, then the route's consumer), then lets the piece go.  All calls come from the writer's thread, which also destroys
+// the outputs when it is done or has failed: before the contexts of the pass (and their devices' memory) go.
+struct PassOut {
+    bool holds_device = false;             // works on the device until finish(): the contexts cannot give their memory back before
+    virtual ~PassOut() {}
+    virtual void start() {}                // before the first piece, while the writer has nothing to do
+    virtual void piece(Batch &b) = 0;
+    virtual void empty(const Ctx &) {}     // an input with no reads, instead of any piece(); the context is the first device's, its index resident
+    virtual void finish() {}
+};
+
+struct SamText : PassOut {
+    const char *const path; const int nthr; double &busy; bool first = true; SamScratch scratch;
+    SamText(const char *p, int n, double &t) : path(p), nthr(n), busy(t) {}
+    void start() override { const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644); if (fd >= 0) ::close(fd); }    // an output file that exists is emptied now: giving back 2 GB of cached pages takes 0.3 s
+    void piece(Batch &b) override { Charge c{busy}; batch_write_sam(b, path, first, PS_PG_LINE, nthr, !first, &scratch); first = false; }
+    void empty(const Ctx &c) override            // the header alone, as upstream's samse prints it before its read loop
+    {
+        const std::string h = sam_header(c.ix.ref, PS_PG_LINE);
+        FILE *f = std::fopen(path, "wb");
+        if (!f) throw Error(std::string("cannot write ") + path);
+        const bool ok = std::fwrite(h.data(), 1, h.size(), f) == h.size();
+        if (std::fclose(f) != 0 || !ok) throw Error(std::string("short write on ") + path);
+    }
+};
+
+// ps_map_to_bam: records go out as BAM, no SAM text at all.  by_name, keep (ps_map_route): sorted by read name; the sorted records also stay in memory
+struct BamOut { int min_mapq = 0; bool sort = false, index = false; int level = 1; BamStats *stats = nullptr; bool by_name = false; BamFile *keep = nullptr; };
+struct BamRecords : PassOut {
+    const BamOut o; const char *const path; const int nthr; double &busy; std::unique_ptr<BamSink> sink;
+    BamRecords(const BamOut &bo, const char *p, int n, double &t) : o(bo), path(p), nthr(n), busy(t) {}
+    BamSink &sink_for(const Ctx &c)
+    {
+        if (!sink) {
+            std::vector<std::pair<std::string, uint32_t>> refs;
+            for (const Contig &ct : c.ix.ref.contigs) refs.emplace_back(ct.name, (uint32_t)ct.len);
+            sink.reset(new BamSink(sam_header(c.ix.ref, PS_PG_LINE), refs, path, o.sort, o.index, nthr, o.level, o.by_name));
+        }
+        return *sink;
+    }
+    void piece(Batch &b) override
+    {
+        Charge c{busy};
+        BamSink &s = sink_for(*b.ctx);
+        std::vector<std::string> enc; std::vector<std::vector<BamRec>> recs;
+        batch_bam_records(b, o.min_mapq, nthr, enc, recs);
+        s.add(enc, recs, (uint64_t)b.rs.n);
+    }
+    void empty(const Ctx &c) override { sink_for(c); }       // the header-only BAM is written by finish()
+    void finish() override { Charge c{busy}; sink->finish(o.stats, o.keep); sink.reset(); }
+};
+
+// ps_map_profiled: the pass also counts its error profile -- the same records, straight from memory, into the profile histograms
+struct ProfileOut : PassOut {
+    const int min_mapq, max_len; const std::string prefix; const int nthr; double &busy; std::unique_ptr<ProfileAccum> accum;
+    ProfileOut(int q, int len, const std::string &pre, int n, double &t) : min_mapq(q), max_len(len), prefix(pre), nthr(n), busy(t) { holds_device = true; }
+    void piece(Batch &b) override
+    {
+        Charge c{busy};
+        if (!accum) accum.reset(new ProfileAccum(b.ctx->device, b.ctx->ix, max_len));     // on the device of the first piece, whose index stays resident until the writer is done
+        ProfRecords pr;
+        batch_profile_records(b, min_mapq, nthr, pr);
+        accum->add(pr);
+    }
+    void finish() override
+    {
+        ProfileCounts pc;
+        if (accum) accum->finish(pc);
+        else { pc.max_len = max_len; pc.conv.assign((size_t)max_len * 16, 0); pc.ins.assign((size_t)max_len, 0); pc.del.assign((size_t)max_len, 0); }
+        error_profile_write(pc, prefix);
+        accum.reset();
+    }
+};
+
+struct PieceFn : PassOut {                 // ps_map_route: what the call keeps of a piece for its next pass
+    const std::function<void(Batch &)> fn;
+    explicit PieceFn(std::function<void(Batch &)> f) : fn(std::move(f)) {}
+    void piece(Batch &b) override { fn(b); }
+};
+
+// ---- the pass ---------------------------------------------------------------------------------------------------------------
+// The contexts of a pass, one per device, each with its index, jump table and lanes of work.  A pass owns the set it makes; a
+// set handed in (MapJob::resident) belongs to the caller and outlives the pass.
+struct CtxSet { std::vector<std::unique_ptr<Ctx>> xs; bool loaded = false; int n_index_loads = 0; };
+struct MapJob {
+    MapArgs a;
+    std::vector<ReadSet> *reads = nullptr; // the input, already parsed, instead of the file a.reads (consumed)
+    bool bam_out = false;                  // the piece plan's: the records are compressed, which wants early pieces
+    std::vector<std::unique_ptr<PassOut>> outs;
+    CtxSet *resident = nullptr;            // ps_map_route: the contexts are taken from there (made and loaded by the first pass that finds none) and left open
+    CtxSet *lanes_from = nullptr;          // the lanes of work (streams, search workspace) of these contexts, which search no more, move to this pass's contexts on the same devices
+    int64_t n_reads = 0; double s_parse = 0, s_index = 0, s_write = 0, s_profile = 0;      // results
+};
+
+struct Piece { int64_t seq = 0; std::unique_ptr<Batch> b; };
+
+struct Pass {
+    explicit Pass(MapJob &j);              // plans, makes the contexts and sets their options: no thread yet, no device call
+    void run();
+    MapJob &job;
+    const bool verbose = std::getenv("PS_VERBOSE") != nullptr;
+    const clk::time_point t_begin = clk::now();
+    const int nthr;
+    DevicePlan dev; PiecePlan cut; int G = 0, n_workers = 0;
+    // What becomes of the contexts at the end, one rule: resident ones are left open; a clean pass with no output that holds the
+    // device releases the devices' memory while the writer formats the last piece and closes the rest on a trash thread; every
+    // other pass closes them on the spot.
+    CtxSet own, &set; const bool preloaded; bool holds_device = false;
+    Ctx &ctx(int g) { return *set.xs[(size_t)g]; }
+    Chan<Piece> parsed;
+    std::mutex mu; std::condition_variable cv;       // guards: failure, the tie-break chain, the finished pieces, index hand-out
+    struct Guarded {
+        bool failed = false; std::string msg;
+        int64_t next_select = 0; uint64_t draws = 0;                 // the tie-break chain
+        std::map<int64_t, std::unique_ptr<Batch>> done; int64_t write_next = 0; int workers_left = 0;    // finished pieces waiting for the writer
+        std::vector<int> index_state;      // per device: 0 not there, 1 resident
+        std::vector<int> attached;         // per device: the device side of the context exists (made by the device's first worker)
+        int64_t n_reads = 0, n_pieces = 0;
+    } gd;
+    size_t done_cap = 0;                   // finished pieces that may wait for the writer
+    double t_parse = 0, t_release = 0, t_index = 0, t_index_all = 0; std::vector<double> t_gpu;
+    double since() const { return secs_since(t_begin); }
+    template <class F> bool wait_for(std::unique_lock<std::mutex> &l, F ready) { cv.wait(l, [&] { return gd.failed || ready(); }); return !gd.failed; }
+    void fail_all(const std::string &m) { { std::lock_guard<std::mutex> l(mu); if (!gd.failed) { gd.failed = true; gd.msg = m; } } cv.notify_all(); parsed.abort(); }
+    void parse();
+    void write();
+    void work(int g, int j, int slot);
+};
+
+int env_mb(const char *name) { const char *e = std::getenv(name); return e ? std::max(1, std::atoi(e)) : 0; }
+
+Pass::Pass(MapJob &j) : job(j), nthr(j.a.threads > 0 ? j.a.threads : 1), set(j.resident ? *j.resident : own), preloaded(j.resident && j.resident->loaded)
+{
+    int per_dev = 1, want = 1, have = 1;
+    if (const char *e = std::getenv("PS_WORKERS_PER_GPU")) per_dev = std::atoi(e);
+    if (const char *e = std::getenv("PARASUITE_GPUS")) want = std::max(1, std::atoi(e));
+    const char *ids = std::getenv("PARASUITE_GPU_IDS");
+    if (!ids && want > 1 && (hipGetDeviceCount(&have) != hipSuccess || have < 1)) throw Error("no HIP device available");   // one device: found out (loudly) when the worker attaches it
+    dev = plan_devices(ids, want, per_dev, have, (int)Ctx::N_WORK);
+    G = (int)dev.devs.size(); n_workers = dev.n_workers();
+    struct stat st;
+    const size_t file_bytes = !job.reads && ::stat(job.a.reads, &st) == 0 && st.st_size > 0 ? (size_t)st.st_size : 0;
+    cut = plan_pieces(file_bytes, n_workers, job.bam_out, env_mb("PS_CHUNK_MB"), env_mb("PS_HUNGRY_MIN_MB"), env_mb("PS_FIRST_MB"));
+    parsed.cap = (size_t)std::max(2, n_workers);
+    done_cap = (size_t)n_workers + 2;
+    gd.workers_left = n_workers; gd.index_state.assign((size_t)G, preloaded ? 1 : 0); gd.attached.assign((size_t)G, 0);
+    t_gpu.assign((size_t)n_workers, 0.0);
+    for (const auto &o : job.outs) holds_device = holds_device || o->holds_device;
+    // the contexts (options) exist before any index is loaded: the parser stage needs the cost model to bin and pack the reads,
+    // not the index; the device side is attached by the device's first worker, beside the parser
+    if (set.xs.empty()) set.xs.resize((size_t)G);
+    if (set.xs.size() != (size_t)G) throw Error("internal: the resident contexts do not match the devices");
+    for (int g = 0; g < G; ++g) {
+        if (!set.xs[g]) set.xs[g].reset(new Ctx(dev.devs[g]));
+        ctx(g).set_options(job.a.mm, job.a.error_profile, job.a.indel_profile);
+        ctx(g).host_threads = nthr;
+        ctx(g).n_work = dev.workers[g];
+    }
+    if (job.lanes_from && job.lanes_from->xs.size() == (size_t)G)
+        for (int g = 0; g < G; ++g) {
+            Ctx &from = *job.lanes_from->xs[g], &to = ctx(g);
+            if (from.device != to.device) continue;
+            std::lock_guard<std::mutex> l1(from.work_mu), l2(to.work_mu);
+            for (int w = 0; w < (int)Ctx::N_WORK; ++w) if (from.work[w] && !to.work[w]) to.work[w] = std::move(from.work[w]);
+        }
+}
+
+// the parser (starts at once)
+void Pass::parse()
+{
+    try {
+        int64_t seq = 0;
+        int pthr = nthr;                                       // all of them: the GPU waits for the first piece, and sharing the cores with the writer later cost nothing measurable (2.78-2.90 -> 2.67-2.80 s per 10 M reads against half of them)
+        if (const char *e = std::getenv("PS_PARSE_THREADS")) pthr = std::max(1, std::atoi(e));
+        const std::function<void(ReadSet &&)> hand_over = [&](ReadSet &&rs) {
+            Piece p; p.seq = seq++; p.b = batch_prepare(&ctx(0), std::move(rs), pthr);     // host only
+            parsed.push(std::move(p));
+        };
+        if (job.reads) {                                       // parsed by an earlier pass: binned and packed again under this pass's cost model
+            for (ReadSet &rs : *job.reads) if (rs.n) hand_over(std::move(rs));
+            job.reads->clear();
+        } else {
+            const std::function<bool()> hungry = [&]() { return parsed.hungry(); };
+            load_reads_chunked(job.a.reads, pthr, cut.chunk_bytes, hand_over, cut.first_bytes, &hungry, cut.hungry_min);
+        }
+        t_parse = since();
+    } catch (const std::exception &e) { fail_all(e.what()); }
+    parsed.close();
+}
+
+// the writer: pieces in input order
+void Pass::write()
+{
+    struct Done { std::vector<std::unique_ptr<PassOut>> &outs; ~Done() { outs.clear(); } } done_with{job.outs};
+    try {
+        for (auto &o : job.outs) o->start();
+        bool first = true;
+        for (;;) {
+            std::unique_ptr<Batch> b;
+            {
+                std::unique_lock<std::mutex> l(mu);
+                if (!wait_for(l, [&] { return gd.done.count(gd.write_next) || (gd.workers_left == 0 && gd.done.empty()); })) return;
+                auto it = gd.done.find(gd.write_next);
+                if (it == gd.done.end()) break;                    // all workers finished and nothing is left
+                b = std::move(it->second); gd.done.erase(it);
+            }
+            for (auto &o : job.outs) o->piece(*b);
+            first = false;
+            { std::lock_guard<std::mutex> l(mu); ++gd.write_next; }
+            cv.notify_all();
+            Charge c{t_release};
+            Batch *q = b.release(); trash_add(std::thread([q]() { delete q; }));   // pinned record buffers, the reads (~40 ms per piece): released on a thread of its own, neither on the GPU worker's time nor on the writer's
+        }
+        if (first) {                       // no reads at all
+            { std::unique_lock<std::mutex> l(mu); if (!wait_for(l, [&] { return gd.index_state[0] == 1; })) return; }
+            for (auto &o : job.outs) o->empty(ctx(0));
+        }
+        for (auto &o : job.outs) o->finish();
+    } catch (const std::exception &e) { fail_all(e.what()); }
+}
+
+// a worker: lane j of device g's context
+void Pass::work(int g, int j, int slot)
+{
+    try {
+        Ctx &c = ctx(g);
+        if (j == 0) { c.attach_device(); { std::lock_guard<std::mutex> l(mu); gd.attached[g] = 1; } cv.notify_all(); }
+        else { std::unique_lock<std::mutex> l(mu); if (!wait_for(l, [&] { return gd.attached[g] == 1; })) return; }
+        require_device(c.device);
+        // The worker's big allocations (69 GB of stack slices + the large slots) are made NOW, on a thread of their own, while the
+        // index loads and the parser works on the first piece: a hipMalloc that is handed memory another call or process has
+        // just freed waits for the driver to clear it (seconds for this size, tools/microbench_malloc) -- behind the index load
+        // that wait is hidden, in front of the first search launch (where the first ws_get used to make it) it is not.  With
+        // several workers on one device it also keeps a worker's allocation from waiting for another worker's running kernel.
+        std::thread reserve([&c, j]() { try { reserve_search_workspace(&c, j); } catch (...) {} });
+        struct Joiner { std::thread &t; ~Joiner() { if (t.joinable()) t.join(); } } reserve_joiner{reserve};
+        if (j == 0 && preloaded) { /* resident since an earlier pass of the call */ }
+        else if (j == 0) {                                     // this device's index: from the files, or from the first device
+            if (g == 0) { index_load(job.a.ref_fa, c.ix, c.stream); t_index = since(); ++set.n_index_loads; }
+            else {
+                { std::unique_lock<std::mutex> l(mu); if (!wait_for(l, [&] { return gd.index_state[0] == 1; })) return; }
+                index_clone(ctx(0).ix, ctx(0).device, c.ix, c.device, c.stream);
+            }
+            { std::lock_guard<std::mutex> l(mu); gd.index_state[g] = 1; t_index_all = since(); }
+            cv.notify_all();
+        } else { std::unique_lock<std::mutex> l(mu); if (!wait_for(l, [&] { return gd.index_state[g] == 1; })) return; }
+        if (reserve.joinable()) reserve.join();
+        Piece p;
+        while (parsed.pop(p)) {
+            { std::lock_guard<std::mutex> l(mu); if (gd.failed) return; gd.n_reads += p.b->rs.n; ++gd.n_pieces; }
+            const auto t0 = clk::now();
+            Batch &b = *p.b;
+            b.ctx = &c;                                        // the piece was packed with the (identical) options of context 0
+            b.work_index = j;
+            batch_upload(b);
+            const double w_up = secs_since(t0);
+            batch_search(b);
+            const double w_search = secs_since(t0) - w_up;
+            {                                                   // the tie-break stream: pieces take their turn in input order
+                std::unique_lock<std::mutex> l(mu);
+                if (!wait_for(l, [&] { return gd.next_select == p.seq; })) return;
+                uint64_t after = 0;
+                batch_select_hard(b, gd.draws, &after);
+                gd.draws = after; ++gd.next_select;
+            }
+            cv.notify_all();
+            batch_select_easy(b, nthr);
+            batch_locate(b);
+            b.release_device();                                // what is left to do (SAM text) reads host memory only
+            if (verbose) {
+                const Timing &t = b.tm;
+                std::fprintf(stderr, "[parasuite-hip]   piece %lld on device %d worker %d: %lld reads; upload %.0f ms, search stage %.0f ms wall (width %.0f backtrack %.0f classify %.0f), select %.0f+%.0f sa2pos %.0f refine %.0f host_post %.0f ms\n",
+                             (long long)p.seq + 1, c.device, j, (long long)b.rs.n, 1e3 * w_up, 1e3 * w_search, t.ms_width, t.ms_backtrack, t.ms_classify, t.ms_sel_hard, t.ms_sel_easy, t.ms_sa2pos, t.ms_refine, t.ms_host_post);
+            }
+            t_gpu[slot] += secs_since(t0);
+            {
+                // at most done_cap finished pieces wait for the writer -- but the piece the writer wants next always gets in
+                std::unique_lock<std::mutex> l(mu);
+                if (!wait_for(l, [&] { return gd.done.size() < done_cap || p.seq == gd.write_next; })) return;
+                gd.done[p.seq] = std::move(p.b);
+            }
+            cv.notify_all();
+        }
+    } catch (const std::exception &e) { fail_all(e.what()); }
+}
+
+void Pass::run()
+{
+    trash_collect();                                           // what an earlier call left to be freed
+    std::thread parser(&Pass::parse, this), writer(&Pass::write, this);
+    bool have_index = true;
+    try {
+        if (!index_files_exist(job.a.ref_fa)) {               // the Java probes <ref>.bwt and indexes first; be lenient if it did not
+            ctx(0).attach_device();
+            Index tmp; index_build(job.a.ref_fa, tmp, ctx(0).stream); index_save(tmp, job.a.ref_fa);
+        }
+    } catch (const std::exception &e) { have_index = false; fail_all(e.what()); }
+    std::vector<std::thread> workers;
+    auto worker = [this](int g, int j, int slot) { work(g, j, slot); { std::lock_guard<std::mutex> l(mu); --gd.workers_left; } cv.notify_all(); };
+    if (have_index) { int slot = 0; for (int g = 0; g < G; ++g) for (int j = 0; j < dev.workers[g]; ++j) workers.emplace_back(worker, g, j, slot++); }
+    else { std::lock_guard<std::mutex> l(mu); gd.workers_left = 0; }
+    for (auto &t : workers) t.join();
+    const double t_workers = since();
+    cv.notify_all();
+    parsed.abort();                                            // a parser still waiting to hand over a piece must not wait forever
+    // The devices' memory (index, 69-GB workspaces: ~0.1 s of hipFree) goes back while the writer formats the last piece, which
+    // reads host memory only; a pass with an output that holds the device (ProfileAccum counts on it until the writer is done) keeps it.
+    const bool early = !holds_device && !job.resident;
+    std::thread early_release;
+    double t_release_dev = 0;
+    if (early) early_release = std::thread([&]() { for (auto &c : set.xs) if (c) { try { ctx_release_device(*c); } catch (...) {} } t_release_dev = since(); });
+    parser.join(); writer.join();
+    const double t_written = since();
+    if (early_release.joinable()) early_release.join();
+    gd.done.clear();
+    job.n_reads = gd.n_reads; job.s_parse = t_parse; job.s_index = t_index_all;
+    // what is left of the contexts (streams, events, the mapped packed text: 0.05 s) goes the way of the written pieces when the
+    // device memory has been given back already; a failed pass and one that held the device close them here
+    if (job.resident) set.loaded = set.loaded || !gd.failed;
+    else if (early && !gd.failed) trash_add(std::thread([gone = std::move(own.xs)]() mutable { gone.clear(); }));
+    else own.xs.clear();
+    const double t_closed = since();
+    if (gd.failed) throw Error(gd.msg);
+    if (!verbose) return;
+    double busy = 0; for (double v : t_gpu) busy += v;
+    std::fprintf(stderr, "[parasuite-hip] ps_map: %lld reads in %lld piece(s) of <= %.0f MB, %d device(s) x %d worker(s), %.3f s; index resident after %.3f s (all devices %.3f s), "
+                         "parser done after %.3f s, GPU stages busy %.3f s (summed over workers) and done after %.3f s, SAM writer busy %.3f s (+ %.3f s handing pieces back, %.3f s error profile) and done after %.3f s, device memory released after %.3f s, contexts closed after %.3f s\n", (long long)gd.n_reads, (long long)gd.n_pieces, cut.chunk_bytes / 1048576.0,
+                         G, dev.workers[0], since(), t_index, t_index_all, t_parse, busy, t_workers, job.s_write, t_release, job.s_profile, t_written, t_release_dev, t_closed);
+}
+
+}  // namespace
+
+void trash_add(std::thread &&t) { Trash &x = trash(); std::lock_guard<std::mutex> l(x.mu); x.th.push_back(std::move(t)); if (!x.hooked) { x.hooked = true; std::atexit(trash_collect); } }
+void trash_collect() { Trash &x = trash(); std::vector<std::thread> all; { std::lock_guard<std::mutex> l(x.mu); all.swap(x.th); } for (auto &t : all) if (t.joinable()) t.join(); }
+
+void map_to_sam(const MapArgs &a, const char *out_sam)
+{
+    MapJob job; job.a = a;
+    job.outs.emplace_back(new SamText(out_sam, a.threads > 0 ? a.threads : 1, job.s_write));
+    Pass(job).run();
+}
+// ps_map + the error profile of its own alignments (those with MAPQ >= min_mapq: what the filtered BAM of the pass would
+// hold), counted from the records in memory while the SAM is being written: <profile_prefix>.errorprofile / .indelprofile
+void map_profiled(const MapArgs &a, const char *out_sam, int min_mapq, int max_read_len, const char *profile_prefix)
+{
+    const int nthr = a.threads > 0 ? a.threads : 1;
+    MapJob job; job.a = a;
+    job.outs.emplace_back(new SamText(out_sam, nthr, job.s_write));
+    job.outs.emplace_back(new ProfileOut(min_mapq, max_read_len, profile_prefix, nthr, job.s_profile));
+    Pass(job).run();
+}
+// ps_map with the records going straight into a BAM file: what PARAsuiteMapping.java:102-152 makes of <prefix>.sam with three
+// samtools calls (view -bS, view -q, and -- Mapping.java:85-108 -- sort + index), without the 2 GB of SAM text in between.  Records
+// with MAPQ < min_mapq are left out; sort_by_coordinate / write_index as in ps_sam_to_bam.  Unsorted output is compressed and written
+// piece by piece while later pieces are searched.  zlib level 1 by default (the BAM is 10 % larger than at samtools' level 6 and the call
+// 0.7 s shorter per 10 M reads: compression, not mapping, is what the host spends its time on); PS_BAM_LEVEL=6 for samtools' own.
+void map_to_bam(const MapArgs &a, const char *out_bam, int min_mapq, bool sort_by_coordinate, bool write_index, BamStats *stats)
+{
+    BamOut bo; bo.min_mapq = min_mapq; bo.sort = sort_by_coordinate; bo.index = write_index; bo.stats = stats;
+    if (const char *e = std::getenv("PS_BAM_LEVEL")) bo.level = std::atoi(e);
+    MapJob job; job.a = a; job.bam_out = true;
+    job.outs.emplace_back(new BamRecords(bo, out_bam, a.threads > 0 ? a.threads : 1, job.s_write));
+    Pass(job).run();
+}
+
+// ---- the whole `map` mode (Main.java:249-420) in one call ---------------------------------------------------------------------
+// The passes are the one above, over contexts that stay open from pass to pass: the genome's index is loaded once and keeps its lanes of
+// work; the reads are parsed once and kept (up to PS_ROUTE_KEEP_MB of host memory) for the profile pass; the first pass's profile is
+// counted from its records in memory (ps_map_profiled's path); the weak reads of the last genomic pass go to the transcript pass as a
+// ReadSet, not as FASTQ text; the sorted records of the last genomic pass and of the transcript pass stay in memory for the lift.
+namespace {
+struct RouteFiles {                    // outputs are written under a temporary name and renamed when their step is done; a failed call removes both kinds
+    std::vector<std::string> tmp, made;
+    static std::string tmp_name(const std::string &name) { return name + ".route-tmp"; }
+    std::string open(const std::string &name) { const std::string t = tmp_name(name); tmp.push_back(t); return t; }
+    void publish(const std::string &t, const std::string &name)
+    {
+        if (std::rename(t.c_str(), name.c_str()) != 0) throw Error("cannot rename " + t + " to " + name);
+        made.push_back(name);
+    }
+    void drop() { for (const std::string &f : tmp) std::remove(f.c_str()); for (const std::string &f : made) std::remove(f.c_str()); }
+};
+size_t readset_bytes(const ReadSet &rs)
+{
+    return rs.len.size() * 4 + rs.off.size() * 8 + rs.name_off.size() * 8 + rs.seq.size() + rs.qual.size() + rs.names.size();
+}
+// ExtractWeakMappingReads on a located piece: the reads whose record has MAPQ < threshold, as a second parse of their FASTQ text would return
+// them (the read as it was sequenced is what the ReadSet holds; the parser takes one more trailing /1 or /2 off the name)
+void gather_weak(const Batch &b, int threshold, ReadSet &w, uint64_t &n_weak)
+{
+    const ReadSet &rs = b.rs;
+    if (w.off.empty()) { w.off.push_back(0); w.name_off.push_back(0); }
+    for (int64_t g = 0; g < rs.n; ++g) {
+        Hit h; b.hit_of(g, h);
+        if ((h.type ? h.mapq : 0) >= threshold) continue;
+        size_t nl; const char *nm = rs.name(g, nl);
+        if (rs.len[g] == 0) throw Error("extract: record " + std::string(nm, nl) + " has MAPQ below " + std::to_string(threshold) + " and no SEQ ('*'): it cannot be mapped again");
+        if (!rs.has_qual) throw Error("extract: record " + std::string(nm, nl) + " has MAPQ below " + std::to_string(threshold) + " and no QUAL ('*'): it cannot be written as FASTQ");
+        if (nl > 2 && nm[nl - 2] == '/' && (nm[nl - 1] == '1' || nm[nl - 1] == '2')) nl -= 2;
+        w.names.insert(w.names.end(), nm, nm + nl); w.name_off.push_back((int64_t)w.names.size());
+        w.seq.insert(w.seq.end(), rs.seq.data() + rs.off[g], rs.seq.data() + rs.off[g + 1]);
+        w.qual.insert(w.qual.end(), rs.qual.data() + rs.off[g], rs.qual.data() + rs.off[g + 1]);
+        w.len.push_back(rs.len[g]); w.off.push_back((int64_t)w.seq.size());
+        ++w.n; ++n_weak;
+    }
+    w.has_qual = true;
+}
+bool has(const char *s) { return s && s[0]; }
+
+// the call's state between its passes, and one pass of it
+struct Route {
+    const ps_route_opts &o; const int threads, gm; int bam_level = 1;
+    RouteFiles files; CtxSet genome, transcripts;
+    std::vector<ReadSet> kept, weak; size_t kept_bytes = 0, keep_bound = (size_t)8192 << 20; bool kept_all = true;
+    uint64_t n_weak = 0;
+    BamFile G, T;
+    Route(const ps_route_opts &opts, int thr, int mapq_genomic) : o(opts), threads(thr), gm(mapq_genomic)
+    {
+        if (const char *e = std::getenv("PS_ROUTE_KEEP_MB")) keep_bound = (size_t)std::max(0, std::atoi(e)) << 20;
+        if (const char *e = std::getenv("PS_BAM_LEVEL")) bam_level = std::atoi(e);
+    }
+    void weak_of(Batch &b) { weak.emplace_back(); gather_weak(b, gm, weak.back(), n_weak); }
+    void keep(Batch &b)                    // the parsed piece stays for the profile pass, within the bound
+    {
+        if (!kept_all) return;
+        const size_t bytes = readset_bytes(b.rs);
+        if (kept_bytes + bytes > keep_bound) { kept_all = false; kept.clear(); kept.shrink_to_fit(); kept_bytes = 0; return; }
+        kept_bytes += bytes; kept.push_back(std::move(b.rs));
+    }
+    // one pass: a sorted BAM (+ index, or by name) under its temporary name, published when the pass is done.  job: the input source,
+    // the contexts and the outputs that follow the records
+    void pass(MapJob &job, const char *mm, const char *ep, const char *ip, const char *ref, const std::string &out, int min_mapq, bool by_name, BamFile *keep_recs, ps_bam_stats &bs_out)
+    {
+        BamStats bs; BamOut bo; bo.min_mapq = min_mapq; bo.sort = !by_name; bo.index = !by_name; bo.by_name = by_name; bo.keep = keep_recs; bo.stats = &bs; bo.level = bam_level;
+        const std::string t = files.open(out); if (!by_name) files.tmp.push_back(t + ".bai");
+        job.a = MapArgs{threads, mm, ep, ip, ref, o.reads_fq}; job.bam_out = true;
+        job.outs.emplace(job.outs.begin(), new BamRecords(bo, t.c_str(), threads, job.s_write));
+        Pass(job).run();
+        files.publish(t, out); if (!by_name) files.publish(t + ".bai", out + ".bai");
+        bs_out.n_in = bs.n_in; bs_out.n_out = bs.n_out; bs_out.bam_bytes = bs.bam_bytes;
+    }
+    void close() { transcripts.xs.clear(); genome.xs.clear(); }
+};
+}
+
+void map_route(const ps_route_opts *o, ps_route_stats *stats_out)
+{
+    if (!o) throw Error("ps_map_route: no options");
+    if (!has(o->reads_fq)) throw Error("ps_map_route: the reads file (-q) is required");
+    if (!has(o->ref_fa)) throw Error("ps_map_route: the reference (-r) is required");
+    if (!has(o->out_prefix)) throw Error("ps_map_route: the output prefix (-o) is required");
+    const bool refine = o->refine != 0, with_t = has(o->transcripts_fa), given = has(o->error_profile);
+    if (given && !refine) throw Error("ps_map_route: an error profile without refine: nothing to map");
+    if (has(o->indel_profile) && !given) throw Error("ps_map_route: an indel profile without an error profile");
+    const int threads = o->threads > 0 ? o->threads : 1, max_len = o->max_read_len > 0 ? o->max_read_len : 101;
+    const int gm = o->mapq_genomic > 0 ? o->mapq_genomic : 10, tm = o->mapq_transcript > 0 ? o->mapq_transcript : 1;
+    const char *bwa_mm = has(o->bwa_mm) ? o->bwa_mm : "2", *para_mm = has(o->parasuite_mm) ? o->parasuite_mm : "-1";
+    if (max_len > 4096) throw Error("ps_map_route: maximum read length out of range");
+    const std::string P = o->out_prefix;
+    const bool first_pass = !given;
+    const std::string f_bwa = P + ".BWA-genomic.bam", f_para = P + ".PARAsuite-genomic.bam", f_comb = P + ".combined.bam";
+    const std::string f_tr = P + (refine ? ".PARAsuite-transcript.bam" : ".BWA-transcript.bam");
+    const std::string f_ep = f_bwa + ".errorprofile", f_ip = f_bwa + ".indelprofile";
+    {
+        // every name the call writes: the outputs, and the temporary name each is written under (RouteFiles::open)
+        std::vector<std::string> outs;
+        auto bam = [&](const std::string &f, bool index) { outs.push_back(f); outs.push_back(RouteFiles::tmp_name(f)); if (index) { outs.push_back(f + ".bai"); outs.push_back(RouteFiles::tmp_name(f) + ".bai"); } };
+        if (first_pass) {
+            bam(f_bwa, true);
+            if (refine) for (const char *x : {".errorprofile", ".indelprofile"}) { outs.push_back(f_bwa + x); outs.push_back(RouteFiles::tmp_name(f_bwa + ".profile") + x); }
+        }
+        if (refine) bam(f_para, true);
+        if (with_t) { bam(f_tr, false); bam(f_comb, true); }
+        const char *ins[] = {o->reads_fq, o->ref_fa, o->transcripts_fa, o->error_profile, o->indel_profile};
+        for (const std::string &f : outs) for (const char *in : ins)
+            if (has(in) && same_file(f.c_str(), in)) throw Error("ps_map_route: the output " + f + " would overwrite the input " + in);
+    }
+    { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error("ps_map_route: no HIP device available: parasuite-hip has no CPU path"); }
+
+    const auto t_begin = clk::now();
+    ps_route_stats st; std::memset(&st, 0, sizeof st);
+    Route r(*o, threads, gm);
+    RouteFiles &files = r.files;
+    std::string step = "first pass";
+    try {
+        const bool weak_after_first = with_t && !refine;
+        std::string ep = given ? o->error_profile : "", ip = has(o->indel_profile) ? o->indel_profile : "";
+        if (first_pass) {
+            const auto t0 = clk::now();
+            MapJob job; job.resident = &r.genome;
+            if (refine) {
+                const std::string prefix = files.open(f_bwa + ".profile");
+                files.tmp.push_back(prefix + ".errorprofile"); files.tmp.push_back(prefix + ".indelprofile");
+                job.outs.emplace_back(new ProfileOut(gm, max_len, prefix, threads, job.s_profile));
+            }
+            if (weak_after_first) job.outs.emplace_back(new PieceFn([&r](Batch &b) { r.weak_of(b); }));
+            else if (refine) job.outs.emplace_back(new PieceFn([&r](Batch &b) { r.keep(b); }));
+            r.pass(job, bwa_mm, nullptr, nullptr, o->ref_fa, f_bwa, gm, false, weak_after_first ? &r.G : nullptr, st.first);
+            st.n_reads = (uint64_t)job.n_reads; st.s_parse = job.s_parse; st.s_index_genome = job.s_index; st.n_fastq_parses = 1;
+            st.s_first = secs_since(t0);
+            if (refine) {
+                step = "profile";
+                const auto t1 = clk::now();
+                const std::string prefix = RouteFiles::tmp_name(f_bwa + ".profile");
+                files.publish(prefix + ".errorprofile", f_ep); files.publish(prefix + ".indelprofile", f_ip);
+                ep = f_ep; ip = f_ip;
+                st.s_profile = secs_since(t1);
+            }
+        }
+        if (refine) {
+            step = "refine pass";
+            const auto t0 = clk::now();
+            MapJob job; job.resident = &r.genome;
+            if (first_pass && r.kept_all) job.reads = &r.kept; else ++st.n_fastq_parses;
+            if (with_t) job.outs.emplace_back(new PieceFn([&r](Batch &b) { r.weak_of(b); }));
+            r.pass(job, para_mm, ep.c_str(), ip.empty() ? nullptr : ip.c_str(), o->ref_fa, f_para, gm, false, with_t ? &r.G : nullptr, st.refine);
+            if (!first_pass) { st.n_reads = (uint64_t)job.n_reads; st.s_parse = job.s_parse; st.s_index_genome = job.s_index; }
+            st.s_refine = secs_since(t0);
+        }
+        r.kept.clear();
+        if (with_t) {
+            step = "transcript pass";
+            const auto t0 = clk::now();
+            st.extract.n_records = st.n_reads; st.extract.n_weak = r.n_weak; st.extract.n_kept = st.n_reads - r.n_weak;
+            MapJob job; job.resident = &r.transcripts; job.reads = &r.weak; job.lanes_from = &r.genome;
+            r.pass(job, refine ? para_mm : bwa_mm, refine ? ep.c_str() : nullptr, refine && !ip.empty() ? ip.c_str() : nullptr, o->transcripts_fa, f_tr, tm, true, &r.T, st.transcript);
+            st.s_index_transcripts = job.s_index; st.s_transcript = secs_since(t0);
+            step = "combine";
+            const auto t1 = clk::now();
+            const int dev = r.genome.xs[0]->device;                    // the first device of the passes
+            const std::string t = files.open(f_comb); files.tmp.push_back(t + ".bai");
+            combine_records(r.G, r.T, f_tr.c_str(), t.c_str(), true, true, threads, dev, &st.combine);
+            files.publish(t, f_comb); files.publish(t + ".bai", f_comb + ".bai");
+            st.s_combine = secs_since(t1);
+        }
+        step = "closing";
+        st.n_index_loads_genome = (uint32_t)r.genome.n_index_loads; st.n_index_loads_transcripts = (uint32_t)r.transcripts.n_index_loads;
+        r.close();
+    } catch (const std::exception &e) {
+        const std::string m = e.what();
+        r.close();
+        files.drop();
+        throw Error("ps_map_route: " + step + ": " + m);
+    }
+    st.s_total = secs_since(t_begin);
+    if (stats_out) *stats_out = st;
+    if (std::getenv("PS_VERBOSE"))
+        std::fprintf(stderr, "[parasuite-hip] ps_map_route: %llu reads, %.3f s: parse %.3f s (the file was parsed %u time(s)), genome index resident after %.3f s (%u load(s)), first pass %.3f s, "
+                             "profile files %.3f s, refine pass %.3f s, %llu weak reads, transcript index after %.3f s (%u load(s)), transcript pass %.3f s, combine %.3f s\n",
+                     (unsigned long long)st.n_reads, st.s_total, st.s_parse, st.n_fastq_parses, st.s_index_genome, st.n_index_loads_genome, st.s_first, st.s_profile, st.s_refine,
+                     (unsigned long long)st.extract.n_weak, st.s_index_transcripts, st.n_index_loads_transcripts, st.s_transcript, st.s_combine);
+}
+
+}  // namespace ps

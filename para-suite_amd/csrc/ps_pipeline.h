@@ -89,6 +89,13 @@ struct Ctx {
     Work *take_work();             // creates the lane's stream on first use
     Work *work_at(int i);          // lane i (ps_map: one per worker thread of the device); thread safe
     std::mutex work_mu;
+    // A context in two steps: options and knobs (no device call: ps_map's parser needs nothing else and starts before the runtime is
+    // up, which takes 0.2-0.3 s in a fresh process), then the device side (stream, clock).
+    explicit Ctx(int device);      // reads the tuning knobs from the environment (PS_FETCH_MIN, PS_N_BIG, ...)
+    void attach_device();          // needs a HIP device; a second call does nothing
+    void set_stock(const char *n_arg);                                            // bwa aln's -n
+    void set_profile(const char *ep, const char *ip, const char *x_arg);          // the two profile files and -X
+    void set_options(const char *mm, const char *ep, const char *ip) { if (ep && ep[0]) set_profile(ep, ip, mm); else set_stock(mm && mm[0] ? mm : "0.04"); }   // a mapping call's three arguments
     ~Ctx();
 };
 

@@ -38,6 +38,36 @@ void require_device(int device)
     PS_HIP(hipSetDevice(device));
 }
 
+Ctx::Ctx(int device_) : device(device_)
+{
+    if (const char *e = std::getenv("PS_FETCH_MIN")) fetch_min = std::atoi(e);       // tuning knobs
+    if (const char *e = std::getenv("PS_N_BIG")) n_big = std::atoi(e);
+    if (const char *e = std::getenv("PS_HIT_MIN")) hit_min = std::atoi(e);
+    if (std::getenv("PS_READ_ITERS")) want_read_iters = true;
+    if (std::getenv("PS_KSTATS")) want_kstats = true;
+    if (const char *e = std::getenv("PS_BT_BLOCKS")) bt_blocks = std::atoi(e);
+    if (const char *e = std::getenv("PS_POOL_CAP")) pool_cap[0] = (uint32_t)std::atoi(e);
+    if (const char *e = std::getenv("PS_ALN_CAP")) { aln_cap[0] = std::max(1, std::atoi(e)); aln_cap_short = 0; }   // hit intervals a read may list in the first tier (stated: for every length)
+}
+void Ctx::attach_device()
+{
+    require_device(device);
+    if (stream) return;
+    PS_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    PS_HIP(hipEventCreate(&ref_event)); PS_HIP(hipEventRecord(ref_event, stream)); PS_HIP(hipEventSynchronize(ref_event));
+}
+void Ctx::set_stock(const char *n_arg)
+{
+    Options o; set_stock_n(o, n_arg);
+    if (o.max_diff < 0 && !(o.fnr > 0.0)) throw Error("bad -n argument");
+    opt = o;
+}
+void Ctx::set_profile(const char *ep, const char *ip, const char *x_arg)
+{
+    double P[16], ins, del; std::string err;
+    if (!read_profile_files(ep, ip, P, ins, del, err)) throw Error(err);
+    Options o; profile_costs(o, P, ins, del, x_arg ? std::atoi(x_arg) : -1); opt = o;
+}
 Ctx::~Ctx() { if (ref_event) (void)hipEventDestroy(ref_event); if (stream) (void)hipStreamDestroy(stream); }
 void ctx_release_device(Ctx &c)
 {

@@ -331,4 +331,28 @@ void reads_from_codes(int64_t n, int len, const uint8_t *codes, ReadSet &rs)
     rs.has_qual = false;
 }
 
+// host-only: parse reads the way ps_map does (whole file on `threads` threads, or streamed in windows of chunk_bytes) and
+// summarise what came out -- {reads, bases, order-sensitive hash of names/sequences/qualities, pieces}
+void parse_check(const char *reads_path, int threads, size_t chunk_bytes, uint64_t out[4])
+{
+    uint64_t n = 0, bases = 0, h = 1469598103934665603ull, pieces = 0;
+    auto mix = [&](const void *p, size_t len) { const unsigned char *c = (const unsigned char *)p; for (size_t i = 0; i < len; ++i) { h ^= c[i]; h *= 1099511628211ull; } h ^= 0xff; h *= 1099511628211ull; };
+    auto eat = [&](const ReadSet &rs) {
+        ++pieces;
+        for (int64_t i = 0; i < rs.n; ++i) {
+            size_t nl; const char *nm = rs.name(i, nl);
+            mix(nm, nl); mix(rs.seq.data() + rs.off[i], (size_t)rs.len[i]); mix(rs.qual.data() + rs.off[i], (size_t)rs.len[i]);
+            bases += (uint64_t)rs.len[i];
+        }
+        n += (uint64_t)rs.n;
+    };
+    if (chunk_bytes == 0) { ReadSet rs; load_reads(reads_path, rs, threads); eat(rs); }
+    else if (const char *e = std::getenv("PS_PARSE_CHECK_HUNGRY")) {       // tests: a consumer that always waits, as ps_map's GPU worker does at the start: pieces go out at `e` bytes
+        const std::function<bool()> hungry = []() { return true; };
+        load_reads_chunked(reads_path, threads, chunk_bytes, [&](ReadSet &&rs) { eat(rs); }, 0, &hungry, (size_t)std::max(1, std::atoi(e)));
+    }
+    else load_reads_chunked(reads_path, threads, chunk_bytes, [&](ReadSet &&rs) { eat(rs); });
+    out[0] = n; out[1] = bases; out[2] = h; out[3] = pieces;
+}
+
 }  // namespace ps

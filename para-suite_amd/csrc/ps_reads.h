@@ -34,5 +34,6 @@ void load_reads(const char *path, ReadSet &rs, int threads = 1); // FASTQ or FAS
 void load_reads_chunked(const char *path, int threads, size_t chunk_bytes, const std::function<void(ReadSet &&)> &sink, size_t first_bytes = 0,
                         const std::function<bool()> *hungry = nullptr, size_t hungry_min_bytes = 0);
 void reads_from_codes(int64_t n, int len, const uint8_t *codes, ReadSet &rs);
+void parse_check(const char *reads_path, int threads, size_t chunk_bytes, uint64_t out[4]);   // ps_parse_check: {reads, bases, hash, pieces}
 
 }  // namespace ps

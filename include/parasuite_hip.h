@@ -324,6 +324,49 @@ typedef struct {
 } ps_route_stats;
 int     ps_map_route(const ps_route_opts *opts, ps_route_stats *stats /* may be NULL */);
 
+/* ---- after the mapping: the toolkit's `benchmark MAPPING OUT.stats READS.fastq` mode (Main.java:489-521) -------------------------
+ * `new ValidateBenchmarkStatisticsPARCLIP().calculateBenchmarkStatistics(mapping, outStatistics, readsFile, onlyBound)`
+ * (src/src/utils/benchmarking/ValidateBenchmarkStatisticsPARCLIP.java:43-242): a mapping of simulated PAR-CLIP reads scored
+ * against the truth in the read names "..|..|CONTIG|START|END|BOUND-..", counted on the GPU; the rules are those of the Java as
+ * it is written, restated in plain Python in tests/java_benchmark.py (no JVM is at hand to pin it to the jar):
+ *   - the reads file (:78-103) is plain text, a gzip magic number is an error.  Lines end at "\n", "\r" or "\r\n"
+ *     (BufferedReader.readLine); a last line without an end counts, an end at the end of the file adds no line.  EVERY line
+ *     that starts with "@SEQ_ID" -- a quality line may -- is split on '|' (trailing empty fields dropped, as String.split
+ *     does) and the text of field 5 before its first '-' counts a positive ("1"), a negative ("0") or nothing;
+ *   - the mapping is SAM or BAM; every record counts in file order whatever its flags, unmapped and secondary ones too
+ *     (:105-163).  QNAME is split the same way; fields 3 and 4 go through Integer.parseInt (one optional sign, ASCII digits,
+ *     int32 range).  The first record where that fails ends the count (:177 catches the exception outside the loop): the
+ *     records before it are scored, n_processed is its 0-based index, bad_number_record its 1-based one, and the file IS written;
+ *   - a record hits when the truth contig equals the reference name ('*' without one), START - 5 <= alignment start and
+ *     END + 5 >= alignment end (32-bit wrap-around as in Java).  Alignment start is POS (0 without one); alignment end
+ *     follows this library's rule for getAlignmentEnd, stated at ps_combine_genome_transcript above: 0 for a record with flag
+ *     4, so a bridging record that keeps RNAME and POS inside the window scores.  A hit counts TP for bound "1", TN for "0";
+ *   - before the comparison (:130-143) the truth contig gets "chr" put in front when the reference name of this OR ANY EARLIER
+ *     record starts with "chr" and it lacks it, loses a leading "chr" when no record so far had one, and then exactly "chrM"
+ *     becomes "chrMT": a chrM contig never scores, a chrMT contig scores from truth M, chrM or chrMT (the Java's quirk);
+ *   - out_statistics (:200-225), no newline at its end: "matched correctly:\t<TP+TN>\nreadsProcessed:\t<n>\nall reads:\t<lines/4>
+ *     \nprecision:\t<f>\nrecall:\t<f>\naccuracy:\t<f>" with FP = positives - TP, FN = negatives - TN, (float)TP / (TP + FP),
+ *     (float)TP / (TP + FN), (float)(TP + TN) / (positives + negatives) in Java int and float arithmetic (NaN for 0/0,
+ *     Infinity for x/0), each as Float.toString writes it (the JDK 19+ definition: the shortest decimal that reads back).
+ * Deviations, all where the Java dies or misleads: a "@SEQ_ID" line or a QNAME with fewer than six fields, or whose field 5 is
+ * made of '-' only (uncaught ArrayIndexOutOfBounds), is an error naming the 1-based line or record -- for a record only when
+ * no unparsable number ended the count before it; a line count that is no multiple of 4 (the Java logs and exits 0 without a
+ * file) and a count above 2^31 - 1 (the Java's ints wrap) are errors; nothing is written then.  The Java's "TP=..; TN=.." line
+ * on stdout is not reproduced: PS_VERBOSE=1 prints it to stderr with the stage times.  --only-bound is parsed by the Java and
+ * never used (:120-125), so it is no parameter here.  Records that score nothing are counted by the first reason that applies
+ * (n_unplaced .. n_other_bound below); that breakdown is this library's own and does not enter the file.
+ * PS_BENCH_PIECE: bytes of the reads file per staged piece (default 64 MiB; the counts do not depend on it).
+ * Without a HIP device the call fails. */
+typedef struct {
+    uint64_t n_lines, n_reads, n_positives, n_negatives;     /* FASTQ pass: lines, lines / 4, "@SEQ_ID" lines with bound "1" / "0" */
+    uint64_t n_records, n_processed, n_tp, n_tn;             /* records in the file; the Java's readsProcessed; truePositives; trueNegatives */
+    uint64_t n_unplaced, n_other_contig, n_outside, n_other_bound; /* why a processed record scored nothing: reference '*'; names differ; the +-5 window fails; bound neither "0" nor "1" (first reason that applies, in this order) */
+    uint64_t bad_number_record;                              /* 1-based index of the record whose start/end did not parse and ended the count; 0: none */
+    float precision, recall, accuracy;                       /* as written to the file */
+} ps_benchmark_stats;
+int     ps_benchmark_reads(const char *mapping_sam_or_bam, const char *out_statistics, const char *reads_fq,
+                           ps_benchmark_stats *stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,7 +44,7 @@ EXPORTS = ["ps_version", "ps_last_error", "ps_index", "ps_map", "ps_ctx_open", "
            "ps_ctx_blob", "ps_ctx_meta", "ps_ctx_from_blobs", "ps_ctx_clone", "ps_ctx_fetch", "ps_ctx_export_blob", "ps_ctx_sa_lookup", "ps_ctx_order_sort", "ps_ctx_index_check", "ps_sam_to_bam", "ps_map_to_bam", "ps_bam_view", "ps_bam_sort", "ps_bam_index", "ps_batch_from_fastq",
            "ps_batch_from_codes", "ps_batch_free", "ps_batch_n", "ps_batch_search", "ps_batch_select_hard",
            "ps_batch_select_easy", "ps_batch_locate", "ps_batch_run", "ps_batch_write_sam", "ps_batch_n_aln",
-           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route"]
+           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route", "ps_benchmark_reads"]
 
 _LIB = None
 
@@ -413,6 +413,22 @@ def ps_combine_genome_transcript(genome_bam, transcript_bam, out_bam, sort_by_co
     _chk(L.ps_combine_genome_transcript(genome_bam.encode(), transcript_bam.encode(), out_bam.encode(), int(bool(sort_by_coordinate)),
                                         int(bool(write_index)), int(threads), C.byref(st)))
     return {f: int(getattr(st, f)) for f, _ in CombineStats._fields_}
+
+
+class BenchmarkStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_lines", "n_reads", "n_positives", "n_negatives", "n_records", "n_processed", "n_tp", "n_tn",
+                                          "n_unplaced", "n_other_contig", "n_outside", "n_other_bound", "bad_number_record")] + \
+               [(k, C.c_float) for k in ("precision", "recall", "accuracy")]
+
+
+def ps_benchmark_reads(mapping, out_statistics, reads_fq):
+    """ValidateBenchmarkStatisticsPARCLIP.calculateBenchmarkStatistics: a mapping of simulated reads (SAM or BAM) scored against
+    the truth in the read names, the reads file counted for the totals (both on the GPU); writes out_statistics and returns
+    the counters"""
+    L = lib(); L.ps_benchmark_reads.argtypes = [C.c_char_p] * 3 + [C.POINTER(BenchmarkStats)]
+    st = BenchmarkStats()
+    _chk(L.ps_benchmark_reads(mapping.encode(), out_statistics.encode(), reads_fq.encode(), C.byref(st)))
+    return {f: getattr(st, f) for f, _ in BenchmarkStats._fields_}
 
 
 def ps_map_profiled(threads, mm, error_profile, indel_profile, ref_fa, reads, out_sam, min_mapq, max_read_len, profile_prefix):

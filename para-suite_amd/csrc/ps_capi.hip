@@ -447,6 +447,17 @@ int ps_combine_genome_transcript(const char *genome_bam, const char *transcript_
     PS_CATCH_INT
 }
 
+// The toolkit's `benchmark` mode (Main.java:489-521): ValidateBenchmarkStatisticsPARCLIP.calculateBenchmarkStatistics.  The file is
+// opened only after both counting passes: an error before that leaves none.
+int ps_benchmark_reads(const char *mapping_sam_or_bam, const char *out_statistics, const char *reads_fq, ps_benchmark_stats *stats)
+{
+    PS_TRY
+        const int dev = first_device();
+        benchmark_run(mapping_sam_or_bam, out_statistics, reads_fq, dev, stats);
+        return 0;
+    PS_CATCH_INT
+}
+
 int ps_sam_to_bam(const char *sam, const char *bam, int min_mapq, int sort_by_coordinate, int write_index, int threads, ps_bam_stats *st)
 {
     PS_TRY

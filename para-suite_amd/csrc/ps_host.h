@@ -128,6 +128,7 @@ void error_profile_write(const ProfileCounts &c, const std::string &out_prefix);
 // the other four files of ErrorProfiling.java: .errorprofile.vcf, .qualityPerMismatch, .indels, .qualities (empty unless c.quals == 2)
 void error_profile_write_extra(const ProfileCounts &c, const std::string &out_prefix);
 std::string java_double_to_string(double v);                                        // java.lang.Double.toString
+std::string java_float_to_string(float v);                                          // java.lang.Float.toString (ps_benchmark.hip)
 
 // ---- RBP-bound clusters from a sorted mapping (ps_clusters.hip; what PileupClusters.calculateReadPileups writes) ----
 void pileup_clusters_run(const char *mapping_sam_or_bam, const char *ref_fa, const char *out_file, const char *snp_vcf, int min_cov,
@@ -139,5 +140,11 @@ void combine_run(const char *genome_sam_or_bam, const char *transcript_sam_or_ba
 struct BamFile;
 void combine_records(BamFile &genome, BamFile &transcript, const char *transcript_path, const char *out_bam, bool sort_by_coordinate, bool write_index,
                      int threads, int device, ps_combine_stats *stats, double parse_ms = 0);   // the same on loaded records, which it consumes
+
+// ---- a mapping of simulated reads scored against the truth in the read names (ps_benchmark.hip; ValidateBenchmarkStatisticsPARCLIP) ----
+void benchmark_run(const char *mapping_sam_or_bam, const char *out_statistics, const char *reads_fq, int device, ps_benchmark_stats *stats);
+struct BenchmarkRatios { int32_t fp, fn, matched; float precision, recall, accuracy; };   // as Java ints (they wrap) and floats
+BenchmarkRatios benchmark_ratios(const ps_benchmark_stats &st);
+std::string benchmark_text(const ps_benchmark_stats &st, const BenchmarkRatios &r);  // the statistics file
 
 }  // namespace ps

@@ -207,6 +207,20 @@ class CombineGenomeTranscript:
             raise ExternalCallErrorException("CombineGenomeTranscript %s %s: %s" % (genomeMappingFileName, transcriptMappingFileName, e))
 
 
+class ValidateBenchmarkStatisticsPARCLIP:
+    """mirror of utils.benchmarking.ValidateBenchmarkStatisticsPARCLIP (ValidateBenchmarkStatisticsPARCLIP.java:43-242), the
+    `benchmark` mode (Main.java:489-521): `new ValidateBenchmarkStatisticsPARCLIP().calculateBenchmarkStatistics(mappingFileName,
+    outStatistics, readsFile, onlyBoundClusters)` scores a mapping of simulated PAR-CLIP reads against the truth in the read names
+    and writes the six lines of outStatistics, counted on the GPU (`ps_benchmark_reads`).  onlyBoundClusters is accepted and
+    ignored, as the Java ignores it (:120-125).  Returns the stats dict."""
+
+    def calculateBenchmarkStatistics(self, mappingFileName, outStatistics, readsFile, onlyBoundClusters=False):
+        try:
+            return capi.ps_benchmark_reads(mappingFileName, outStatistics, readsFile)
+        except capi.PsError as e:
+            raise ExternalCallErrorException("ValidateBenchmarkStatisticsPARCLIP %s %s: %s" % (mappingFileName, readsFile, e))
+
+
 class Main:
     """mirror of main.Main's `map` mode (Main.java:249-420) for the BWA and PARA-suite mappers, as ONE library call
     (`ps_map_route`): `-q readFileName -r referenceFileName -o outputPrefix [-t transcriptFileName] [-p threads] [-l maxReadLength]

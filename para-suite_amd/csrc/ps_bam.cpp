@@ -20,6 +20,7 @@
 #include <vector>
 #include "ps_bam.h"
 #include "ps_error.h"
+#include "ps_java.h"
 
 namespace ps {
 namespace {
@@ -93,7 +94,7 @@ static bool encode_line(const char *line, size_t n, const std::map<std::string, 
             if (!w || !any) throw Error("bad CIGAR: " + std::string(f[5].p, f[5].n));
             const int op = (int)(w - ops);
             cig.push_back((num << 4) | (uint32_t)op);
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += num;
+            if (cigar_on_ref(op)) ref_len += num;
             num = 0; any = false;
         }
     }
@@ -289,7 +290,8 @@ static void inflate_bgzf(const char *path, int threads, Blocks &out)
         }
     });
 }
-static uint32_t rd32(const std::string &s, size_t at) { const unsigned char *p = (const unsigned char *)s.data() + at; return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+static uint32_t rd32(const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
+static uint32_t rd32(const std::string &s, size_t at) { return rd32((const uint8_t *)s.data() + at); }
 
 // ---- BAM file -> Data (records stay as they are; their place in the file is kept for indexing)
 static void load_bam(const char *path, int threads, Data &d, Blocks *keep_blocks, std::vector<uint64_t> *rec_u)
@@ -322,8 +324,8 @@ static void load_bam(const char *path, int threads, Data &d, Blocks *keep_blocks
         const uint32_t l_name = w & 0xff, n_cig = fl & 0xffff;
         r.flag = fl >> 16;
         int64_t ref_len = 0;
-        const size_t cig_at = p + 36 + l_name;
-        for (uint32_t c = 0; c < n_cig; ++c) { const uint32_t v = rd32(e, cig_at + 4 * c); const int op = (int)(v & 15); if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += v >> 4; }
+        const size_t cig_at = p + 36 + l_name;                   // words beyond the record's end (a corrupt record: flatten_records names it) are not read
+        for (uint32_t c = 0; c < n_cig && cig_at + 4 * c + 4 <= p + 4 + bs; ++c) { const uint32_t v = rd32(e, cig_at + 4 * c); if (cigar_on_ref((int)(v & 15))) ref_len += v >> 4; }
         r.end = (int32_t)(r.pos + (ref_len > 0 ? ref_len : 1));
         d.recs.push_back(r);
         if (rec_u) rec_u->push_back((uint64_t)(base_u + p));
@@ -649,45 +651,6 @@ void bam_index(const char *bam, int threads)
     write_bai(std::string(bam) + ".bai", d, lay);
 }
 
-void load_alignments(const char *path, int threads, AlnTable &out, bool with_qual)
-{
-    threads = clamp_threads(threads);
-    unsigned char mg[2] = {0, 0};
-    { FILE *f = std::fopen(path, "rb"); if (!f) throw Error(std::string("cannot open ") + path); const size_t g = std::fread(mg, 1, 2, f); (void)g; std::fclose(f); }
-    Data d;
-    if (mg[0] == 31 && mg[1] == 139) load_bam(path, threads, d, nullptr, nullptr); else load_sam(path, -1, threads, d);
-    out = AlnTable();
-    out.refs = d.refs;
-    if (d.text.compare(0, 3, "@HD") == 0) {
-        const std::string hd = d.text.substr(0, d.text.find('\n'));
-        const size_t at = hd.find("\tSO:");
-        if (at != std::string::npos) { const size_t e = hd.find('\t', at + 1); out.sort_order = hd.substr(at + 4, e == std::string::npos ? e : e - at - 4); }
-    }
-    const size_t n = d.recs.size();
-    out.ref.resize(n); out.pos.resize(n); out.l_seq.resize(n); out.flag.resize(n); out.cig_off.resize(n); out.n_cig.resize(n); out.seq_off.resize(n);
-    uint64_t bases = 0; uint32_t ops = 0;
-    for (size_t i = 0; i < n; ++i) {
-        const Rec &r = d.recs[i]; const std::string &e = d.enc[r.part];
-        const uint32_t w = rd32(e, r.off + 12), fl = rd32(e, r.off + 16), l_seq = rd32(e, r.off + 20);
-        out.ref[i] = r.ref; out.pos[i] = r.pos; out.flag[i] = fl >> 16; out.l_seq[i] = (int32_t)l_seq;
-        out.n_cig[i] = fl & 0xffff; out.cig_off[i] = ops; out.seq_off[i] = bases;
-        ops += fl & 0xffff; bases += (l_seq + 1) / 2 * 2;          // records start on a byte
-        (void)w;
-    }
-    out.cigar.resize(ops); out.seq.assign((size_t)(bases / 2), 0);
-    if (with_qual) out.qual.assign((size_t)bases, 0xff);          // a record's padding base stays 0xFF
-    par(threads, threads, [&](int t) {
-        for (size_t i = (size_t)t; i < n; i += (size_t)threads) {
-            const Rec &r = d.recs[i]; const std::string &e = d.enc[r.part];
-            const uint32_t l_name = rd32(e, r.off + 12) & 0xff;
-            const size_t cig_at = r.off + 36 + l_name, seq_at = cig_at + 4 * (size_t)out.n_cig[i];
-            for (uint32_t c = 0; c < out.n_cig[i]; ++c) out.cigar[out.cig_off[i] + c] = rd32(e, cig_at + 4 * c);
-            std::memcpy(&out.seq[(size_t)(out.seq_off[i] / 2)], e.data() + seq_at, (size_t)((out.l_seq[i] + 1) / 2));
-            if (with_qual) std::memcpy(&out.qual[(size_t)out.seq_off[i]], e.data() + seq_at + (out.l_seq[i] + 1) / 2, (size_t)out.l_seq[i]);
-        }
-    });
-}
-
 static std::string header_sort_order(const std::string &text)
 {
     if (text.compare(0, 3, "@HD") != 0) return std::string();
@@ -712,6 +675,54 @@ void load_records(const char *path, int threads, BamFile &out)
     out = BamFile();
     out.sort_order = header_sort_order(d.text);
     out.text.swap(d.text); out.refs.swap(d.refs); out.enc.swap(d.enc); out.recs.swap(d.recs);
+}
+
+void flatten_records(const BamFile &f, unsigned columns, const std::vector<int32_t> *rows, int threads, RecTable &out)
+{
+    threads = clamp_threads(threads);
+    const bool cig = columns & kRecCigar, sq = columns & kRecSeq, ql = columns & kRecQual, nm = columns & kRecNames;
+    const size_t n = rows ? rows->size() : f.n();
+    auto row = [&](size_t j) { return rows ? (size_t)(*rows)[j] : j; };
+    out = RecTable();
+    out.columns = columns; out.refs = f.refs; out.sort_order = f.sort_order;
+    out.ref.resize(n); out.pos.resize(n); out.l_seq.resize(n); out.flag.resize(n);
+    if (cig) { out.cig_off.resize(n); out.n_cig.resize(n); }
+    if (sq || ql) out.seq_off.resize(n);
+    if (nm) { out.name_off.resize(n); out.name_len.resize(n); }
+    // a record: block_size, 32 fixed bytes (l_read_name at 12, n_cigar_op at 16, l_seq at 20), name with its NUL, CIGAR, SEQ, QUAL, tags
+    uint64_t words = 0, bases = 0, name_bytes = 0;
+    for (size_t j = 0; j < n; ++j) {
+        const BamRec &r = f.recs[row(j)]; const uint8_t *p = f.rec(row(j));
+        const uint32_t l_name = p[12], n_cig = p[16] | ((uint32_t)p[17] << 8), l_seq = rd32(p + 20);
+        if (r.ref < -1 || r.ref >= (int32_t)f.refs.size()) throw Error("record " + std::to_string(row(j) + 1) + " refers to a reference that is not in the header");
+        if (l_name < 1 || 36 + (uint64_t)l_name + 4 * (uint64_t)n_cig + (sq || ql ? ((uint64_t)l_seq + 1) / 2 : 0) + (ql ? (uint64_t)l_seq : 0) > r.len)
+            throw Error("corrupt record " + std::to_string(row(j) + 1));
+        out.ref[j] = r.ref; out.pos[j] = r.pos; out.flag[j] = r.flag; out.l_seq[j] = (int32_t)l_seq;
+        if (cig) { out.n_cig[j] = n_cig; out.cig_off[j] = (uint32_t)words; words += n_cig; }
+        if (sq || ql) { out.seq_off[j] = bases; bases += ((uint64_t)l_seq + 1) / 2 * 2; }
+        if (nm) { out.name_len[j] = (uint8_t)(l_name - 1); out.name_off[j] = name_bytes; name_bytes += l_name - 1; }
+    }
+    if (words > 0xffffffffull) throw Error("more than 2^32 CIGAR operations");
+    out.cigar.resize((size_t)words); out.names.resize((size_t)name_bytes);
+    if (sq) out.seq.assign((size_t)(bases / 2), 0);
+    if (ql) out.qual.assign((size_t)bases, 0xff);
+    par(threads, threads, [&](int t) {
+        for (size_t j = n * (size_t)t / (size_t)threads; j < n * ((size_t)t + 1) / (size_t)threads; ++j) {
+            const uint8_t *p = f.rec(row(j)), *cg = p + 36 + p[12], *bs = cg + 4 * (size_t)(p[16] | ((uint32_t)p[17] << 8));
+            const size_t l_seq = (size_t)(uint32_t)out.l_seq[j];
+            if (nm && out.name_len[j]) std::memcpy(&out.names[(size_t)out.name_off[j]], p + 36, out.name_len[j]);
+            if (cig) for (uint32_t c = 0; c < out.n_cig[j]; ++c) out.cigar[out.cig_off[j] + c] = rd32(cg + 4 * c);
+            if (sq && l_seq) std::memcpy(&out.seq[(size_t)(out.seq_off[j] / 2)], bs, (l_seq + 1) / 2);
+            if (ql && l_seq) std::memcpy(&out.qual[(size_t)out.seq_off[j]], bs + (l_seq + 1) / 2, l_seq);
+        }
+    });
+}
+
+void load_rec_table(const char *path, unsigned columns, int threads, RecTable &out)
+{
+    BamFile f;
+    load_records(path, threads, f);
+    flatten_records(f, columns, nullptr, threads, out);
 }
 
 bool same_file(const char *a, const char *b)

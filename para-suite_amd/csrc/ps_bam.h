@@ -41,19 +41,7 @@ private:
 void sam_to_bam(const char *sam_path, const char *bam_path, int min_mapq, bool sort_by_coordinate, bool write_index, int threads, BamStats *stats);
 void bam_view(const char *in_bam, const char *out_bam, int min_mapq, int threads, BamStats *stats);     // samtools view -q Q -b
 void bam_sort(const char *in_bam, const char *out_bam, bool by_name, int threads, BamStats *stats);    // samtools sort [-n]
-void bam_index(const char *bam, int threads);
-// the alignments of a SAM or BAM file as flat arrays (what the error-profile stage counts over; ErrorProfiling.java:145-172
-// reads the same fields through htsjdk): CIGAR as BAM words (len<<4|op, MIDNSHP=X), bases as BAM nibbles (=ACMGRSVTWYHKDBN)
-struct AlnTable {
-    std::vector<std::pair<std::string, uint32_t>> refs;       // @SQ name, length
-    std::vector<int32_t> ref, pos, l_seq; std::vector<uint32_t> flag;   // pos: 0-based leftmost; ref -1: unplaced
-    std::vector<uint32_t> cig_off, n_cig, cigar;
-    std::vector<uint64_t> seq_off; std::vector<uint8_t> seq;   // seq_off in bases; base j of a record: nibble (seq_off + j)
-    std::vector<uint8_t> qual;    // with_qual only: Phred value of base j at byte (seq_off + j), as BAM stores it (0xFF: QUAL absent)
-    std::string sort_order;       // SO: of the @HD header line ("" when there is none)
-    size_t n() const { return ref.size(); }
-};
-void load_alignments(const char *sam_or_bam, int threads, AlnTable &out, bool with_qual = false);                                                          // samtools index -> <bam>.bai
+void bam_index(const char *bam, int threads);                                                           // samtools index -> <bam>.bai
 // the records of a SAM or BAM file as they are encoded (SAMv1 4.2), for the steps that pass records on: name, MAPQ, mate fields,
 // QUAL and the raw tag bytes are all in rec(i); recs[i] carries reference id, position, end and flag.  Records in file order;
 // the records of part k are one run of recs, parts in order.
@@ -65,6 +53,26 @@ struct BamFile {
     const uint8_t *rec(size_t i) const { return (const uint8_t *)enc[(size_t)recs[i].part].data() + recs[i].off; }   // block_size first
 };
 void load_records(const char *sam_or_bam, int threads, BamFile &out);
+// The record table: the fields of the records of a BamFile as flat arrays, for the analysis modes' kernels.
+// ref, pos, flag and l_seq always; the other columns by mask.  BAM conventions throughout: pos 0-based (a kernel that wants
+// htsjdk's 1-based start adds one), ref -1 unplaced, CIGAR words len<<4|op with MIDNSHP=X, bases as nibbles =ACMGRSVTWYHKDBN.
+enum : unsigned { kRecCigar = 1, kRecSeq = 2, kRecQual = 4, kRecNames = 8 };
+struct RecTable {
+    unsigned columns = 0;
+    std::vector<std::pair<std::string, uint32_t>> refs; std::string sort_order;   // as the BamFile has them
+    std::vector<int32_t> ref, pos, l_seq; std::vector<uint32_t> flag;
+    std::vector<uint32_t> cig_off, n_cig, cigar;               // kRecCigar
+    std::vector<uint64_t> seq_off;                             // kRecSeq or kRecQual: in bases and always even (records start on a byte)
+    std::vector<uint8_t> seq;                                  // kRecSeq: base j of a record is nibble (seq_off + j)
+    std::vector<uint8_t> qual;                                 // kRecQual: Phred value of base j at byte (seq_off + j); QUAL absent: 0xFF, as a record's padding byte
+    std::vector<uint64_t> name_off; std::vector<uint8_t> name_len, names;   // kRecNames: the name's bytes without its NUL
+    size_t n() const { return flag.size(); }
+};
+// rows: the records to take, in this order (null: all).  The fill runs on `threads` threads.  Every record is checked against its own
+// length first: "corrupt record N", "record N refers to a reference that is not in the header" (N: 1-based, in the file), and
+// "more than 2^32 CIGAR operations" -- the caller puts its name in front.
+void flatten_records(const BamFile &f, unsigned columns, const std::vector<int32_t> *rows, int threads, RecTable &out);
+void load_rec_table(const char *sam_or_bam, unsigned columns, int threads, RecTable &out);   // load_records + flatten_records of all rows
 bool same_file(const char *a, const char *b);   // the same path, or two paths to one file (device and inode)
 struct ExtractStats { uint64_t n_records = 0, n_weak = 0, n_kept = 0, bam_bytes = 0; };
 // ExtractWeakMappingReads.extractReads: records with MAPQ < mapq_threshold -> four FASTQ lines each (read orientation restored),

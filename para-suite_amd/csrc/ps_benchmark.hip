@@ -21,16 +21,15 @@
 #include <fcntl.h>
 #include <unistd.h>
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include "../../include/parasuite_hip.h"
-#include "ps_host.h"
+#include "ps_dev.h"
+#include "ps_java.h"
 #include "ps_pipeline.h"
-#include "ps_bam.h"
 
 namespace ps {
 
@@ -70,23 +69,6 @@ __host__ __device__ inline BmSplit bm_split(const uint8_t *s, uint32_t n)
         r.fatal = k == bl;
     } else if (d == 1) r.bound = b[0] == '1' ? kBmPos : (b[0] == '0' ? kBmNeg : kBmOther);
     return r;
-}
-
-// Integer.parseInt on ASCII: one optional sign, at least one digit, the value in int32 range
-__host__ __device__ inline bool bm_parse_int(const uint8_t *s, uint32_t n, int32_t &v)
-{
-    uint32_t i = 0; bool neg = false;
-    if (n && (s[0] == '-' || s[0] == '+')) { neg = s[0] == '-'; i = 1; }
-    if (i >= n) return false;
-    unsigned long long x = 0;
-    for (; i < n; ++i) {
-        if (s[i] < '0' || s[i] > '9') return false;
-        x = x * 10 + (unsigned long long)(s[i] - '0');
-        if (x > 2147483648ull) return false;                              // leading zeros are fine, so the length says nothing
-    }
-    if (!neg && x > 2147483647ull) return false;
-    v = (int32_t)(neg ? 0u - (uint32_t)x : (uint32_t)x);
-    return true;
 }
 
 __host__ __device__ inline bool bm_is_chr(const uint8_t *s, uint32_t n) { return n >= 3 && s[0] == 'c' && s[1] == 'h' && s[2] == 'r'; }
@@ -153,7 +135,7 @@ __global__ void __launch_bounds__(256) k_bm_fastq(const uint8_t *buf, uint32_t l
 
 struct BmRecs {                        // the records as flat arrays; the reference table has one more entry, "*", at n_ref
     int n; const uint64_t *name_off; const uint8_t *name_len, *names;
-    const int32_t *ref, *aln_start; const uint32_t *flag, *cig_off, *n_cig, *cigar;
+    const int32_t *ref, *pos; const uint32_t *flag, *cig_off, *n_cig, *cigar;
     int n_ref; const uint32_t *ref_off, *ref_len; const uint8_t *ref_names, *ref_chr;
     int32_t *start, *end; uint32_t *truth; uint8_t *cls;                 // k_bm_parse -> k_bm_score: truth = offset | length << 16 of field 2 in the name, cls = bound | status << 4
 };
@@ -167,7 +149,7 @@ __global__ void __launch_bounds__(256) k_bm_parse(BmRecs a, unsigned *first /* F
         const BmSplit sp = bm_split(s, a.name_len[j]);
         int32_t st = 0, en = 0;
         if (sp.fatal) status = kBmFatal;                                  // :113-118 run before :127
-        else if (!bm_parse_int(s + sp.off[1], sp.len[1], st) || !bm_parse_int(s + sp.off[2], sp.len[2], en)) status = kBmBadNum;
+        else if (!java_parse_int(s + sp.off[1], sp.len[1], st) || !java_parse_int(s + sp.off[2], sp.len[2], en)) status = kBmBadNum;
         a.start[j] = st; a.end[j] = en;
         a.truth[j] = sp.off[0] | (sp.len[0] << 16);
         a.cls[j] = (uint8_t)(sp.bound | (status << 4));
@@ -184,13 +166,8 @@ __global__ void __launch_bounds__(256) k_bm_score(BmRecs a, int n, unsigned firs
     const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     int what = -1;
     if (j < n) {
-        const uint32_t *cg = a.cigar + a.cig_off[j];
-        uint32_t ref_len = 0;
-        for (uint32_t k = 0; k < a.n_cig[j]; ++k) {
-            const uint32_t op = cg[k] & 15u;
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += cg[k] >> 4;
-        }
-        const int32_t aln_start = a.aln_start[j];
+        const uint32_t ref_len = (uint32_t)cigar_ref_span(a.cigar + a.cig_off[j], a.n_cig[j]);
+        const int32_t aln_start = (int32_t)((uint32_t)a.pos[j] + 1u);     // htsjdk getAlignmentStart
         const int32_t aln_end = (a.flag[j] & 4u) ? 0 : (int32_t)((uint32_t)aln_start + ref_len - 1u);
         const int r = a.ref[j] < 0 ? a.n_ref : a.ref[j];
         const uint32_t tr = a.truth[j];
@@ -201,32 +178,6 @@ __global__ void __launch_bounds__(256) k_bm_score(BmRecs a, int n, unsigned firs
 }
 
 // ---- host side
-
-// java.lang.Float.toString: java_double_to_string's rules (ps_profile.hip) for a float -- the shortest decimal that reads back
-// as the same float (the JDK 19+ definition), plain for 1e-3 <= |v| < 1e7, else d.dddE<exp>
-std::string java_float_to_string(float v)
-{
-    if (v != v) return "NaN";
-    if (std::isinf(v)) return v > 0 ? "Infinity" : "-Infinity";
-    if (v == 0) return std::signbit(v) ? "-0.0" : "0.0";
-    char buf[64];
-    for (int prec = 1; prec <= 9; ++prec) { std::snprintf(buf, sizeof buf, "%.*e", prec - 1, (double)v); if (std::strtof(buf, nullptr) == v) break; }
-    std::string m(buf); const size_t ep = m.find('e');
-    const int e10 = std::atoi(m.c_str() + ep + 1);
-    std::string digits; bool neg = false;
-    for (size_t i = 0; i < ep; ++i) { if (m[i] == '-') neg = true; else if (m[i] >= '0' && m[i] <= '9') digits.push_back(m[i]); }
-    while (digits.size() > 1 && digits.back() == '0') digits.pop_back();
-    std::string o = neg ? "-" : "";
-    const float av = std::fabs(v);
-    if (av >= 1e-3f && av < 1e7f) {
-        if (e10 >= 0) {
-            std::string ip = digits.substr(0, std::min(digits.size(), (size_t)e10 + 1));
-            while ((int)ip.size() < e10 + 1) ip.push_back('0');
-            o += ip + "." + (digits.size() > (size_t)e10 + 1 ? digits.substr((size_t)e10 + 1) : "0");
-        } else o += "0." + std::string((size_t)(-e10 - 1), '0') + digits;
-    } else o += digits.substr(0, 1) + "." + (digits.size() > 1 ? digits.substr(1) : "0") + "E" + std::to_string(e10);
-    return o;
-}
 
 // :165-166, :200-225.  Java int arithmetic (it wraps) and float division: 0/0 is NaN, x/0 an infinity
 BenchmarkRatios benchmark_ratios(const ps_benchmark_stats &st)
@@ -273,8 +224,7 @@ struct BmTimes { double read = 0, decode = 0, copy = 0, k_fastq = 0, k_records =
 
 void benchmark_run(const char *mapping_path, const char *out_path, const char *reads_path, int device, ps_benchmark_stats *stats)
 {
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
+    using clk = HostClock;
     const std::string who = "ps_benchmark_reads: ";
     if (!mapping_path || !mapping_path[0] || !out_path || !out_path[0] || !reads_path || !reads_path[0])
         throw Error(who + "mapping file, statistics file and reads file are required");
@@ -293,10 +243,8 @@ void benchmark_run(const char *mapping_path, const char *out_path, const char *r
     if (B.n() > (size_t)INT_MAX) throw Error(who + "more than 2^31 - 1 records");
     tm.read = ms_since(t0);
 
-    hipStream_t s; PS_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct SG { hipStream_t s; ~SG() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } sg{s};
+    StreamGuard sg; hipStream_t s = sg.s;
     struct Drain { hipStream_t s; ~Drain() { (void)hipStreamSynchronize(s); } };   // declared behind buffers a copy may still read: runs before they are let go
-    struct Ev { hipEvent_t e = nullptr; ~Ev() { if (e) (void)hipEventDestroy(e); } void make() { PS_HIP(hipEventCreate(&e)); } };
 
     // ---- pass 1: the FASTQ in pieces through two page-locked buffers; one piece is copied and counted while the next is staged
     DevBuf<unsigned long long> d_cnt1; d_cnt1.alloc(4);
@@ -305,15 +253,11 @@ void benchmark_run(const char *mapping_path, const char *out_path, const char *r
         d_cnt1.upload(init, 4, s); PS_HIP(hipStreamSynchronize(s));
     }
     {
-        PinBuf pin[2]; DevBuf<uint8_t> dev[2]; Ev ev[2][3]; bool used[2] = {false, false};   // events: before the copy, between copy and kernel, after the kernel
+        PinBuf pin[2]; DevBuf<uint8_t> dev[2]; EventPair ev_copy[2], ev_kernel[2]; bool used[2] = {false, false};
         Drain drain{s};                                                    // an error below unwinds pin[]: no copy may be in flight then
-        for (int k = 0; k < 2; ++k) for (int e = 0; e < 3; ++e) ev[k][e].make();
         auto retire = [&](int k) {
             if (!used[k]) return;
-            PS_HIP(hipEventSynchronize(ev[k][2].e));
-            float ms_copy = 0, ms_kernel = 0;
-            PS_HIP(hipEventElapsedTime(&ms_copy, ev[k][0].e, ev[k][1].e)); PS_HIP(hipEventElapsedTime(&ms_kernel, ev[k][1].e, ev[k][2].e));
-            tm.copy += ms_copy; tm.k_fastq += ms_kernel; used[k] = false;
+            tm.k_fastq += ev_kernel[k].ms(); tm.copy += ev_copy[k].ms(); used[k] = false;   // the kernel is the later of the two
         };
         int prev = -1; size_t k = 0;
         for (size_t off = 0; off < fq.n; off += piece, ++k) {
@@ -331,13 +275,13 @@ void benchmark_run(const char *mapping_path, const char *out_path, const char *r
             std::memcpy(h, fq.p + off, avail);
             tm.read += ms_since(r0);
             if (dev[slot].n < avail) dev[slot].alloc(avail + avail / 8);
-            PS_HIP(hipEventRecord(ev[slot][0].e, s));
+            ev_copy[slot].start(s);
             PS_HIP(hipMemcpyAsync(dev[slot].p, h, avail, hipMemcpyHostToDevice, s));
-            PS_HIP(hipEventRecord(ev[slot][1].e, s));
+            ev_copy[slot].stop(s); ev_kernel[slot].start(s);
             hipLaunchKernelGGL(k_bm_fastq, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, s, dev[slot].p, (uint32_t)len, (uint32_t)avail, prev,
                                (unsigned long long)off, d_cnt1.p, d_cnt1.p + 3);
             PS_HIP(hipGetLastError());
-            PS_HIP(hipEventRecord(ev[slot][2].e, s));
+            ev_kernel[slot].stop(s);
             used[slot] = true;
             prev = fq.p[off + len - 1];
         }
@@ -358,26 +302,8 @@ void benchmark_run(const char *mapping_path, const char *out_path, const char *r
     t0 = clk::now();
     const int n = (int)B.n(); const size_t nn = (size_t)std::max(1, n), n_ref = B.refs.size();
     st.n_records = (uint64_t)n;
-    std::vector<uint64_t> name_off(nn); std::vector<uint8_t> name_len(nn); std::vector<int32_t> ref(nn), aln_start(nn);
-    std::vector<uint32_t> flag(nn), cig_off(nn), n_cig(nn);
-    auto le32 = [](const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); };
-    uint64_t n_name = 0, n_words = 0;
-    for (int j = 0; j < n; ++j) {
-        const BamRec &r = B.recs[(size_t)j]; const uint8_t *p = B.rec((size_t)j);
-        if (r.ref < -1 || r.ref >= (int32_t)n_ref) throw Error(who + "record " + std::to_string(j + 1) + " refers to a reference that is not in the header");
-        if (p[12] < 1 || 36 + (size_t)p[12] + 4 * (size_t)(le32(p + 16) & 0xffff) > r.len) throw Error(who + "corrupt record " + std::to_string(j + 1));
-        ref[(size_t)j] = r.ref; aln_start[(size_t)j] = (int32_t)((uint32_t)r.pos + 1u); flag[(size_t)j] = r.flag;
-        name_len[(size_t)j] = (uint8_t)(p[12] - 1); n_cig[(size_t)j] = le32(p + 16) & 0xffff;
-        name_off[(size_t)j] = n_name; cig_off[(size_t)j] = (uint32_t)n_words;
-        n_name += name_len[(size_t)j]; n_words += n_cig[(size_t)j];
-    }
-    if (n_words > (uint64_t)UINT_MAX) throw Error(who + "more than 2^32 CIGAR operations");
-    std::vector<uint8_t> names((size_t)std::max<uint64_t>(1, n_name)); std::vector<uint32_t> cigar((size_t)std::max<uint64_t>(1, n_words));
-    for (int j = 0; j < n; ++j) {
-        const uint8_t *p = B.rec((size_t)j), *cg = p + 36 + p[12];
-        if (name_len[(size_t)j]) std::memcpy(&names[(size_t)name_off[(size_t)j]], p + 36, name_len[(size_t)j]);
-        for (uint32_t k = 0; k < n_cig[(size_t)j]; ++k) cigar[cig_off[(size_t)j] + k] = le32(cg + 4 * k);
-    }
+    RecTable R;
+    try { flatten_records(B, kRecCigar | kRecNames, nullptr, 8, R); } catch (const std::exception &e) { throw Error(who + e.what()); }
     std::vector<uint32_t> ref_off(n_ref + 1), ref_len(n_ref + 1); std::vector<uint8_t> ref_chr(n_ref + 1, 0), ref_names;
     for (size_t r = 0; r <= n_ref; ++r) {                                  // entry n_ref: "*", the name of no reference
         const std::string nm = r < n_ref ? B.refs[r].first : std::string("*");
@@ -388,11 +314,10 @@ void benchmark_run(const char *mapping_path, const char *out_path, const char *r
     tm.decode = ms_since(t0);
 
     t0 = clk::now();
-    auto up = [&](auto &d, const auto &v) { d.alloc(v.size()); d.upload(v.data(), v.size(), s); };
-    DevBuf<uint64_t> d_noff; DevBuf<uint8_t> d_nlen, d_names, d_rnames, d_rchr, d_cls; DevBuf<int32_t> d_ref, d_as, d_start, d_end;
-    DevBuf<uint32_t> d_flag, d_coff, d_nc, d_cig, d_roff, d_rlen, d_truth; DevBuf<unsigned> d_first; DevBuf<unsigned long long> d_cnt2;
-    up(d_noff, name_off); up(d_nlen, name_len); up(d_names, names); up(d_ref, ref); up(d_as, aln_start); up(d_flag, flag);
-    up(d_coff, cig_off); up(d_nc, n_cig); up(d_cig, cigar); up(d_roff, ref_off); up(d_rlen, ref_len); up(d_rnames, ref_names); up(d_rchr, ref_chr);
+    DevRecTable d; DevBuf<uint8_t> d_rnames, d_rchr, d_cls; DevBuf<int32_t> d_start, d_end;
+    DevBuf<uint32_t> d_roff, d_rlen, d_truth; DevBuf<unsigned> d_first; DevBuf<unsigned long long> d_cnt2;
+    d.upload(R, s);
+    upload(d_roff, ref_off, s); upload(d_rlen, ref_len, s); upload(d_rnames, ref_names, s); upload(d_rchr, ref_chr, s);
     d_start.alloc(nn); d_end.alloc(nn); d_truth.alloc(nn); d_cls.alloc(nn); d_first.alloc(3); d_cnt2.alloc(kBmCounters);
     const unsigned none[3] = {kBmNone, kBmNone, kBmNone};
     d_first.upload(none, 3, s); d_cnt2.zero(s);
@@ -401,8 +326,8 @@ void benchmark_run(const char *mapping_path, const char *out_path, const char *r
 
     t0 = clk::now();
     BmRecs a;
-    a.n = n; a.name_off = d_noff.p; a.name_len = d_nlen.p; a.names = d_names.p; a.ref = d_ref.p; a.aln_start = d_as.p; a.flag = d_flag.p;
-    a.cig_off = d_coff.p; a.n_cig = d_nc.p; a.cigar = d_cig.p; a.n_ref = (int)n_ref; a.ref_off = d_roff.p; a.ref_len = d_rlen.p;
+    a.n = n; a.name_off = d.name_off.p; a.name_len = d.name_len.p; a.names = d.names.p; a.ref = d.ref.p; a.pos = d.pos.p; a.flag = d.flag.p;
+    a.cig_off = d.cig_off.p; a.n_cig = d.n_cig.p; a.cigar = d.cigar.p; a.n_ref = (int)n_ref; a.ref_off = d_roff.p; a.ref_len = d_rlen.p;
     a.ref_names = d_rnames.p; a.ref_chr = d_rchr.p; a.start = d_start.p; a.end = d_end.p; a.truth = d_truth.p; a.cls = d_cls.p;
     unsigned first[3] = {kBmNone, kBmNone, kBmNone};
     if (n) {
@@ -435,10 +360,7 @@ void benchmark_run(const char *mapping_path, const char *out_path, const char *r
     const BenchmarkRatios rt = benchmark_ratios(st);
     const std::string text = benchmark_text(st, rt);
     st.precision = rt.precision; st.recall = rt.recall; st.accuracy = rt.accuracy;
-    FILE *f = std::fopen(out_path, "wb");
-    if (!f) throw Error(who + "cannot write " + out_path);
-    const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
-    if (std::fclose(f) != 0 || !ok) { std::remove(out_path); throw Error(who + "cannot write " + out_path); }
+    try { write_text_file(out_path, text, true); } catch (const std::exception &e) { throw Error(who + e.what()); }
     tm.write = ms_since(t0);
     if (stats) *stats = st;
     if (std::getenv("PS_VERBOSE"))

@@ -19,16 +19,14 @@
 #include <hipcub/hipcub.hpp>
 #include <zlib.h>
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cstdio>
 #include <cstring>
-#include <map>
 #include <thread>
 #include <unordered_map>
 #include "../../include/parasuite_hip.h"
-#include "ps_host.h"
-#include "ps_bam.h"
+#include "ps_dev.h"
+#include "ps_java.h"
 #include "ps_pacref.h"
 
 namespace ps {
@@ -51,7 +49,7 @@ __global__ void k_cl_classify(int n, const uint32_t *flag, const int32_t *ref, c
     for (int c = 0; c < (int)n_cig[r]; ++c) {
         const int op = (int)(cg[c] & 15u), len = (int)(cg[c] >> 4);
         has_i |= op == 1; has_d |= op == 2; has_n |= op == 3;
-        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += len;
+        if (cigar_on_ref(op)) span += len;
         if (op == 0 || op == 7 || op == 8) { bases += len; over |= rp + len > l_seq[r]; }
         if (op == 0 || op == 1 || op == 4 || op == 7 || op == 8) rp += len;
     }
@@ -164,7 +162,7 @@ __global__ void __launch_bounds__(256) k_cl_count(ClCountArgs a)
             for (int z = 0; z < len; ++z, ++u) {
                 const int pr = rf.at(g1 + gp + z);
                 const uint64_t b = sb + (uint64_t)(rp + z);
-                const int nib = (a.seq[b >> 1] >> ((~b & 1u) << 2)) & 15;
+                const int nib = bam_nibble(a.seq, b);
                 const int i = rev ? B - 1 - u : u, p = rev ? e - i : s + i;
                 if (p < lo || p > hi) continue;                              // never: [start, end] lies in the window
                 const unsigned long long at = base + (unsigned long long)(p - lo);
@@ -317,16 +315,6 @@ __global__ void __launch_bounds__(64 * (kSfLoaders + 1)) k_cl_sitefreq(const int
 
 // ---- host side
 
-template <class F> static void cub_call(hipStream_t s, F f)
-{
-    size_t bytes = 0;
-    PS_HIP(f(nullptr, bytes));
-    DevBuf<uint8_t> tmp; tmp.alloc(std::max<size_t>(bytes, 1));
-    PS_HIP(f((void *)tmp.p, bytes));
-    PS_HIP(hipStreamSynchronize(s));
-}
-static inline unsigned blocks_for(size_t n, unsigned per = 256) { return (unsigned)std::max<size_t>(1, (n + per - 1) / per); }
-
 // the whole FASTA as stored (soft-masked lower case kept): first word of the header -> bases
 static std::unordered_map<std::string, std::string> cl_read_fasta(const char *path)
 {
@@ -410,45 +398,32 @@ struct ClResult {
 
 static void pileup_clusters(const char *mapping, const char *ref_fa, const char *vcf, int min_cov, int device, int threads, ClResult &res)
 {
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
     require_device(device);
-    auto t0 = clk::now();
-    AlnTable t;
-    try { load_alignments(mapping, threads, t, false); } catch (const std::exception &e) { throw Error(e.what()); }
+    auto t0 = HostClock::now();
+    RecTable t;
+    try { load_rec_table(mapping, kRecCigar | kRecSeq, threads, t); } catch (const std::exception &e) { throw Error(e.what()); }
     if (t.sort_order != "coordinate")                                  // :85-92
         throw Error(std::string("ps_pileup_clusters: ") + mapping + " is not sorted by coordinate: its header says SO:" +
                     (t.sort_order.empty() ? "(none)" : t.sort_order) + ", SO:coordinate is required");
     if (t.n() > (size_t)INT_MAX) throw Error("ps_pileup_clusters: more than 2^31 records");
     res.ms_parse = ms_since(t0);
-    t0 = clk::now();
+    t0 = HostClock::now();
     const std::vector<unsigned long long> snp = cl_read_vcf(vcf, t.refs);
     res.ms_vcf = ms_since(t0);
 
-    t0 = clk::now();
-    hipStream_t s; PS_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct SG { hipStream_t s; ~SG() { (void)hipStreamDestroy(s); } } sg{s};
+    t0 = HostClock::now();
+    StreamGuard sg; hipStream_t s = sg.s;
     Index ix;
     index_load_pac(ref_fa, ix, s);
-    std::map<std::string, int> cid_of;
-    for (size_t c = 0; c < ix.ref.contigs.size(); ++c) cid_of[ix.ref.contigs[c].name] = (int)c;
-    std::vector<int32_t> ref_to_contig(std::max<size_t>(1, t.refs.size()), -1), clen(std::max<size_t>(1, ix.ref.contigs.size()));
-    std::vector<int64_t> coff(clen.size(), 0);
-    for (size_t r = 0; r < t.refs.size(); ++r) { auto it = cid_of.find(t.refs[r].first); if (it != cid_of.end()) ref_to_contig[r] = it->second; }
-    for (size_t c = 0; c < ix.ref.contigs.size(); ++c) { clen[c] = ix.ref.contigs[c].len; coff[c] = ix.ref.contigs[c].offset; }
-    std::vector<int64_t> hoff(ix.ref.holes.size()); std::vector<int32_t> hlen(ix.ref.holes.size());
-    for (size_t h = 0; h < ix.ref.holes.size(); ++h) { hoff[h] = ix.ref.holes[h].offset; hlen[h] = ix.ref.holes[h].len; }
-
+    const RefTables rt(ix, s);
+    const std::vector<int32_t> ref_to_contig = RefTables::ref_to_contig(ix, t.refs);
     const int n = (int)t.n();
-    auto up = [&](auto &d, const auto &v) { d.alloc(std::max<size_t>(1, v.size())); if (!v.empty()) d.upload(v.data(), v.size(), s); };
-    DevBuf<uint32_t> d_flag, d_coff, d_nc, d_cig; DevBuf<int32_t> d_ref, d_pos, d_lseq, d_r2c, d_clen, d_hlen; DevBuf<int64_t> d_ctgoff, d_hoff;
-    DevBuf<uint64_t> d_soff; DevBuf<uint8_t> d_seq; DevBuf<unsigned long long> d_snp;
-    up(d_flag, t.flag); up(d_ref, t.ref); up(d_pos, t.pos); up(d_lseq, t.l_seq); up(d_coff, t.cig_off); up(d_nc, t.n_cig); up(d_cig, t.cigar);
-    up(d_soff, t.seq_off); up(d_seq, t.seq); up(d_r2c, ref_to_contig); up(d_clen, clen); up(d_ctgoff, coff); up(d_hoff, hoff); up(d_hlen, hlen); up(d_snp, snp);
+    DevRecTable d; DevBuf<int32_t> d_r2c; DevBuf<unsigned long long> d_snp;
+    d.upload(t, s); upload(d_r2c, ref_to_contig, s); upload(d_snp, snp, s);
     DevBuf<uint8_t> d_keep; DevBuf<int32_t> d_start, d_end; DevBuf<unsigned long long> d_cnt; DevBuf<unsigned> d_err;
     d_keep.alloc(std::max(1, n)); d_start.alloc(std::max(1, n)); d_end.alloc(std::max(1, n)); d_cnt.alloc(3); d_cnt.zero(s); d_err.alloc(1); d_err.zero(s);
-    if (n) hipLaunchKernelGGL(k_cl_classify, dim3(blocks_for(n)), dim3(256), 0, s, n, d_flag.p, d_ref.p, d_pos.p, d_lseq.p, d_coff.p, d_nc.p, d_cig.p,
-                              d_r2c.p, (int)t.refs.size(), d_clen.p, d_keep.p, d_start.p, d_end.p, d_cnt.p, d_err.p);
+    if (n) hipLaunchKernelGGL(k_cl_classify, dim3(blocks_for(n)), dim3(256), 0, s, n, d.flag.p, d.ref.p, d.pos.p, d.l_seq.p, d.cig_off.p, d.n_cig.p, d.cigar.p,
+                              d_r2c.p, (int)t.refs.size(), rt.contig_len.p, d_keep.p, d_start.p, d_end.p, d_cnt.p, d_err.p);
     PS_HIP(hipGetLastError());
     DevBuf<int32_t> d_kidx; DevBuf<int> d_nsel; d_kidx.alloc(std::max(1, n)); d_nsel.alloc(1); d_nsel.zero(s);
     if (n) cub_call(s, [&](void *tmp, size_t &b) { return hipcub::DeviceSelect::Flagged(tmp, b, hipcub::CountingInputIterator<int32_t>(0), d_keep.p, d_kidx.p, d_nsel.p, n, s); });
@@ -469,7 +444,7 @@ static void pileup_clusters(const char *mapping, const char *ref_fa, const char 
     d_open.alloc(Kn); d_cid.alloc(Kn); d_key.alloc(Kn); d_mx.alloc(Kn);
     int C = 0;
     if (K) {
-        hipLaunchKernelGGL(k_cl_gather, dim3(blocks_for(K)), dim3(256), 0, s, K, d_kidx.p, d_start.p, d_end.p, d_flag.p, d_ref.p, d_sk.p, d_ek.p, d_rv.p, d_rk.p, d_head.p);
+        hipLaunchKernelGGL(k_cl_gather, dim3(blocks_for(K)), dim3(256), 0, s, K, d_kidx.p, d_start.p, d_end.p, d.flag.p, d.ref.p, d_sk.p, d_ek.p, d_rv.p, d_rk.p, d_head.p);
         cub_call(s, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::InclusiveSum(tmp, b, d_head.p, d_seg.p, K, s); });
         hipLaunchKernelGGL(k_cl_key, dim3(blocks_for(K)), dim3(256), 0, s, K, d_seg.p, d_ek.p, d_key.p);
         cub_call(s, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::InclusiveScan(tmp, b, d_key.p, d_mx.p, hipcub::Max(), K, s); });
@@ -508,9 +483,9 @@ static void pileup_clusters(const char *mapping, const char *ref_fa, const char 
         d_cov.zero(s); d_t2c.zero(s);
         PS_HIP(hipMemsetAsync(d_first.p, 0xff, Tn * sizeof(unsigned long long), s));
         ClCountArgs a;
-        a.K = K; a.kidx = d_kidx.p; a.cid = d_cid.p; a.sk = d_sk.p; a.ek = d_ek.p; a.rv = d_rv.p; a.ref = d_ref.p; a.ref_to_contig = d_r2c.p; a.contig_off = d_ctgoff.p;
-        a.cig_off = d_coff.p; a.n_cig = d_nc.p; a.cigar = d_cig.p; a.seq_off = d_soff.p; a.seq = d_seq.p;
-        a.pac = ix.pac.p; a.hole_off = d_hoff.p; a.hole_len = d_hlen.p; a.n_holes = (int)hoff.size();
+        a.K = K; a.kidx = d_kidx.p; a.cid = d_cid.p; a.sk = d_sk.p; a.ek = d_ek.p; a.rv = d_rv.p; a.ref = d.ref.p; a.ref_to_contig = d_r2c.p; a.contig_off = rt.contig_off.p;
+        a.cig_off = d.cig_off.p; a.n_cig = d.n_cig.p; a.cigar = d.cigar.p; a.seq_off = d.seq_off.p; a.seq = d.seq.p;
+        a.pac = ix.pac.p; a.hole_off = rt.hole_off.p; a.hole_len = rt.hole_len.p; a.n_holes = rt.n_holes;
         a.lo = d_lo.p; a.hi = d_hi.p; a.off = d_off.p; a.cov = d_cov.p; a.t2c = d_t2c.p; a.first = d_first.p; a.cflags = d_cflags.p; a.ct2c = d_ct2c.p; a.beyond = d_beyond.p;
         hipLaunchKernelGGL(k_cl_count, dim3(blocks_for(K)), dim3(256), 0, s, a);
         hipLaunchKernelGGL(k_cl_nsites, dim3(C), dim3(64), 0, s, d_off.p, d_w.p, d_t2c.p, d_nsites.p);
@@ -559,7 +534,7 @@ static void pileup_clusters(const char *mapping, const char *ref_fa, const char 
     std::vector<double> afreq((size_t)kmax, 0.0);
     if (kmax) {
         DevBuf<int32_t> d_xl; DevBuf<double> d_acc;
-        up(d_xl, xl); d_acc.alloc((size_t)kmax);
+        upload(d_xl, xl, s); d_acc.alloc((size_t)kmax);
         hipLaunchKernelGGL(k_cl_sitefreq, dim3(blocks_for(kmax, 64)), dim3(64 * (kSfLoaders + 1)), 0, s, d_xl.p, (int)xl.size(), d_off.p, d_res.p, d_sorted.p, kmax, d_acc.p);
         PS_HIP(hipGetLastError());
         d_acc.download(afreq.data(), (size_t)kmax, s);
@@ -568,7 +543,7 @@ static void pileup_clusters(const char *mapping, const char *ref_fa, const char 
     res.ms_kernels = ms_since(t0);
 
     // text: the cluster and CCR sequences from the FASTA bytes (:262-343, :367-487)
-    t0 = clk::now();
+    t0 = HostClock::now();
     const auto fasta = cl_read_fasta(ref_fa);
     std::vector<const std::string *> ref_seq(t.refs.size(), nullptr);
     for (size_t r = 0; r < t.refs.size(); ++r) { auto it = fasta.find(t.refs[r].first); if (it != fasta.end()) ref_seq[r] = &it->second; }
@@ -601,9 +576,7 @@ static void pileup_clusters(const char *mapping, const char *ref_fa, const char 
                     const int rr = kidx[(size_t)j];
                     const int64_t st_j = (int64_t)t.pos[(size_t)rr] + 1;
                     const uint32_t *cg = t.cigar.data() + t.cig_off[(size_t)rr];
-                    int64_t span = 0;
-                    for (uint32_t k = 0; k < t.n_cig[(size_t)rr]; ++k) { const int op = (int)(cg[k] & 15u); if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) span += cg[k] >> 4; }
-                    const int64_t en_j = st_j + span - 1;
+                    const int64_t en_j = st_j + cigar_ref_span(cg, t.n_cig[(size_t)rr]) - 1;
                     int64_t cbs = st_j;
                     if (j == j0) {
                         for (uint32_t k = 0; k < t.n_cig[(size_t)rr]; ++k) {
@@ -673,14 +646,6 @@ static void pileup_clusters(const char *mapping, const char *ref_fa, const char 
     res.ms_text = ms_since(t0);
 }
 
-static void cl_write(const std::string &path, const std::string &text)
-{
-    FILE *f = std::fopen(path.c_str(), "wb");
-    if (!f) throw Error("cannot write " + path);
-    const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
-    if (std::fclose(f) != 0 || !ok) throw Error("cannot write " + path);
-}
-
 void pileup_clusters_run(const char *mapping, const char *ref_fa, const char *out_file, const char *snp_vcf, int min_cov,
                          const char *site_prefix, int device, ps_cluster_stats *stats)
 {
@@ -688,10 +653,10 @@ void pileup_clusters_run(const char *mapping, const char *ref_fa, const char *ou
     ClResult r;
     pileup_clusters(mapping, ref_fa, snp_vcf, min_cov, device, 8, r);
     const std::string out = out_file, sp = site_prefix && site_prefix[0] ? site_prefix : mapping;
-    const auto t0 = std::chrono::steady_clock::now();
-    cl_write(out, r.out); cl_write(out + ".ccr.fasta", r.fasta); cl_write(out + ".ccr.tsv", r.tsv); cl_write(out + ".report", r.report);
-    cl_write(sp + ".sitefrequency.tsv", r.sitefreq); cl_write(sp + ".sitepositions.tsv", r.sitepos);
-    r.ms_text += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const auto t0 = HostClock::now();
+    write_text_file(out, r.out); write_text_file(out + ".ccr.fasta", r.fasta); write_text_file(out + ".ccr.tsv", r.tsv); write_text_file(out + ".report", r.report);
+    write_text_file(sp + ".sitefrequency.tsv", r.sitefreq); write_text_file(sp + ".sitepositions.tsv", r.sitepos);
+    r.ms_text += ms_since(t0);
     if (stats) *stats = r.st;
     if (std::getenv("PS_VERBOSE"))
         std::fprintf(stderr, "[parasuite-hip] ps_pileup_clusters: %llu records, %llu kept, %llu clusters, %llu written, %llu crosslinked; "

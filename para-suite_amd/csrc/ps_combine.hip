@@ -17,15 +17,15 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 #include <algorithm>
-#include <chrono>
 #include <climits>
 #include <cstdio>
 #include <cstring>
 #include <thread>
 #include <unordered_map>
 #include "../../include/parasuite_hip.h"
-#include "ps_host.h"
-#include "ps_bam.h"
+#include "ps_dev.h"
+#include "ps_java.h"
+#include "ps_pacref.h"
 
 namespace ps {
 
@@ -34,7 +34,7 @@ enum : int { kCbNone = 0, kCbEmpty = 1, kCbEmit = 2, kCbAmbiguous = 3, kCbNoCont
 constexpr int kCbNoRef = -2;                                                                  // genome contig of a transcript: absent (-1: MT without chrM)
 
 struct CbLiftArgs {
-    int n; const int32_t *ctg, *aln_start, *l_seq; const uint32_t *flag, *cig_off, *n_cig, *cigar;
+    int n; const int32_t *ctg, *pos, *l_seq; const uint32_t *flag, *cig_off, *n_cig, *cigar;
     const uint32_t *ex_off; const int32_t *ex_n, *strand, *es, *ee;
     uint32_t *status; int32_t *start; unsigned long long *nwords;       // pass 0 writes these, pass 1 reads nwords
     const unsigned long long *woff; uint32_t *words;                    // pass 1
@@ -55,9 +55,9 @@ __global__ void __launch_bounds__(256) k_cb_lift(CbLiftArgs a)
     for (int k = 0; k < n_own; ++k) {
         const int op = (int)(own[k] & 15u);
         has_id |= op == 1 || op == 2; own_n |= op == 3;
-        if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += (int)(own[k] >> 4);
+        if (cigar_on_ref(op)) ref_len += (int)(own[k] >> 4);
     }
-    const int aln_start = a.aln_start[j], read_len = a.l_seq[j];
+    const int aln_start = (int32_t)((uint32_t)a.pos[j] + 1u), read_len = a.l_seq[j];   // htsjdk getAlignmentStart
     const int aln_end = (a.flag[j] & 4u) ? 0 : aln_start + ref_len - 1;       // getAlignmentEnd: 0 for an unmapped (bridging) record
     const int total = WRITE ? (int)a.nwords[j] : 0;
     uint32_t *out = WRITE ? a.words + a.woff[j] : nullptr;
@@ -119,7 +119,7 @@ __global__ void __launch_bounds__(256) k_cb_lift(CbLiftArgs a)
     a.nwords[j] = located ? (unsigned long long)k : 0ull;
 }
 
-__global__ void __launch_bounds__(256) k_cb_heads(int n, const uint64_t *name_off, const uint32_t *name_len, const uint8_t *names, uint32_t *head)
+__global__ void __launch_bounds__(256) k_cb_heads(int n, const uint64_t *name_off, const uint8_t *name_len, const uint8_t *names, uint32_t *head)
 {
     const int j = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (j >= n) return;
@@ -158,7 +158,6 @@ __global__ void __launch_bounds__(256) k_cb_groups(int n, const uint32_t *head, 
     gstat[j] = kCbEmit; emit[j] = e;
 }
 
-__device__ __forceinline__ unsigned cb_nib(const uint8_t *s, int i) { return (s[i >> 1] >> ((~i & 1) << 2)) & 15u; }
 __device__ __forceinline__ void cb_set_nib(uint8_t *s, int i, unsigned v)
 {
     const int sh = (~i & 1) << 2;
@@ -174,45 +173,23 @@ __global__ void __launch_bounds__(256) k_cb_revcomp(int n, const uint8_t *gstat,
     if (j >= n || gstat[j] != kCbEmit) return;
     const int e = emit[j];
     if (strand[ctg[e]] != 2) return;
-    uint8_t *s = seq + seq_off[e]; const int L = l_seq[e];
+    uint8_t *s = seq + (seq_off[e] >> 1); const int L = l_seq[e];
+    auto cb_nib = [s](int i) { return (unsigned)bam_nibble(s, (uint64_t)i); };
     for (int i = 0; i < L / 2; ++i) {
-        const unsigned x = cb_nib(s, i), y = cb_nib(s, L - 1 - i);
+        const unsigned x = cb_nib(i), y = cb_nib(L - 1 - i);
         cb_set_nib(s, i, cb_comp(y)); cb_set_nib(s, L - 1 - i, cb_comp(x));
     }
-    if (L & 1) cb_set_nib(s, L / 2, cb_comp(cb_nib(s, L / 2)));
+    if (L & 1) cb_set_nib(s, L / 2, cb_comp(cb_nib(L / 2)));
 }
 
 // ---- host side
 
-template <class F> static void cb_cub(hipStream_t s, F f)
+// an exon position of a transcript name: Integer.parseInt, except that more than ten digits are refused whatever they spell
+// (leading zeros, which parseInt takes): kept as it has been
+static bool cb_exon_int(const std::string &s, int32_t &v)
 {
-    size_t bytes = 0;
-    PS_HIP(f(nullptr, bytes));
-    DevBuf<uint8_t> tmp; tmp.alloc(std::max<size_t>(bytes, 1));
-    PS_HIP(f((void *)tmp.p, bytes));
-    PS_HIP(hipStreamSynchronize(s));
-}
-static inline unsigned cb_blocks(size_t n, unsigned per = 256) { return (unsigned)std::max<size_t>(1, (n + per - 1) / per); }
-
-// String.split(sep): trailing empty strings are dropped, an empty input is one empty string
-static std::vector<std::string> cb_java_split(const std::string &s, char sep)
-{
-    std::vector<std::string> out; size_t p = 0;
-    for (;;) { const size_t q = s.find(sep, p); if (q == std::string::npos) { out.push_back(s.substr(p)); break; } out.push_back(s.substr(p, q - p)); p = q + 1; }
-    if (s.empty()) return out;
-    while (!out.empty() && out.back().empty()) out.pop_back();
-    return out;
-}
-static bool cb_parse_int(const std::string &s, int32_t &v)                 // Integer.parseInt: sign, decimal digits, 32 bits
-{
-    size_t i = 0; bool neg = false;
-    if (i < s.size() && (s[i] == '-' || s[i] == '+')) { neg = s[i] == '-'; ++i; }
-    if (i >= s.size() || s.size() - i > 10) return false;
-    int64_t x = 0;
-    for (; i < s.size(); ++i) { if (s[i] < '0' || s[i] > '9') return false; x = x * 10 + (s[i] - '0'); }
-    if (neg) x = -x;
-    if (x < INT_MIN || x > INT_MAX) return false;
-    v = (int32_t)x; return true;
+    const size_t sign = !s.empty() && (s[0] == '-' || s[0] == '+');
+    return s.size() - sign <= 10 && java_parse_int((const uint8_t *)s.data(), (uint32_t)s.size(), v);
 }
 
 struct CbTimes { double parse = 0, tables = 0, h2d = 0, kernels = 0, d2h = 0, assemble = 0, write = 0; };
@@ -220,12 +197,11 @@ struct CbTimes { double parse = 0, tables = 0, h2d = 0, kernels = 0, d2h = 0, as
 void combine_run(const char *genome_path, const char *transcript_path, const char *out_bam, bool sort_by_coordinate, bool write_index,
                  int threads, int device, ps_combine_stats *stats)
 {
-    using clk = std::chrono::steady_clock;
     if (!genome_path || !transcript_path || !out_bam || !out_bam[0]) throw Error("ps_combine_genome_transcript: genomic mapping, transcript mapping and output file are required");
     if (same_file(out_bam, genome_path) || same_file(out_bam, transcript_path)) throw Error("ps_combine_genome_transcript: the output may not be one of the inputs");
     if (write_index && !sort_by_coordinate) throw Error("a .bai index needs coordinate-sorted output");
     require_device(device);                                                // before the files are read
-    const auto t0 = clk::now();
+    const auto t0 = HostClock::now();
     BamFile G, T;
     {
         std::string err;
@@ -234,8 +210,7 @@ void combine_run(const char *genome_path, const char *transcript_path, const cha
         other.join();
         if (!err.empty()) throw Error(err);
     }
-    combine_records(G, T, transcript_path, out_bam, sort_by_coordinate, write_index, threads, device, stats,
-                    std::chrono::duration<double, std::milli>(clk::now() - t0).count());
+    combine_records(G, T, transcript_path, out_bam, sort_by_coordinate, write_index, threads, device, stats, ms_since(t0));
 }
 
 // the same on records in memory (both are consumed): the files' loader above, or ps_map_route's passes, which hand over what they
@@ -244,12 +219,10 @@ void combine_run(const char *genome_path, const char *transcript_path, const cha
 void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const char *out_bam, bool sort_by_coordinate, bool write_index,
                      int threads, int device, ps_combine_stats *stats, double parse_ms)
 {
-    using clk = std::chrono::steady_clock;
-    auto ms_since = [](clk::time_point t) { return std::chrono::duration<double, std::milli>(clk::now() - t).count(); };
     threads = threads < 1 ? 1 : (threads > 64 ? 64 : threads);
     PS_HIP(hipSetDevice(device));
     CbTimes tm; ps_combine_stats st{};
-    auto t0 = clk::now();
+    auto t0 = HostClock::now();
     if (T.sort_order != "queryname")                                       // :85-94 (the Java logs this and exits with status 0)
         throw Error(std::string("ps_combine_genome_transcript: ") + transcript_path + " is not sorted by read name: its header says SO:" +
                     (T.sort_order.empty() ? "(none)" : T.sort_order) + ", SO:queryname is required");
@@ -258,7 +231,7 @@ void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const 
     tm.parse = parse_ms;
 
     // placed records (RNAME not '*', :105-107) as flat arrays; exon tables of the transcripts they name, parsed once each
-    t0 = clk::now();
+    t0 = HostClock::now();
     std::vector<int32_t> pidx; pidx.reserve(T.n());
     for (size_t i = 0; i < T.n(); ++i) { if (T.recs[i].ref < 0) ++st.n_unplaced; else pidx.push_back((int32_t)i); }
     const int n = (int)pidx.size();
@@ -276,15 +249,15 @@ void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const 
     for (size_t c = 0; c < T.refs.size(); ++c) {
         if (!used[c]) continue;
         const std::string &nm = T.refs[c].first;
-        const std::vector<std::string> f = cb_java_split(nm, '|');
+        const std::vector<std::string> f = java_split(nm, '|');
         if (f.size() < 6) throw Error("ps_combine_genome_transcript: transcript name " + nm + " has fewer than six '|' fields (Gene|Transcript|Chr|starts|ends|strand)");
-        std::vector<std::string> s = cb_java_split(f[3], ';'), e = cb_java_split(f[4], ';');
+        std::vector<std::string> s = java_split(f[3], ';'), e = java_split(f[4], ';');
         if (s.size() != e.size()) throw Error("ps_combine_genome_transcript: transcript name " + nm + " lists " + std::to_string(s.size()) + " exon starts and " + std::to_string(e.size()) + " exon ends");
         std::sort(s.begin(), s.end()); std::sort(e.begin(), e.end());      // Arrays.sort(String[]): byte order, "100000" before "99990"
         ex_off[c] = (uint32_t)es.size(); ex_n[c] = (int32_t)s.size();
         for (size_t k = 0; k < s.size(); ++k) {
             int32_t a = 0, b = 0;
-            if (!cb_parse_int(s[k], a) || !cb_parse_int(e[k], b)) throw Error("ps_combine_genome_transcript: transcript name " + nm + " has an exon position that is not a number");
+            if (!cb_exon_int(s[k], a) || !cb_exon_int(e[k], b)) throw Error("ps_combine_genome_transcript: transcript name " + nm + " has an exon position that is not a number");
             es.push_back(a); ee.push_back(b);
         }
         strand[c] = f[5] == "1" ? 1 : (f[5] == "-1" ? 2 : 0);
@@ -294,63 +267,34 @@ void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const 
         else gref[c] = first;
     }
     if (es.size() > (size_t)UINT_MAX) throw Error("ps_combine_genome_transcript: more than 2^32 exons");
-    std::vector<int32_t> ctg((size_t)n), aln_start((size_t)n), l_seq((size_t)n); std::vector<uint32_t> flag((size_t)n), cig_off((size_t)n), n_cig((size_t)n), name_len((size_t)n);
-    std::vector<uint64_t> name_off((size_t)n), seq_off((size_t)n);
-    uint64_t n_words = 0, n_name = 0, n_seq = 0;
-    auto le32 = [](const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); };
-    for (int j = 0; j < n; ++j) {
-        const size_t i = (size_t)pidx[(size_t)j]; const uint8_t *p = T.rec(i);
-        ctg[(size_t)j] = T.recs[i].ref; aln_start[(size_t)j] = T.recs[i].pos + 1; flag[(size_t)j] = T.recs[i].flag;
-        name_len[(size_t)j] = (uint32_t)p[12] - 1; n_cig[(size_t)j] = le32(p + 16) & 0xffff; l_seq[(size_t)j] = (int32_t)le32(p + 20);
-        cig_off[(size_t)j] = (uint32_t)n_words; name_off[(size_t)j] = n_name; seq_off[(size_t)j] = n_seq;
-        n_words += n_cig[(size_t)j]; n_name += name_len[(size_t)j]; n_seq += ((uint64_t)l_seq[(size_t)j] + 1) / 2;
-    }
-    if (n_words > (uint64_t)UINT_MAX) throw Error("ps_combine_genome_transcript: more than 2^32 CIGAR operations");
-    std::vector<uint32_t> cigar((size_t)n_words); std::vector<uint8_t> names((size_t)n_name), seq((size_t)n_seq);
-    {
-        const int W = threads;
-        std::vector<std::thread> th;
-        auto fill = [&](int w) {
-            for (int j = (int)((int64_t)n * w / W); j < (int)((int64_t)n * (w + 1) / W); ++j) {
-                const uint8_t *p = T.rec((size_t)pidx[(size_t)j]);
-                const uint8_t *cg = p + 36 + p[12];
-                if (name_len[(size_t)j]) std::memcpy(&names[(size_t)name_off[(size_t)j]], p + 36, name_len[(size_t)j]);
-                for (uint32_t k = 0; k < n_cig[(size_t)j]; ++k) cigar[cig_off[(size_t)j] + k] = le32(cg + 4 * k);
-                if (l_seq[(size_t)j]) std::memcpy(&seq[(size_t)seq_off[(size_t)j]], cg + 4 * (size_t)n_cig[(size_t)j], (size_t)(l_seq[(size_t)j] + 1) / 2);
-            }
-        };
-        for (int w = 1; w < W; ++w) th.emplace_back(fill, w);
-        fill(0);
-        for (auto &x : th) x.join();
-    }
+    RecTable R;
+    try { flatten_records(T, kRecCigar | kRecSeq | kRecNames, &pidx, threads, R); } catch (const std::exception &e) { throw Error(std::string("ps_combine_genome_transcript: ") + e.what()); }
+    const std::vector<int32_t> &ctg = R.ref, &l_seq = R.l_seq; const std::vector<uint32_t> &flag = R.flag, &n_cig = R.n_cig;
+    std::vector<uint8_t> &seq = R.seq;
     tm.tables = ms_since(t0);
 
     // device
-    t0 = clk::now();
-    hipStream_t s; PS_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct SG { hipStream_t s; ~SG() { (void)hipStreamDestroy(s); } } sg{s};
-    auto up = [&](auto &d, const auto &v) { d.alloc(std::max<size_t>(1, v.size())); if (!v.empty()) d.upload(v.data(), v.size(), s); };
-    DevBuf<int32_t> d_ctg, d_as, d_lseq, d_exn, d_strand, d_es, d_ee, d_gref; DevBuf<uint32_t> d_flag, d_coff, d_nc, d_cig, d_exoff, d_nlen;
-    DevBuf<uint64_t> d_noff, d_soff; DevBuf<uint8_t> d_names, d_seq;
-    up(d_ctg, ctg); up(d_as, aln_start); up(d_lseq, l_seq); up(d_flag, flag); up(d_coff, cig_off); up(d_nc, n_cig); up(d_cig, cigar);
-    up(d_exoff, ex_off); up(d_exn, ex_n); up(d_strand, strand); up(d_es, es); up(d_ee, ee); up(d_gref, gref);
-    up(d_nlen, name_len); up(d_noff, name_off); up(d_names, names); up(d_soff, seq_off); up(d_seq, seq);
+    t0 = HostClock::now();
+    StreamGuard sg; hipStream_t s = sg.s;
+    DevRecTable d; DevBuf<int32_t> d_exn, d_strand, d_es, d_ee, d_gref; DevBuf<uint32_t> d_exoff;
+    d.upload(R, s);
+    upload(d_exoff, ex_off, s); upload(d_exn, ex_n, s); upload(d_strand, strand, s); upload(d_es, es, s); upload(d_ee, ee, s); upload(d_gref, gref, s);
     const size_t nn = (size_t)std::max(1, n);
     DevBuf<uint32_t> d_status, d_head, d_words; DevBuf<int32_t> d_start, d_emit; DevBuf<unsigned long long> d_nw, d_woff; DevBuf<uint8_t> d_gstat;
     d_status.alloc(nn); d_head.alloc(nn); d_start.alloc(nn); d_emit.alloc(nn); d_nw.alloc(nn); d_woff.alloc(nn); d_gstat.alloc(nn);
     PS_HIP(hipStreamSynchronize(s));
     tm.h2d = ms_since(t0);
 
-    t0 = clk::now();
+    t0 = HostClock::now();
     unsigned long long total_words = 0;
     if (n) {
         CbLiftArgs a;
-        a.n = n; a.ctg = d_ctg.p; a.aln_start = d_as.p; a.l_seq = d_lseq.p; a.flag = d_flag.p; a.cig_off = d_coff.p; a.n_cig = d_nc.p; a.cigar = d_cig.p;
+        a.n = n; a.ctg = d.ref.p; a.pos = d.pos.p; a.l_seq = d.l_seq.p; a.flag = d.flag.p; a.cig_off = d.cig_off.p; a.n_cig = d.n_cig.p; a.cigar = d.cigar.p;
         a.ex_off = d_exoff.p; a.ex_n = d_exn.p; a.strand = d_strand.p; a.es = d_es.p; a.ee = d_ee.p;
         a.status = d_status.p; a.start = d_start.p; a.nwords = d_nw.p; a.woff = d_woff.p; a.words = nullptr;
-        hipLaunchKernelGGL(k_cb_lift<false>, dim3(cb_blocks((size_t)n)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_cb_lift<false>, dim3(blocks_for((size_t)n)), dim3(256), 0, s, a);
         PS_HIP(hipGetLastError());
-        cb_cub(s, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, d_nw.p, d_woff.p, n, s); });
+        cub_call(s, [&](void *tmp, size_t &b) { return hipcub::DeviceScan::ExclusiveSum(tmp, b, d_nw.p, d_woff.p, n, s); });
         unsigned long long lw = 0, lo = 0;
         PS_HIP(hipMemcpyAsync(&lw, d_nw.p + (n - 1), sizeof lw, hipMemcpyDeviceToHost, s));
         PS_HIP(hipMemcpyAsync(&lo, d_woff.p + (n - 1), sizeof lo, hipMemcpyDeviceToHost, s));
@@ -358,29 +302,29 @@ void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const 
         total_words = lo + lw;
         d_words.alloc((size_t)std::max<unsigned long long>(1, total_words));
         a.words = d_words.p;
-        hipLaunchKernelGGL(k_cb_lift<true>, dim3(cb_blocks((size_t)n)), dim3(256), 0, s, a);
-        hipLaunchKernelGGL(k_cb_heads, dim3(cb_blocks((size_t)n)), dim3(256), 0, s, n, d_noff.p, d_nlen.p, d_names.p, d_head.p);
-        hipLaunchKernelGGL(k_cb_groups, dim3(cb_blocks((size_t)n)), dim3(256), 0, s, n, d_head.p, d_status.p, d_start.p, d_flag.p, d_ctg.p, d_gref.p, d_gstat.p, d_emit.p);
-        hipLaunchKernelGGL(k_cb_revcomp, dim3(cb_blocks((size_t)n)), dim3(256), 0, s, n, d_gstat.p, d_emit.p, d_ctg.p, d_strand.p, d_soff.p, d_lseq.p, d_seq.p);
+        hipLaunchKernelGGL(k_cb_lift<true>, dim3(blocks_for((size_t)n)), dim3(256), 0, s, a);
+        hipLaunchKernelGGL(k_cb_heads, dim3(blocks_for((size_t)n)), dim3(256), 0, s, n, d.name_off.p, d.name_len.p, d.names.p, d_head.p);
+        hipLaunchKernelGGL(k_cb_groups, dim3(blocks_for((size_t)n)), dim3(256), 0, s, n, d_head.p, d_status.p, d_start.p, d.flag.p, d.ref.p, d_gref.p, d_gstat.p, d_emit.p);
+        hipLaunchKernelGGL(k_cb_revcomp, dim3(blocks_for((size_t)n)), dim3(256), 0, s, n, d_gstat.p, d_emit.p, d.ref.p, d_strand.p, d.seq_off.p, d.l_seq.p, d.seq.p);
         PS_HIP(hipGetLastError());
         PS_HIP(hipStreamSynchronize(s));
     }
     tm.kernels = ms_since(t0);
 
-    t0 = clk::now();
+    t0 = HostClock::now();
     std::vector<uint32_t> status((size_t)n), words((size_t)total_words); std::vector<int32_t> start((size_t)n), emit((size_t)n);
     std::vector<unsigned long long> nw((size_t)n), woff((size_t)n); std::vector<uint8_t> gstat((size_t)n);
     if (n) {
         d_status.download(status.data(), (size_t)n, s); d_start.download(start.data(), (size_t)n, s); d_emit.download(emit.data(), (size_t)n, s);
         d_nw.download(nw.data(), (size_t)n, s); d_woff.download(woff.data(), (size_t)n, s); d_gstat.download(gstat.data(), (size_t)n, s);
         if (total_words) d_words.download(words.data(), (size_t)total_words, s);
-        if (n_seq) d_seq.download(seq.data(), (size_t)n_seq, s);
+        if (!seq.empty()) d.seq.download(seq.data(), seq.size(), s);
         PS_HIP(hipStreamSynchronize(s));
     }
     tm.d2h = ms_since(t0);
 
     // the records
-    t0 = clk::now();
+    t0 = HostClock::now();
     std::vector<int32_t> out_rec;                                          // emitted records, in transcript-file order of their groups
     for (int j = 0; j < n; ++j) {
         if (!(status[(size_t)j] & kCbLocated)) ++st.n_unlocated;
@@ -401,6 +345,7 @@ void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const 
     st.n_lifted = out_rec.size();
     const int W = std::max(1, std::min<int>(threads, (int)(out_rec.size() / 4096) + 1));
     std::vector<std::string> bufs((size_t)W); std::vector<std::vector<BamRec>> brecs((size_t)W); std::vector<std::string> errs((size_t)W);
+    auto le32 = [](const uint8_t *p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); };
     auto build = [&](int w) {
         try {
             std::string &o = bufs[(size_t)w];
@@ -410,8 +355,7 @@ void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const 
                 const size_t bs = le32(p), l_name = p[12], nc0 = n_cig[(size_t)e], ls = (size_t)l_seq[(size_t)e];
                 const uint32_t *cw = words.data() + woff[(size_t)e]; const size_t nc = (size_t)nw[(size_t)e];
                 if (nc > 65535) throw Error("ps_combine_genome_transcript: a lifted CIGAR has more than 65535 operations");
-                int64_t ref_len = 0;
-                for (size_t k = 0; k < nc; ++k) { const int op = (int)(cw[k] & 15u); if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) ref_len += cw[k] >> 4; }
+                const int64_t ref_len = cigar_ref_span(cw, (uint32_t)nc);
                 const int c = ctg[(size_t)e]; const int32_t pos = start[(size_t)e] - 1;
                 BamCore core{gref[(size_t)c], pos, pos + (ref_len > 0 ? ref_len : 1), 10, (int)(flag[(size_t)e] ^ (strand[(size_t)c] == 2 ? 16u : 0u)),
                              (uint32_t)nc, (uint32_t)ls, (int32_t)le32(p + 24), (int32_t)le32(p + 28), (int32_t)le32(p + 32)};
@@ -419,7 +363,7 @@ void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const 
                 bam_rec_begin(o, core, (const char *)p + 36, l_name - 1, r);
                 bam_rec_cigar(o, cw, nc);
                 const uint8_t *q = p + 36 + l_name + 4 * nc0 + (ls + 1) / 2;  // QUAL as it is (the Java does not reverse it), then the tags
-                o.append((const char *)&seq[(size_t)seq_off[(size_t)e]], (ls + 1) / 2);
+                o.append((const char *)seq.data() + R.seq_off[(size_t)e] / 2, (ls + 1) / 2);
                 o.append((const char *)q, (size_t)(p + 4 + bs - q));
                 bam_rec_end(o, r);
                 brecs[(size_t)w].push_back(r);
@@ -431,7 +375,7 @@ void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const 
     tm.assemble = ms_since(t0);
 
     // genomic records in file order, then the lifted ones
-    t0 = clk::now();
+    t0 = HostClock::now();
     BamStats bst;
     try {
         BamSink sink(G.text, G.refs, out_bam, sort_by_coordinate, write_index, threads, 6);

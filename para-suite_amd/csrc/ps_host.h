@@ -7,6 +7,7 @@
 #include <string>
 #include <vector>
 #include "ps_error.h"
+#include "ps_bam.h"
 #include "ps_types.h"
 #include "ps_model.h"
 #include "ps_kernels.h"
@@ -98,14 +99,9 @@ struct ProfileCounts {                 // raw counts, read orientation; [pos][re
     unsigned long long n_without_qual = 0, n_qual_beyond_read = 0;
     double ms_count = 0, ms_sd = 0;                     // kernel times (events)
 };
-// alignment records as the counting kernel takes them (BAM conventions: CIGAR words len<<4|op with MIDNSHP=X, bases as nibbles
-// =ACMGRSVTWYHKDBN in the orientation of the SAM record); gpos = start on the packed forward strand, < 0: not counted;
-// qual (ProfileAccum with quals >= 1 only): one Phred byte per base at the base's seq_off index, 0xFF first byte = QUAL absent
-struct ProfRecords {
-    std::vector<int64_t> gpos; std::vector<int32_t> l_seq; std::vector<uint32_t> flag, cig_off, n_cig, cigar;
-    std::vector<uint64_t> seq_off; std::vector<uint8_t> seq, qual;
-    size_t n() const { return gpos.size(); }
-};
+// alignment records as the counting kernel takes them: a record table (ps_bam.h) with CIGAR and bases, and QUAL for
+// ProfileAccum with quals >= 1; gpos = start on the packed forward strand, < 0: not counted.  ref and pos are not looked at.
+struct ProfRecords : RecTable { std::vector<int64_t> gpos; };
 // device-side totals that several batches of records add to (the fused first pass adds one batch per piece of the input).
 // quals: 0 the two files of the mapper, 1 + the .qualityPerMismatch sums, 2 + the per-position quality values (.qualities);
 // with quals == 2 the batches stay on the device until finish(), which walks them again in order for the standard deviation
@@ -127,8 +123,6 @@ void error_profile_count(const char *mapping_sam_or_bam, const char *ref_prefix,
 void error_profile_write(const ProfileCounts &c, const std::string &out_prefix);    // <out_prefix>.errorprofile / .indelprofile
 // the other four files of ErrorProfiling.java: .errorprofile.vcf, .qualityPerMismatch, .indels, .qualities (empty unless c.quals == 2)
 void error_profile_write_extra(const ProfileCounts &c, const std::string &out_prefix);
-std::string java_double_to_string(double v);                                        // java.lang.Double.toString
-std::string java_float_to_string(float v);                                          // java.lang.Float.toString (ps_benchmark.hip)
 
 // ---- RBP-bound clusters from a sorted mapping (ps_clusters.hip; what PileupClusters.calculateReadPileups writes) ----
 void pileup_clusters_run(const char *mapping_sam_or_bam, const char *ref_fa, const char *out_file, const char *snp_vcf, int min_cov,
@@ -137,7 +131,6 @@ void pileup_clusters_run(const char *mapping_sam_or_bam, const char *ref_fa, con
 // ---- transcript hits lifted onto the genome and appended to the genomic mapping (ps_combine.hip; CombineGenomeTranscript.combine) ----
 void combine_run(const char *genome_sam_or_bam, const char *transcript_sam_or_bam, const char *out_bam, bool sort_by_coordinate, bool write_index,
                  int threads, int device, ps_combine_stats *stats);
-struct BamFile;
 void combine_records(BamFile &genome, BamFile &transcript, const char *transcript_path, const char *out_bam, bool sort_by_coordinate, bool write_index,
                      int threads, int device, ps_combine_stats *stats, double parse_ms = 0);   // the same on loaded records, which it consumes
 

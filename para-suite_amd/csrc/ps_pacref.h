@@ -6,9 +6,10 @@
 
 namespace ps {
 
+__device__ __forceinline__ int bam_nibble(const uint8_t *seq, uint64_t base) { return (seq[base >> 1] >> ((~base & 1u) << 2)) & 15; }   // base `base` of 4-bit packed bases, high nibble first
 __device__ __forceinline__ int prof_read_code(const uint8_t *seq, uint64_t base)     // BAM nibble -> 0..3, -1 otherwise
 {
-    const int nib = (seq[base >> 1] >> ((~base & 1u) << 2)) & 15;
+    const int nib = bam_nibble(seq, base);
     return nib == 1 ? 0 : (nib == 2 ? 1 : (nib == 4 ? 2 : (nib == 8 ? 3 : -1)));
 }
 struct ProfRef {              // reference bases of one record with its holes

@@ -18,13 +18,11 @@
 // in forward-strand coordinates while the base counts they are divided by are in read orientation (:247-272, :553-570).
 #include <hip/hip_runtime.h>
 #include <algorithm>
-#include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <map>
-#include "ps_host.h"
-#include "ps_bam.h"
+#include "ps_dev.h"
+#include "ps_java.h"
 #include "ps_pacref.h"
 
 namespace ps {
@@ -83,7 +81,7 @@ __global__ void __launch_bounds__(256) k_profile(ProfArgs a)
         int R = 0; bool gapped = false;
         for (int c = 0; c < nc; ++c) {
             const int op = (int)(cg[c] & 15u), len = (int)(cg[c] >> 4);
-            if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) R += len;
+            if (cigar_on_ref(op)) R += len;
             if (Q && (op == 1 || op == 2)) gapped = true;                    // the CIGAR string contains I or D (:379-382)
         }
         if (R < 1) R = 1;                                                    // htsjdk: alignment end = start for an empty span
@@ -231,8 +229,8 @@ __global__ void __launch_bounds__(64 * (kSdLoaders + 1)) k_qual_sd(const uint8_t
 }
 
 struct ProfileAccum::Impl {
-    int device, max_len, quals = 0; hipStream_t s = nullptr; const uint8_t *pac;
-    DevBuf<int64_t> d_hoff; DevBuf<int32_t> d_hlen; int n_holes = 0;
+    int device, max_len, quals = 0; StreamGuard sg; const uint8_t *pac;
+    std::unique_ptr<RefTables> ref;
     DevBuf<unsigned long long> d_acc; size_t n_acc = 0;
     struct Kept { DevBuf<uint8_t> qual; DevBuf<uint64_t> soff; DevBuf<int32_t> nq; int n = 0; };
     std::vector<Kept> kept;                   // quals == 2: the batches in order, for the standard-deviation walk
@@ -244,40 +242,21 @@ static size_t prof_acc_words(int max_len, int quals)
 {
     return (size_t)max_len * 18 + 4 + (quals >= 1 ? 2 + 32 : 0) + (quals == 2 ? (size_t)max_len * 2 : 0);
 }
-ProfileAccum::ProfileAccum(int device, const Index &ix, int max_len, int quals) : p(new Impl())
+ProfileAccum::ProfileAccum(int device, const Index &ix, int max_len, int quals)
 {
-    if (max_len < 1 || max_len > 4096) { delete p; throw Error("error profile: maximum read length out of range"); }
-    if (quals < 0 || quals > 2 || (quals && max_len > profile_max_len(quals))) { delete p; throw Error("error profile: maximum read length out of range for the quality files (1.." + std::to_string(profile_max_len(quals)) + ")"); }
-    p->device = device; p->max_len = max_len; p->quals = quals; p->pac = ix.pac.p;
-    try {
-        require_device(device);
-        PS_HIP(hipStreamCreateWithFlags(&p->s, hipStreamNonBlocking));
-        std::vector<int64_t> hoff(ix.ref.holes.size()); std::vector<int32_t> hlen(ix.ref.holes.size());
-        for (size_t h = 0; h < ix.ref.holes.size(); ++h) { hoff[h] = ix.ref.holes[h].offset; hlen[h] = ix.ref.holes[h].len; }
-        p->n_holes = (int)hoff.size();
-        p->d_hoff.alloc(std::max<size_t>(1, hoff.size())); p->d_hlen.alloc(std::max<size_t>(1, hlen.size()));
-        if (!hoff.empty()) { p->d_hoff.upload(hoff.data(), hoff.size(), p->s); p->d_hlen.upload(hlen.data(), hlen.size(), p->s); }
-        p->n_acc = prof_acc_words(max_len, quals);
-        p->d_acc.alloc(p->n_acc); p->d_acc.zero(p->s);
-        if (quals == 2) { p->d_ssd.alloc((size_t)max_len); p->d_ssd.zero(p->s); }
-        PS_HIP(hipStreamSynchronize(p->s));
-    } catch (...) { if (p->s) (void)hipStreamDestroy(p->s); delete p; throw; }
+    if (max_len < 1 || max_len > 4096) throw Error("error profile: maximum read length out of range");
+    if (quals < 0 || quals > 2 || (quals && max_len > profile_max_len(quals))) throw Error("error profile: maximum read length out of range for the quality files (1.." + std::to_string(profile_max_len(quals)) + ")");
+    require_device(device);
+    std::unique_ptr<Impl> q(new Impl());
+    q->device = device; q->max_len = max_len; q->quals = quals; q->pac = ix.pac.p;
+    q->ref.reset(new RefTables(ix, q->sg.s));
+    q->n_acc = prof_acc_words(max_len, quals);
+    q->d_acc.alloc(q->n_acc); q->d_acc.zero(q->sg.s);
+    if (quals == 2) { q->d_ssd.alloc((size_t)max_len); q->d_ssd.zero(q->sg.s); }
+    PS_HIP(hipStreamSynchronize(q->sg.s));
+    p = q.release();
 }
-ProfileAccum::~ProfileAccum() { if (p->s) (void)hipStreamDestroy(p->s); delete p; }
-// elapsed milliseconds of what `launch` enqueues on s, waited for
-template <class F> static double timed(hipStream_t s, F launch)
-{
-    hipEvent_t e0, e1;
-    PS_HIP(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); throw Error("hipEventCreate failed"); }
-    struct EG { hipEvent_t a, b; ~EG() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } } eg{e0, e1};
-    PS_HIP(hipEventRecord(e0, s));
-    launch();
-    PS_HIP(hipEventRecord(e1, s));
-    PS_HIP(hipEventSynchronize(e1));
-    float ms = 0; PS_HIP(hipEventElapsedTime(&ms, e0, e1));
-    return ms;
-}
+ProfileAccum::~ProfileAccum() { delete p; }
 void ProfileAccum::add(const ProfRecords &t)
 {
     const size_t n = t.n();
@@ -286,21 +265,19 @@ void ProfileAccum::add(const ProfRecords &t)
     const int Q = p->quals;
     if (Q && t.qual.size() != t.seq.size() * 2) throw Error("error profile: the records carry no base qualities");
     require_device(p->device);
-    hipStream_t s = p->s;
+    hipStream_t s = p->sg.s;
     std::vector<int32_t> lo(n), hi(n);
     for (size_t i = 0; i < n; ++i) { const int64_t g = t.gpos[i]; lo[i] = g < 0 ? 0 : (int32_t)(uint32_t)(g & 0xffffffffll); hi[i] = g < 0 ? -1 : (int32_t)(g >> 32); }
-    DevBuf<int32_t> d_lo, d_hi, d_lseq, d_nq; DevBuf<uint32_t> d_flag, d_coff, d_nc, d_cig; DevBuf<uint64_t> d_soff; DevBuf<uint8_t> d_seq, d_qual;
-    auto up = [&](auto &d, const auto &v) { d.alloc(std::max<size_t>(1, v.size())); if (!v.empty()) d.upload(v.data(), v.size(), s); };
-    up(d_lo, lo); up(d_hi, hi); up(d_lseq, t.l_seq); up(d_flag, t.flag); up(d_coff, t.cig_off); up(d_nc, t.n_cig); up(d_cig, t.cigar); up(d_soff, t.seq_off); up(d_seq, t.seq);
-    if (Q) up(d_qual, t.qual);
+    DevBuf<int32_t> d_lo, d_hi, d_nq; DevRecTable d;
+    upload(d_lo, lo, s); upload(d_hi, hi, s); d.upload(t, s);
     if (Q == 2) d_nq.alloc(n);
     const int max_len = p->max_len;
     ProfArgs a;
-    a.ref_off_lo = d_lo.p; a.ref_off_hi = d_hi.p; a.l_seq = d_lseq.p; a.flag = d_flag.p; a.cig_off = d_coff.p; a.n_cig = d_nc.p; a.cigar = d_cig.p;
-    a.seq_off = d_soff.p; a.seq = d_seq.p; a.pac = p->pac; a.hole_off = p->d_hoff.p; a.hole_len = p->d_hlen.p; a.n_holes = p->n_holes;
+    a.ref_off_lo = d_lo.p; a.ref_off_hi = d_hi.p; a.l_seq = d.l_seq.p; a.flag = d.flag.p; a.cig_off = d.cig_off.p; a.n_cig = d.n_cig.p; a.cigar = d.cigar.p;
+    a.seq_off = d.seq_off.p; a.seq = d.seq.p; a.pac = p->pac; a.hole_off = p->ref->hole_off.p; a.hole_len = p->ref->hole_len.p; a.n_holes = p->ref->n_holes;
     a.n_records = (int)n; a.max_len = max_len;
     a.conv = p->d_acc.p; a.ins = p->d_acc.p + (size_t)max_len * 16; a.del = a.ins + max_len; a.stat = a.del + max_len;
-    a.qual = d_qual.p; a.qpm = Q ? a.stat + 6 : nullptr; a.qpos = Q == 2 ? a.stat + 6 + 32 : nullptr; a.n_q = d_nq.p;
+    a.qual = d.qual.p; a.qpm = Q ? a.stat + 6 : nullptr; a.qpos = Q == 2 ? a.stat + 6 + 32 : nullptr; a.n_q = d_nq.p;
     int blocks = (int)std::min<size_t>(2048, (n + 255) / 256); if (blocks < 1) blocks = 1;
     if (Q == 0) {
         const size_t lds = prof_lds_bytes(0, max_len);
@@ -314,7 +291,7 @@ void ProfileAccum::add(const ProfRecords &t)
     void (*kern)(ProfArgs) = Q == 1 ? k_profile<1> : k_profile<2>;
     set_dynamic_lds(reinterpret_cast<const void *>(kern), Q == 1 ? "k_profile<1>" : "k_profile<2>", lds);
     p->ms_count += timed(s, [&]() { hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), lds, s, a); PS_HIP(hipGetLastError()); });
-    if (Q == 2) { Impl::Kept k; k.qual = std::move(d_qual); k.soff = std::move(d_soff); k.nq = std::move(d_nq); k.n = (int)n; p->kept.push_back(std::move(k)); }
+    if (Q == 2) { Impl::Kept k; k.qual = std::move(d.qual); k.soff = std::move(d.seq_off); k.nq = std::move(d_nq); k.n = (int)n; p->kept.push_back(std::move(k)); }
 }
 void ProfileAccum::finish(ProfileCounts &out)
 {
@@ -322,8 +299,8 @@ void ProfileAccum::finish(ProfileCounts &out)
     const int max_len = p->max_len, Q = p->quals;
     const size_t st = (size_t)max_len * 18;
     std::vector<unsigned long long> acc(p->n_acc);
-    p->d_acc.download(acc.data(), p->n_acc, p->s);
-    PS_HIP(hipStreamSynchronize(p->s));
+    p->d_acc.download(acc.data(), p->n_acc, p->sg.s);
+    PS_HIP(hipStreamSynchronize(p->sg.s));
     out.max_len = max_len;
     out.conv.assign(acc.begin(), acc.begin() + (size_t)max_len * 16);
     out.ins.assign(acc.begin() + (size_t)max_len * 16, acc.begin() + (size_t)max_len * 17);
@@ -343,11 +320,11 @@ void ProfileAccum::finish(ProfileCounts &out)
     const int grid = (max_len + 63) / 64;
     out.ms_sd = 0;
     for (Impl::Kept &k : p->kept)
-        out.ms_sd += timed(p->s, [&]() { hipLaunchKernelGGL(k_qual_sd, dim3(grid), dim3(64 * (kSdLoaders + 1)), 0, p->s, k.qual.p, k.soff.p, k.nq.p, k.n, max_len, qpos, p->d_ssd.p); PS_HIP(hipGetLastError()); });
+        out.ms_sd += timed(p->sg.s, [&]() { hipLaunchKernelGGL(k_qual_sd, dim3(grid), dim3(64 * (kSdLoaders + 1)), 0, p->sg.s, k.qual.p, k.soff.p, k.nq.p, k.n, max_len, qpos, p->d_ssd.p); PS_HIP(hipGetLastError()); });
     p->kept.clear();
     out.qssd.assign((size_t)max_len, 0.0);
-    p->d_ssd.download(out.qssd.data(), (size_t)max_len, p->s);
-    PS_HIP(hipStreamSynchronize(p->s));
+    p->d_ssd.download(out.qssd.data(), (size_t)max_len, p->sg.s);
+    PS_HIP(hipStreamSynchronize(p->sg.s));
 }
 
 void error_profile_count(const char *mapping, const char *ref_prefix, int max_len, int device, int threads, ProfileCounts &out, int quals, double *ms_parse)
@@ -355,66 +332,30 @@ void error_profile_count(const char *mapping, const char *ref_prefix, int max_le
     if (max_len < 1 || max_len > 4096) throw Error("error profile: maximum read length out of range");
     if (quals && max_len > profile_max_len(quals)) throw Error("error profile: maximum read length out of range for the quality files (1.." + std::to_string(profile_max_len(quals)) + ")");
     require_device(device);
-    AlnTable t;
-    const auto t0 = std::chrono::steady_clock::now();
-    try { load_alignments(mapping, threads, t, quals > 0); } catch (const std::exception &e) { throw Error(e.what()); }
-    if (ms_parse) *ms_parse = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    hipStream_t s; PS_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct SG { hipStream_t s; ~SG() { (void)hipStreamDestroy(s); } } sg{s};
+    ProfRecords r;
+    const auto t0 = HostClock::now();
+    try { load_rec_table(mapping, kRecCigar | kRecSeq | (quals > 0 ? kRecQual : 0u), threads, r); } catch (const std::exception &e) { throw Error(e.what()); }
+    if (ms_parse) *ms_parse = ms_since(t0);
+    StreamGuard sg;
     Index ix;
-    index_load_pac(ref_prefix, ix, s);
-    std::map<std::string, int> cid;
-    for (size_t c = 0; c < ix.ref.contigs.size(); ++c) cid[ix.ref.contigs[c].name] = (int)c;
-    std::vector<int> ref_to_contig(t.refs.size(), -1);
-    for (size_t r = 0; r < t.refs.size(); ++r) { auto it = cid.find(t.refs[r].first); if (it != cid.end()) ref_to_contig[r] = it->second; }
-    const size_t n = t.n();
+    index_load_pac(ref_prefix, ix, sg.s);
+    const std::vector<int32_t> ref_to_contig = RefTables::ref_to_contig(ix, r.refs);
+    const size_t n = r.n();
     out = ProfileCounts(); out.max_len = max_len;
     unsigned long long n_unmapped = 0, n_duplicate = 0, n_start_zero = 0;
-    ProfRecords r;
     r.gpos.assign(n, -1);
     for (size_t i = 0; i < n; ++i) {
-        if (t.flag[i] & 4u) { ++n_unmapped; continue; }                       // ErrorProfiling.java:155-158
-        if (t.flag[i] & 1024u) { ++n_duplicate; continue; }                   // :159-162
-        if (t.pos[i] < 0) { ++n_start_zero; continue; }                       // :163-166 (alignment start 0 = no position)
-        if (t.ref[i] < 0 || (size_t)t.ref[i] >= ref_to_contig.size() || ref_to_contig[t.ref[i]] < 0) throw Error("error profile: a record names a sequence the reference does not have");
-        r.gpos[i] = ix.ref.contigs[ref_to_contig[t.ref[i]]].offset + (int64_t)t.pos[i];
+        if (r.flag[i] & 4u) { ++n_unmapped; continue; }                       // ErrorProfiling.java:155-158
+        if (r.flag[i] & 1024u) { ++n_duplicate; continue; }                   // :159-162
+        if (r.pos[i] < 0) { ++n_start_zero; continue; }                       // :163-166 (alignment start 0 = no position)
+        if (r.ref[i] < 0 || ref_to_contig[r.ref[i]] < 0) throw Error("error profile: a record names a sequence the reference does not have");
+        r.gpos[i] = ix.ref.contigs[ref_to_contig[r.ref[i]]].offset + (int64_t)r.pos[i];
     }
-    r.l_seq = std::move(t.l_seq); r.flag = std::move(t.flag); r.cig_off = std::move(t.cig_off); r.n_cig = std::move(t.n_cig); r.cigar = std::move(t.cigar);
-    r.seq_off = std::move(t.seq_off); r.seq = std::move(t.seq); r.qual = std::move(t.qual);
+    r.ref = {}; r.pos = {};                                                   // gpos stands for them: nothing to upload
     ProfileAccum acc(device, ix, max_len, quals);
     acc.add(r);
     acc.finish(out);
     out.n_records = n; out.n_unmapped = n_unmapped; out.n_duplicate = n_duplicate; out.n_start_zero = n_start_zero;
-}
-
-// java.lang.Double.toString: the shortest decimal that reads back as the same double (the JDK 19+ definition; older JDKs
-// print a longer digit string for a few values), plain notation with at least one fraction digit for 1e-3 <= |v| < 1e7,
-// otherwise d.dddE<exp>
-std::string java_double_to_string(double v)
-{
-    if (v != v) return "NaN";
-    if (std::isinf(v)) return v > 0 ? "Infinity" : "-Infinity";
-    if (v == 0) return std::signbit(v) ? "-0.0" : "0.0";
-    char buf[64]; int prec = 1;
-    for (; prec <= 17; ++prec) { std::snprintf(buf, sizeof buf, "%.*e", prec - 1, v); if (std::strtod(buf, nullptr) == v) break; }
-    std::string m(buf); const size_t ep = m.find('e');
-    const int e10 = std::atoi(m.c_str() + ep + 1);
-    std::string digits; bool neg = false;
-    for (size_t i = 0; i < ep; ++i) { if (m[i] == '-') neg = true; else if (m[i] >= '0' && m[i] <= '9') digits.push_back(m[i]); }
-    while (digits.size() > 1 && digits.back() == '0') digits.pop_back();
-    std::string o = neg ? "-" : "";
-    const double av = std::fabs(v);
-    if (av >= 1e-3 && av < 1e7) {
-        if (e10 >= 0) {
-            std::string ip = digits.substr(0, std::min(digits.size(), (size_t)e10 + 1));
-            while ((int)ip.size() < e10 + 1) ip.push_back('0');
-            std::string fp = digits.size() > (size_t)e10 + 1 ? digits.substr((size_t)e10 + 1) : "0";
-            o += ip + "." + fp;
-        } else o += "0." + std::string((size_t)(-e10 - 1), '0') + digits;
-    } else {
-        o += digits.substr(0, 1) + "." + (digits.size() > 1 ? digits.substr(1) : "0") + "E" + std::to_string(e10);
-    }
-    return o;
 }
 
 // what the Java derives from the counts before it writes (ErrorProfiling.java:448-458, :553-570): totals per (reference,
@@ -440,15 +381,12 @@ void error_profile_write(const ProfileCounts &c, const std::string &out_prefix)
 {
     const int ML = c.max_len;
     const ProfTotals t = profile_totals(c);
-    {
-        FILE *f = std::fopen((out_prefix + ".errorprofile").c_str(), "wb");
-        if (!f) throw Error("cannot write " + out_prefix + ".errorprofile");
-        for (int j = 0; j < 4; ++j) {
-            for (int k = 0; k < 4; ++k) std::fprintf(f, "%s\t", java_double_to_string(t.tot[j][k] / t.base[j]).c_str());
-            std::fputc('\n', f);
-        }
-        std::fclose(f);
+    std::string text;
+    for (int j = 0; j < 4; ++j) {
+        for (int k = 0; k < 4; ++k) text += java_double_to_string(t.tot[j][k] / t.base[j]) + "\t";
+        text += "\n";
     }
+    write_text_file(out_prefix + ".errorprofile", text);
     // a position without counted bases has rate 0 and is left out of the mean, as one whose gaps are 0 (:554-558)
     double ins_all = 0, del_all = 0; int ins_zero = 0, del_zero = 0;
     for (int i = 0; i < ML; ++i) {
@@ -458,10 +396,7 @@ void error_profile_write(const ProfileCounts &c, const std::string &out_prefix)
     }
     if (ML == ins_zero && ML == del_zero) ins_all = del_all = 0.0;
     else { ins_all = ins_all / (ML - ins_zero); del_all = del_all / (ML - del_zero); }
-    FILE *f = std::fopen((out_prefix + ".indelprofile").c_str(), "wb");
-    if (!f) throw Error("cannot write " + out_prefix + ".indelprofile");
-    std::fprintf(f, "%s\t%s", java_double_to_string(ins_all).c_str(), java_double_to_string(del_all).c_str());
-    std::fclose(f);
+    write_text_file(out_prefix + ".indelprofile", java_double_to_string(ins_all) + "\t" + java_double_to_string(del_all));
 }
 
 // the other four files the Java always writes: .errorprofile.vcf (:504-531, the raw totals as doubles, a blank line after each
@@ -488,13 +423,7 @@ void error_profile_write_extra(const ProfileCounts &c, const std::string &out_pr
             qua += java_double_to_string(mean) + "\t" + java_double_to_string(sd) + "\n";
         }
     const std::pair<const char *, const std::string *> files[4] = {{".errorprofile.vcf", &vcf}, {".qualityPerMismatch", &qpm}, {".indels", &ind}, {".qualities", &qua}};
-    for (const auto &fl : files) {
-        const std::string path = out_prefix + fl.first;
-        FILE *f = std::fopen(path.c_str(), "wb");
-        if (!f) throw Error("cannot write " + path);
-        const bool ok = std::fwrite(fl.second->data(), 1, fl.second->size(), f) == fl.second->size();
-        if (std::fclose(f) != 0 || !ok) throw Error("cannot write " + path);
-    }
+    for (const auto &fl : files) write_text_file(out_prefix + fl.first, *fl.second);
 }
 
 }  // namespace ps

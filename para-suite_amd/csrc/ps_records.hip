@@ -327,6 +327,7 @@ void batch_profile_records(const Batch &b, int min_mapq, int threads, ProfRecord
         }
         t_rec[t] = nr; t_cig[t] = nc; t_base[t] = nb;
     });
+    out.columns = kRecCigar | kRecSeq;
     size_t r0 = out.n(), c0 = out.cigar.size(), b0 = out.seq.size() * 2;     // every record starts on a whole byte
     std::vector<size_t> br(nt + 1), bc(nt + 1), bb(nt + 1);
     br[0] = r0; bc[0] = c0; bb[0] = b0;

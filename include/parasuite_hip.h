@@ -367,6 +367,91 @@ typedef struct {
 int     ps_benchmark_reads(const char *mapping_sam_or_bam, const char *out_statistics, const char *reads_fq,
                            ps_benchmark_stats *stats /* may be NULL */);
 
+/* ---- before the mapping: the toolkit's `simulate TRANSCRIPT_FILE OUTPUT_PREFIX ERROR_PROFILE T2C_PROFILE T2C_POSITIONS_PROFILE
+ * QUALITY_DIST INDEL_PROFILE RBP_BOUND` mode (Main.java:684-802, which hands the eight arguments to
+ * bin/createSimulatedPARCLIPDataset.pl in that order): PAR-CLIP reads drawn from transcripts on the GPU.  Writes the five files
+ * the Perl opens (:35-39): <out_prefix>.fastq, .clusters (the truth of the cluster benchmark), _snps.vsf, .log and .err.  The
+ * rules are those of the Perl as it is written, restated in plain Python in tests/perl_simulator.py, which the library matches
+ * byte for byte; the random stream is the library's own (Math::Random's cannot be reproduced, and the files must not depend
+ * on how the work is cut):
+ *   the stream   - every draw is a pure function draw32(seed, transcript ordinal, cluster ordinal, read ordinal, slot):
+ *                  mix = the finalizer of splitmix64; run = mix(seed + 0x9E3779B97F4A7C15);
+ *                  unit = mix(mix(run ^ transcript) ^ (cluster << 32 | read)); draw32 = mix(unit ^ slot) >> 32.  Transcripts count
+ *                  from 0 in file order; cluster 0 / read 0 is the transcript's own unit, cluster 1..3 / read 0 a cluster's, read
+ *                  i + 1 the read named ":i".  Slots -- transcript: 0 selection, 1 number of clusters; cluster: 0-11 reads, 12
+ *                  position, 13 / 14 / 15 number of T->C sites / starts / ends, 16 + 12 i starts, 52 + 12 i ends, 88 bound, 89 + k
+ *                  the k-th site, 128 + 4 z + {0 SNP, 1 alternative base, 2 zygosity, 3 report} for transcript position z; read: 0
+ *                  start, 1 end, and for iteration `it` of the per-base loop 16 + 64 it + {0 test, 1 base for a non-ACGT
+ *                  character, 2 SNP passes, 3 indel test, 4 inserted base, 8-19 quality, 20-31 the SNP's extra quality, 32-43 the
+ *                  insertion's quality};
+ *                - rand() is draw32 / 2^32 as a double; ceil(rand() * k) is 1 + floor(draw32 * k / 2^32) and floor(rand() * k) is
+ *                  floor(draw32 * k / 2^32), both in integers (the former differs from Perl only at a draw of 0);
+ *                  random_normal(mean, sd) is mean + sd * z with z = (sum of 12 draws - 6 * 2^32) * 2^-32, the product and the sum
+ *                  rounded separately, no fused multiply-add and no libm call anywhere; int() truncates toward zero;
+ *   transcripts  - lines end at "\n" only (chomp), so a "\r" of a CRLF file is part of the sequence; text before the first header
+ *                  is dropped.  THE LAST TRANSCRIPT OF THE FILE IS NEVER SIMULATED: createReads runs when the next header
+ *                  arrives (:203-218).  The header is split on '|' (trailing empty fields dropped): field 2 the chromosome, 3
+ *                  and 4 the exon starts and ends, ';'-separated and each list sorted numerically on its own, the last field the
+ *                  strand (read as a number; == -1 reverses the position list, :242-262).  Field 0 keeps its '>', so read names
+ *                  begin "@SEQ_ID:>GENE|" (:611);
+ *   selection    - a transcript is used when rand() < select_read; it gets 1..3 clusters of int(N(16, 10)) reads each.  A cluster
+ *                  at a position < 10 is skipped: it still takes its cl_<n> number, does not advance the cluster index of the
+ *                  read names and writes no .clusters line (:276-281);
+ *   clusters     - 1..4 T->C sites, 1..3 starts int(N(pos, 1)), 1..3 ends int(N(pos + 23, 1)); the .clusters line
+ *                  "cl_<n>\tchr<chr>\t<start>\t<end>\t<bound>" is built from min(starts) and max(ends) through the exon map,
+ *                  swapped on strand -1 (:295-301, :366).  Bound when rand() < bound_prob: the 'T's in [max(starts), min(ends))
+ *                  are candidates, and per k one is picked by the weights of the site-positions file at position - max(starts)
+ *                  (doubles added in the Perl's order; no draw when one candidate is left), removed, and given rate
+ *                  sitefrequency[k] (:316-362, :652-686);
+ *   SNPs         - per cluster that is not skipped, over the WHOLE transcript: a position is a SNP with snp_rate, homozygous (1)
+ *                  or heterozygous (0.5) with equal chance, its alternative one of the three other bases (none for a character
+ *                  that is no ACGT: the Perl's undef); written to _snps.vsf with snp_report; snp<id> counts across the whole
+ *                  run whether reported or not (:369-394);
+ *   reads        - one of the starts and one of the ends; left out, its ":i" kept, when end - start > 30 or start >= end
+ *                  (:412-418).  The per-base loop (:428-591): a T->C site of a bound cluster gives 'C' when rate > test, else
+ *                  the base, and moves on; a non-ACGT character writes an .err entry (three lines, the whole sequence among
+ *                  them) and takes the error row of a uniformly drawn base, a match still copying the character and a mismatch
+ *                  by k giving ACGT[(0 + k) % 4]; a SNP at the position passes with probability 1 or 0.5 and APPENDS an extra
+ *                  quality and the alternative base -- the error step still follows, so such a read is one character longer
+ *                  (and where the alternative is none, its quality line is); the error step uses the profile row with its
+ *                  diagonal replaced by 1 - the other three and thresholds in the order base, +1, +2, +3, a mismatch moving on;
+ *                  a match falls through to the indel step when allow_indels: only the first indel of a read counts, an
+ *                  insertion (test <= ins[j]) appends a random base with a quality and repeats position j, a deletion
+ *                  (<= del[j]) only counts -- the base was appended already.  "bases simulated" counts only iterations that
+ *                  reach the loop's end;
+ *   qualities    - int(N(mean_j, sd_j)); above 64 becomes 64, at or below 2 becomes 3, the character is 33 + q (:621-633).
+ *                  Numbers in the profile files are read as Perl reads a string in numeric context: the decimal number it
+ *                  starts with, so the "\r" of a CRLF file is ignored;
+ *   read names   - "@SEQ_ID:<field 0>|<field 1>|<chr>|<a>|<b>|<bound>-<cluster index>:<i>" with a, b = gp[start], gp[end] on strand
+ *                  == 1 and gp[end] + 1, gp[start] + 1 otherwise (:603-611);
+ *   .log         - the eleven counter lines and the two parameter lines (:221-227); divisions as Perl prints numbers (%.15g);
+ *                  "read with most T2C" includes the Perl's count of "+2" mismatches (:538).
+ * Deviations.  The Perl binds the error row before it replaces a non-ACGT character (:453, :497), so it reads an empty row there;
+ * this library takes the row of the drawn base, as the replacement intends.  Where the Perl dies or reads undefined values the
+ * call fails, naming the transcript or the file: a run that emits no read (the Perl divides by zero and leaves an empty FASTQ); a
+ * header with fewer than six fields, a non-integer exon bound or unequal numbers of starts and ends; exons shorter in total than
+ * the sequence (all checked for every transcript but the last, selected or not); a profile file with fewer lines than the loop
+ * can index: 4 error rows, 4 site frequencies, 40 site positions, 31 quality lines, 31 indel lines.  On any error nothing is left
+ * behind: the files are written under <name>.sim-tmp and renamed together.  The Perl's progress lines are not reproduced;
+ * PS_VERBOSE=1 prints the stage times.  Without a HIP device the call fails. */
+typedef struct {
+    const char *transcripts_fa, *out_prefix, *error_profile, *t2c_profile, *t2c_positions, *quality_dist, *indel_profile;   /* all required */
+    double bound_prob;                               /* RBP_BOUND: the fraction of clusters that are bound */
+    uint64_t seed;
+    double select_read;                              /* <= 0: 0.216, the Perl's $select_read */
+    double snp_rate;                                 /* < 0: 0.01 (:377); 0 switches SNPs off */
+    double snp_report;                               /* < 0: 0.8, the Perl's $report_snp */
+    int32_t allow_indels, pad_;                      /* < 0: 1, the Perl's $allow_indels; 0: no indel step, the indel file is not read */
+} ps_simulate_opts;
+typedef struct {
+    uint64_t n_reads, n_bases_simulated, sum_read_length, n_clusters, n_t2c, n_errors, most_t2c, most_errors, n_indels, n_snps;   /* the .log, in its order (sum_read_length: the numerator of its third line) */
+    uint64_t n_transcripts, n_selected, n_clusters_skipped, n_reads_skipped, n_snps_reported, n_non_acgt;   /* headers in the file; transcripts used; clusters at a position < 10; reads left out; _snps.vsf lines; .err entries */
+    uint64_t n_snps_preselected, n_snp_positions;    /* SNPs of the pre-selection; (cluster, position) pairs it drew for */
+    double avg_read_length, avg_reads_per_cluster;   /* as written to the .log */
+    double s_total, s_read, s_plan, s_snp, s_snp_kernels, s_reads, s_write;   /* seconds: the inputs; plan kernel, scans, download; SNP passes with scan and download, and their two kernels alone; read kernel and download; text and files */
+} ps_simulate_stats;
+int     ps_simulate_reads(const ps_simulate_opts *opts, ps_simulate_stats *stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,7 +44,7 @@ EXPORTS = ["ps_version", "ps_last_error", "ps_index", "ps_map", "ps_ctx_open", "
            "ps_ctx_blob", "ps_ctx_meta", "ps_ctx_from_blobs", "ps_ctx_clone", "ps_ctx_fetch", "ps_ctx_export_blob", "ps_ctx_sa_lookup", "ps_ctx_order_sort", "ps_ctx_index_check", "ps_sam_to_bam", "ps_map_to_bam", "ps_bam_view", "ps_bam_sort", "ps_bam_index", "ps_batch_from_fastq",
            "ps_batch_from_codes", "ps_batch_free", "ps_batch_n", "ps_batch_search", "ps_batch_select_hard",
            "ps_batch_select_easy", "ps_batch_locate", "ps_batch_run", "ps_batch_write_sam", "ps_batch_n_aln",
-           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route", "ps_benchmark_reads"]
+           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route", "ps_benchmark_reads", "ps_simulate_reads"]
 
 _LIB = None
 
@@ -431,7 +431,36 @@ def ps_benchmark_reads(mapping, out_statistics, reads_fq):
     return {f: getattr(st, f) for f, _ in BenchmarkStats._fields_}
 
 
-def ps_map_profiled(threads, mm, error_profile, indel_profile, ref_fa, reads, out_sam, min_mapq, max_read_len, profile_prefix):
+class SimulateOpts(C.Structure):
+    _fields_ = [(k, C.c_char_p) for k in ("transcripts_fa", "out_prefix", "error_profile", "t2c_profile", "t2c_positions", "quality_dist",
+                                          "indel_profile")] + \
+               [("bound_prob", C.c_double), ("seed", C.c_uint64), ("select_read", C.c_double), ("snp_rate", C.c_double),
+                ("snp_report", C.c_double), ("allow_indels", C.c_int32), ("pad_", C.c_int32)]
+
+
+class SimulateStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_reads", "n_bases_simulated", "sum_read_length", "n_clusters", "n_t2c", "n_errors", "most_t2c",
+                                          "most_errors", "n_indels", "n_snps", "n_transcripts", "n_selected", "n_clusters_skipped",
+                                          "n_reads_skipped", "n_snps_reported", "n_non_acgt", "n_snps_preselected", "n_snp_positions")] + \
+               [(k, C.c_double) for k in ("avg_read_length", "avg_reads_per_cluster", "s_total", "s_read", "s_plan", "s_snp", "s_snp_kernels",
+                                          "s_reads", "s_write")]
+
+
+def ps_simulate_reads(transcripts_fa, out_prefix, error_profile, t2c_profile, t2c_positions, quality_dist, indel_profile, bound_prob, seed=0,
+                      select_read=None, snp_rate=None, snp_report=None, allow_indels=None):
+    """bin/createSimulatedPARCLIPDataset.pl, the `simulate` mode: PAR-CLIP reads drawn from transcripts on the GPU; writes
+    <out_prefix>.fastq, .clusters, _snps.vsf, .log and .err and returns the counters.  None for one of the last four selects the
+    Perl's constant (0.216, 0.01, 0.8, indels allowed)"""
+    L = lib(); L.ps_simulate_reads.argtypes = [C.POINTER(SimulateOpts), C.POINTER(SimulateStats)]
+    o = SimulateOpts(*[str(v).encode() for v in (transcripts_fa, out_prefix, error_profile, t2c_profile, t2c_positions, quality_dist, indel_profile)],
+                     float(bound_prob), int(seed), -1.0 if select_read is None else float(select_read), -1.0 if snp_rate is None else float(snp_rate),
+                     -1.0 if snp_report is None else float(snp_report), -1 if allow_indels is None else int(bool(allow_indels)), 0)
+    st = SimulateStats()
+    _chk(L.ps_simulate_reads(C.byref(o), C.byref(st)))
+    return {f: getattr(st, f) for f, _ in SimulateStats._fields_}
+
+
+def ps_map_profiled(threads, mm,error_profile, indel_profile, ref_fa, reads, out_sam, min_mapq, max_read_len, profile_prefix):
     """ps_map + <profile_prefix>.errorprofile / .indelprofile of its alignments with MAPQ >= min_mapq, counted from memory"""
     enc = lambda v: v.encode() if v else None
     L = lib(); L.ps_map_profiled.argtypes = [C.c_int] + [C.c_char_p] * 6 + [C.c_int, C.c_int, C.c_char_p]

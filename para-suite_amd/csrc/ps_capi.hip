@@ -458,6 +458,18 @@ int ps_benchmark_reads(const char *mapping_sam_or_bam, const char *out_statistic
     PS_CATCH_INT
 }
 
+// The toolkit's `simulate` mode (Main.java:684-802): bin/createSimulatedPARCLIPDataset.pl.  The five files are written under
+// temporary names after every kernel has run and renamed together: an error leaves none.
+int ps_simulate_reads(const ps_simulate_opts *opts, ps_simulate_stats *stats)
+{
+    PS_TRY
+        if (!opts) throw Error("ps_simulate_reads: opts is NULL");
+        const int dev = first_device();
+        simulate_run(*opts, dev, stats);
+        return 0;
+    PS_CATCH_INT
+}
+
 int ps_sam_to_bam(const char *sam, const char *bam, int min_mapq, int sort_by_coordinate, int write_index, int threads, ps_bam_stats *st)
 {
     PS_TRY

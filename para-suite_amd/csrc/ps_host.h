@@ -140,4 +140,7 @@ struct BenchmarkRatios { int32_t fp, fn, matched; float precision, recall, accur
 BenchmarkRatios benchmark_ratios(const ps_benchmark_stats &st);
 std::string benchmark_text(const ps_benchmark_stats &st, const BenchmarkRatios &r);  // the statistics file
 
+// ---- PAR-CLIP reads drawn from transcripts (ps_simulate.hip; bin/createSimulatedPARCLIPDataset.pl) ----
+void simulate_run(const ps_simulate_opts &opts, int device, ps_simulate_stats *stats);
+
 }  // namespace ps

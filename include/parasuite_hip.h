@@ -29,7 +29,10 @@ const char *ps_version(void);
 const char *ps_last_error(void);
 
 /* `bwa index`: writes <ref_fa>.bwt/.sa/.pac/.ann (this project's formats; the caller only tests that
- * <ref_fa>.bwt exists, PARAsuiteMapping.java:45-46).  Suffix sorting runs on the GPU. */
+ * <ref_fa>.bwt exists, PARAsuiteMapping.java:45-46).  Suffix sorting runs on the GPU.
+ * ref_fa: FASTA as plain text, gzip (RFC 1952, concatenated members too) or BGZF, told apart by its first two bytes, as bwa
+ * reads it through gzopen.  The index files are named after the path as given (genome.fa.gz.bwt, ...), as `bwa index` names
+ * them; every call that takes ref_fa takes the same string.  Deviations: as for the reads of ps_map. */
 int ps_index(const char *ref_fa);
 
 /* `bwa parasuite` (or `bwa aln` when error_profile is NULL) + `bwa samse` fused: FASTQ in, SAM out.
@@ -44,7 +47,16 @@ int ps_index(const char *ref_fa);
  *   stock -n INT: 0..37 (3n + 15 score buckets; -n 38 is refused); -n with a '.' is a false-negative rate.
  *   read length: 1..250 bp (PS_MAX_LEN); one longer read fails the call.
  * Above 64 score buckets (-X 8 and up, -X -1 from 190 bp, -n 17 and up) a launch takes the wide search stack; reads with the
- * same gap limit share one launch, which the longest of them decides. */
+ * same gap limit share one launch, which the longest of them decides.
+ * fastq: FASTQ or FASTA as plain text, gzip (RFC 1952: CM 8, FEXTRA / FNAME / FCOMMENT / FHCRC skipped, CRC32 and ISIZE of
+ * every member checked, concatenated members decoded one after the other) or BGZF, a regular file or a FIFO, told apart by the
+ * first two bytes -- what bwa accepts through gzopen.  gzip is inflated by one thread that runs ahead of the parser, BGZF block
+ * by block on `threads`; the text's size is unknown then, so the pieces are cut as for a FIFO (csrc/ps_inflate.h).  The same
+ * holds for ps_map_to_bam, ps_map_profiled, ps_map_route's reads and ps_batch_from_fastq.
+ * Deviations: (1) gzread hands out a truncated stream as if it ended there, so bwa maps half a file and exits 0; here an input
+ * that ends inside a member (header, data or trailer) fails the call.  (2) gzread ignores bytes behind the last member; here
+ * bytes behind a complete member that do not start another member fail the call.  Both, a CRC32 / ISIZE mismatch, invalid
+ * deflate data, CM other than 8, reserved flag bits and a bad BGZF BSIZE are errors that name the file and the compressed byte. */
 int ps_map(int threads, const char *mm, const char *error_profile, const char *indel_profile,
            const char *ref_fa, const char *fastq, const char *out_sam);
 
@@ -119,7 +131,9 @@ int     ps_batch_timing(ps_batch *, ps_timing *out);
 int64_t ps_ctx_read_iters(ps_ctx *, uint32_t *out, int64_t cap);   /* profiling aid (env PS_READ_ITERS=1): per read of the last search launch 20 words -- iterations | stack slots used | lower bounds as fetched (read, seed << 8) and the effort estimate's two scans (<< 16, << 24) | best score, final budget << 8, hits << 16 | 16 words of D bounds -- in the order the launch held the reads (leading-base order of the bin, not input order); returns the word count */
 int     ps_batch_kstats(ps_batch *, int which /*0 width 1 backtrack 2 sa2pos*/, ps_kstats *out);
 /* host-only check of the read parser: whole file on `threads` threads (chunk_bytes 0) or streamed in windows of chunk_bytes as
- * ps_map does; out = {reads, bases, order-sensitive hash of names / sequences / qualities, pieces} */
+ * ps_map does; out = {reads, bases, order-sensitive hash of names / sequences / qualities, pieces}.  reads_path: plain, gzip or
+ * BGZF as for ps_map, with the same two deviations (a truncated member and trailing bytes are errors); for a compressed input
+ * the piece count is the one of an input whose size is unknown */
 /* the library keeps up to 3 GB of page-locked host buffers between calls (locking and unlocking them costs ~0.1 s per piece of a
  * ps_map call); this gives them back */
 void    ps_release_host_cache(void);
@@ -200,7 +214,8 @@ int     ps_error_profile_full(const char *mapping_sam_or_bam, const char *ref_fa
  * CIGAR holds (I or D) and N are skipped and counted, and the last cluster is never written (all as in the Java).
  * site_prefix NULL or "": the mapping file's name.  snp_vcf NULL or "": no known SNPs (an extension); the VCF is read whole
  * (plain, gzip or BGZF), so no .tbi is needed.  ref_fa needs its index (.ann/.pac, ps_index); sequence text comes from the
- * FASTA itself.  Where the Java throws or is undefined, this does not, and counts the case in stats instead:
+ * FASTA itself, which may be plain, gzip or BGZF like ps_index's (the same string serves both; the index is named after it as
+ * given); deviations as for ps_map's reads: a truncated member or bytes behind the last one fail the call.  Where the Java throws or is undefined, this does not, and counts the case in stats instead:
  *   - T->C at read index >= 51 (the Java's boolean[51] throws): counted everywhere but the read-index flags (n_t2c_beyond_51);
  *   - CCR window starting before base 1 (htsjdk reads bytes before the contig): empty CCR sequence (n_ccr_clipped);
  *   - a HashMap bucket of more than 8 sites at the end of a cluster (the Java resizes or makes a tree, and its iteration

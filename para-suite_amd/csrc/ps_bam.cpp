@@ -20,6 +20,7 @@
 #include <vector>
 #include "ps_bam.h"
 #include "ps_error.h"
+#include "ps_inflate.h"
 #include "ps_java.h"
 
 namespace ps {
@@ -261,15 +262,16 @@ static void inflate_bgzf(const char *path, int threads, Blocks &out)
     if (sz && std::fread(raw.data(), 1, (size_t)sz, f) != (size_t)sz) { std::fclose(f); throw Error(std::string("short read on ") + path); }
     std::fclose(f);
     out.file_bytes = (uint64_t)sz;
-    struct B { size_t at, bsize; uint32_t isize; uint64_t u; };
+    // the header and the inflate of one block are ps_inflate.h's, shared with the byte source of the text inputs
+    struct B { size_t at, bsize, hl; uint32_t isize; uint64_t u; };
     std::vector<B> bl; size_t at = 0; uint64_t u = 0;
     while (at < raw.size()) {
-        if (at + 28 > raw.size() || raw[at] != 31 || raw[at + 1] != 139 || raw[at + 12] != 'B' || raw[at + 13] != 'C') throw Error(std::string("not a BGZF file: ") + path);
-        const size_t bsize = (size_t)(raw[at + 16] | (raw[at + 17] << 8)) + 1;
+        size_t hl = 0, bsize = 0; const char *why = nullptr;
+        if (gz_member_header(raw.data() + at, raw.size() - at, hl, bsize, why) <= 0 || bsize < hl + 8) throw Error(std::string("not a BGZF file: ") + path);
         if (at + bsize > raw.size()) throw Error(std::string("truncated BGZF block in ") + path);
-        const unsigned char *t = raw.data() + at + bsize - 4;
-        const uint32_t isize = (uint32_t)t[0] | ((uint32_t)t[1] << 8) | ((uint32_t)t[2] << 16) | ((uint32_t)t[3] << 24);
-        bl.push_back(B{at, bsize, isize, u});
+        const uint32_t isize = bgzf_isize(raw.data() + at, bsize);
+        if (isize > kBgzfMaxOut) throw Error(std::string("corrupt BGZF block in ") + path);
+        bl.push_back(B{at, bsize, hl, isize, u});
         u += isize; at += bsize;
     }
     out.data.assign((size_t)u, '\0');
@@ -279,14 +281,8 @@ static void inflate_bgzf(const char *path, int threads, Blocks &out)
     par(T, T, [&](int t) {
         for (size_t k = (size_t)t; k < bl.size(); k += (size_t)T) {
             const B &b = bl[k];
-            if (!b.isize) continue;
-            z_stream zs; std::memset(&zs, 0, sizeof zs);
-            if (inflateInit2(&zs, -15) != Z_OK) throw Error("inflateInit2 failed");
-            zs.next_in = raw.data() + b.at + 18; zs.avail_in = (uInt)(b.bsize - 26);
-            zs.next_out = (Bytef *)&out.data[(size_t)b.u]; zs.avail_out = b.isize;
-            const int rc = inflate(&zs, Z_FINISH);
-            inflateEnd(&zs);
-            if (rc != Z_STREAM_END || zs.total_out != b.isize) throw Error(std::string("corrupt BGZF block in ") + path);
+            if (const char *e = bgzf_inflate_block(raw.data() + b.at, b.bsize, b.hl, b.isize ? &out.data[(size_t)b.u] : nullptr, b.isize))
+                throw Error(std::string("corrupt BGZF block in ") + path + ": " + e + " at compressed byte " + std::to_string(b.at));
         }
     });
 }

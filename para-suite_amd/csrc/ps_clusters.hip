@@ -26,6 +26,7 @@
 #include <unordered_map>
 #include "../../include/parasuite_hip.h"
 #include "ps_dev.h"
+#include "ps_inflate.h"
 #include "ps_java.h"
 #include "ps_pacref.h"
 
@@ -318,13 +319,11 @@ __global__ void __launch_bounds__(64 * (kSfLoaders + 1)) k_cl_sitefreq(const int
 // the whole FASTA as stored (soft-masked lower case kept): first word of the header -> bases
 static std::unordered_map<std::string, std::string> cl_read_fasta(const char *path)
 {
-    FILE *f = std::fopen(path, "rb");
-    if (!f) throw Error(std::string("cannot open ") + path);
-    std::fseek(f, 0, SEEK_END); const long sz = std::ftell(f); std::fseek(f, 0, SEEK_SET);
-    std::string b((size_t)std::max(0L, sz), '\0');
-    const bool ok = sz <= 0 || std::fread(&b[0], 1, (size_t)sz, f) == (size_t)sz;
-    std::fclose(f);
-    if (!ok) throw Error(std::string("short read on ") + path);
+    std::string b;                                             // plain, gzip or BGZF, as ps_index reads the same path (ps_inflate.h)
+    {
+        ByteSource src(path, "cannot open ");
+        read_all(src, b, 8);
+    }
     std::unordered_map<std::string, std::string> out;
     std::string *cur = nullptr;
     size_t i = 0;

@@ -52,7 +52,7 @@ struct RefSeq {
     int pos2rid(int64_t pos_f) const;
     int cnt_ambi(int64_t pos_f, int len, int *ref_id) const;
 };
-void load_fasta(const char *path, RefSeq &ref);
+void load_fasta(const char *path, RefSeq &ref);      // plain, gzip or BGZF (ps_inflate.h)
 
 // 48-bit LCG of POSIX drand48/lrand48 (the generator upstream bwa seeds with 11)
 struct Rng48 {

@@ -23,6 +23,7 @@
 #include <sys/mman.h>
 #include "ps_host.h"
 #include "ps_core.h"
+#include "ps_inflate.h"
 
 namespace ps {
 
@@ -40,13 +41,13 @@ static inline int nt4(int c)
 // the pac, in its contig and in the lrand48 stream (jump-ahead), the second pass packs.
 void load_fasta(const char *path, RefSeq &ref)
 {
-    FILE *f = std::fopen(path, "rb");
-    if (!f) throw Error(std::string("cannot open reference ") + path);
-    std::fseek(f, 0, SEEK_END); long sz = std::ftell(f); std::fseek(f, 0, SEEK_SET);
-    std::vector<char> buf((size_t)sz + 1);
-    if (sz && std::fread(buf.data(), 1, (size_t)sz, f) != (size_t)sz) { std::fclose(f); throw Error(std::string("short read on ") + path); }
-    std::fclose(f);
-    const size_t n = (size_t)sz;
+    std::vector<char> buf;                                     // plain, gzip or BGZF (ps_inflate.h)
+    {
+        ByteSource src(path, "cannot open reference ");
+        read_all(src, buf, 8);
+    }
+    const size_t n = buf.size();
+    buf.push_back('\0');
     const char *b = buf.data();
     ref = RefSeq();
     // ---- records: header fields and body spans

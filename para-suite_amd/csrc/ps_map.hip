@@ -27,6 +27,7 @@
 #include <fcntl.h>
 #include <sys/stat.h>
 #include <unistd.h>
+#include "ps_inflate.h"
 #include "ps_map.h"
 #include "ps_map_plan.h"
 
@@ -185,7 +186,7 @@ Pass::Pass(MapJob &j) : job(j), nthr(j.a.threads > 0 ? j.a.threads : 1), set(j.r
     dev = plan_devices(ids, want, per_dev, have, (int)Ctx::N_WORK);
     G = (int)dev.devs.size(); n_workers = dev.n_workers();
     struct stat st;
-    const size_t file_bytes = !job.reads && ::stat(job.a.reads, &st) == 0 && st.st_size > 0 ? (size_t)st.st_size : 0;
+    const size_t file_bytes = !job.reads && ::stat(job.a.reads, &st) == 0 && st.st_size > 0 && !is_gzip_file(job.a.reads) ? (size_t)st.st_size : 0;   // compressed: the text's size is unknown
     cut = plan_pieces(file_bytes, n_workers, job.bam_out, env_mb("PS_CHUNK_MB"), env_mb("PS_HUNGRY_MIN_MB"), env_mb("PS_FIRST_MB"));
     parsed.cap = (size_t)std::max(2, n_workers);
     done_cap = (size_t)n_workers + 2;

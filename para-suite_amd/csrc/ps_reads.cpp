@@ -1,4 +1,5 @@
-// ps_reads.cpp -- read input: FASTQ / FASTA files as ReadSets, whole or streamed in pieces of whole records (host only).
+// ps_reads.cpp -- read input: FASTQ / FASTA files (plain, gzip or BGZF: ps_inflate.h) as ReadSets, whole or streamed in pieces of
+// whole records (host only).
 #include <algorithm>
 #include <cctype>
 #include <cerrno>
@@ -7,9 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <thread>
-#include <fcntl.h>
-#include <unistd.h>
-#include <sys/stat.h>
+#include "ps_inflate.h"
 #include "ps_reads.h"
 
 namespace ps {
@@ -211,35 +210,6 @@ static void parser_times(int threads)
         std::fprintf(stderr, "[parasuite-hip]     parser: reading %.0f ms, cutting %.0f ms, parsing on %d threads %.0f ms, placing the threads' parts %.0f ms (sums over the windows)\n", 1e3 * g_t_fread, 1e3 * g_t_cut, threads, 1e3 * g_t_par, 1e3 * g_t_merge);
     g_t_fread = g_t_cut = g_t_par = g_t_merge = 0;
 }
-// `want` bytes at file offset `at` into dst, by a few threads side by side when the file is a regular one (one thread copies ~3 GB/s out
-// of the page cache); returns the bytes read (fewer than wanted: the input ends there)
-static size_t read_at(int fd, bool regular, off_t at, char *dst, size_t want, int threads)
-{
-    auto one = [&](size_t lo, size_t hi) -> size_t {
-        size_t have = lo;
-        while (have < hi) {
-            const ssize_t r = regular ? ::pread(fd, dst + have, hi - have, at + (off_t)have) : ::read(fd, dst + have, hi - have);
-            if (r < 0) { if (errno == EINTR) continue; throw Error("read error on the reads file"); }
-            if (r == 0) break;
-            have += (size_t)r;
-        }
-        return have - lo;
-    };
-    const int nt = regular ? (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(threads, 8), want >> 22)) : 1;      // >= 4 MB per thread
-    if (nt == 1) return one(0, want);
-    std::vector<size_t> got((size_t)nt, 0); std::vector<std::string> err((size_t)nt);
-    auto part = [&](int t) { try { got[t] = one(want * (size_t)t / nt, want * (size_t)(t + 1) / nt); } catch (const std::exception &e) { err[t] = e.what(); } };
-    { std::vector<std::thread> th; for (int t = 1; t < nt; ++t) th.emplace_back(part, t); part(0); for (auto &x : th) x.join(); }
-    size_t total = 0;
-    for (int t = 0; t < nt; ++t) {
-        if (!err[t].empty()) throw Error(err[t]);
-        total += got[t];
-        if (got[t] < want * (size_t)(t + 1) / nt - want * (size_t)t / nt) break;       // the input ended inside this part: what lies behind is not there
-    }
-    return total;
-}
-struct FdCloser { int fd; ~FdCloser() { if (fd >= 0) ::close(fd); } };
-
 void load_reads(const char *path, ReadSet &rs, int threads)
 {
     rs = ReadSet();
@@ -250,15 +220,14 @@ void load_reads(const char *path, ReadSet &rs, int threads)
 void load_reads_chunked(const char *path, int threads, size_t chunk_bytes, const std::function<void(ReadSet &&)> &sink, size_t first_bytes,
                         const std::function<bool()> *hungry, size_t hungry_min_bytes)
 {
-    const int fd = ::open(path, O_RDONLY);
-    if (fd < 0) throw Error(std::string("cannot open reads ") + path);
-    FdCloser closer{fd};
-    struct stat st;
-    const bool regular = ::fstat(fd, &st) == 0 && S_ISREG(st.st_mode);
     if (chunk_bytes < 4096) chunk_bytes = 4096;
     size_t unit = (size_t)64 << 20;
     if (const char *e = std::getenv("PS_UNIT_MB")) unit = (size_t)std::max(1, std::atoi(e)) << 20;
     unit = std::min(unit, chunk_bytes);
+    // plain, gzip or BGZF (ps_inflate.h); a compressed input's text has no known size and takes the branches a FIFO takes below
+    ByteSource src(path, "cannot open reads ", unit);
+    const bool sized = src.size_known();             // a plain regular file
+    const off_t text_bytes = sized ? (off_t)src.size() : 0;
     // the first piece may be smaller (the stages behind the parser start sooner), the following ones double up to chunk_bytes
     size_t cur = first_bytes && first_bytes < chunk_bytes ? std::max<size_t>(first_bytes, 4096) : chunk_bytes;
     RawVec<char> buf; size_t have = 0; bool eof = false; char mark = 0; off_t file_at = 0;
@@ -271,7 +240,7 @@ void load_reads_chunked(const char *path, int threads, size_t chunk_bytes, const
         if (buf.size() < want + 1) buf.resize(want + 1);
         const auto tr0 = std::chrono::steady_clock::now();
         if (!eof && have < want) {
-            const size_t got = read_at(fd, regular, file_at, buf.data() + have, want - have, threads);
+            const size_t got = src.read(buf.data() + have, want - have, threads);
             if (got < want - have) eof = true;
             have += got; file_at += (off_t)got;
         }
@@ -288,7 +257,7 @@ void load_reads_chunked(const char *path, int threads, size_t chunk_bytes, const
         }
         if (cut) {
             const size_t tiny = cur / 8;                                                                        // an end of the input not worth a launch of its own
-            const bool to_the_end = regular && (size_t)std::max<off_t>(0, st.st_size - file_at) + have <= tiny;  // this window and all behind it
+            const bool to_the_end = sized && (size_t)std::max<off_t>(0, text_bytes - file_at) + have <= tiny;  // this window and all behind it
             if (acc_bytes && acc_bytes + cut > cur + fine && !to_the_end) flush();    // this window would take the piece well over its size (a window that had to grow)
             const bool first_window = acc.n == 0;
             parse_span(buf.data(), 0, cut, threads, acc);
@@ -301,7 +270,7 @@ void load_reads_chunked(const char *path, int threads, size_t chunk_bytes, const
             acc_bytes += cut;
             // no piece is cut off just in front of the end of the input: what is left would be a launch of its own (>= 0.3 s for 0.6 M reads,
             // measured) -- the piece takes it along, up to an eighth over its size
-            const size_t rest = regular ? (size_t)std::max<off_t>(0, st.st_size - file_at) + (have - cut) : ~(size_t)0;
+            const size_t rest = sized ? (size_t)std::max<off_t>(0, text_bytes - file_at) + (have - cut) : ~(size_t)0;
             const bool tiny_rest = !eof && rest <= tiny;
             if (!tiny_rest && (acc_bytes + fine > cur || (hungry && acc_bytes >= hungry_min_bytes && (*hungry)()))) flush();
         }

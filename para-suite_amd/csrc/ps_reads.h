@@ -27,8 +27,9 @@ struct ReadSet {
     RawVec<char> names; RawVec<int64_t> name_off;            // n+1
     const char *name(int64_t i, size_t &l) const { l = (size_t)(name_off[i + 1] - name_off[i]); return names.data() + name_off[i]; }
 };
-void load_reads(const char *path, ReadSet &rs, int threads = 1); // FASTQ or FASTA
-// The input in pieces of whole records, in order; sink(piece) may block.  The file is STREAMED in windows of <= 64 MB; a piece is the
+void load_reads(const char *path, ReadSet &rs, int threads = 1); // FASTQ or FASTA; plain, gzip or BGZF (ps_inflate.h)
+// The input in pieces of whole records, in order; sink(piece) may block.  The file is STREAMED in windows of <= 64 MB (a compressed
+// one inflated as it goes: its text has no known size, so the end of the input is met as on a FIFO); a piece is the
 // windows parsed so far and goes out when another window would take it over chunk_bytes (first_bytes for the first piece, doubling from
 // there) or -- `hungry` given -- as soon as it holds hungry_min_bytes and hungry() says that the stage behind is waiting for work.
 void load_reads_chunked(const char *path, int threads, size_t chunk_bytes, const std::function<void(ReadSet &&)> &sink, size_t first_bytes = 0,

@@ -1,5 +1,5 @@
 // ps_dev.h -- what the host code of every analysis mode does around its kernels (ps_profile, ps_clusters, ps_combine,
-// ps_benchmark): a stream of its own, tables onto the device, a hipCUB call, times, the reference's tables, a text file.
+// ps_benchmark; the clock and the event timer serve the mapping stages too): a stream of its own, tables onto the device, a hipCUB call, times, the reference's tables, a text file.
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -40,11 +40,15 @@ inline double ms_since(HostClock::time_point t) { return std::chrono::duration<d
 struct EventPair {                     // device time between start() and stop() on one stream
     hipEvent_t a = nullptr, b = nullptr;
     EventPair() { PS_HIP(hipEventCreate(&a)); if (hipEventCreate(&b) != hipSuccess) { (void)hipEventDestroy(a); throw Error("hipEventCreate failed"); } }
+    explicit EventPair(hipStream_t s) : EventPair() { start(s); }
     EventPair(const EventPair &) = delete;
     ~EventPair() { (void)hipEventDestroy(a); (void)hipEventDestroy(b); }
     void start(hipStream_t s) { PS_HIP(hipEventRecord(a, s)); }
     void stop(hipStream_t s) { PS_HIP(hipEventRecord(b, s)); }
+    // stop(): the end is recorded and the host goes on submitting; ms(): the time, once the host has a reason to wait anyway
     double ms() { PS_HIP(hipEventSynchronize(b)); float v = 0; PS_HIP(hipEventElapsedTime(&v, a, b)); return v; }   // waits for stop()
+    // start / stop on a context's clock (ms since its reference event): launches of two streams that overlap in time
+    void span(hipEvent_t ref, double &t_begin, double &t_end) { float x = 0, y = 0; if (ref && hipEventElapsedTime(&x, ref, a) == hipSuccess && hipEventElapsedTime(&y, ref, b) == hipSuccess) { t_begin = x; t_end = y; } }
 };
 // elapsed milliseconds of what `launch` enqueues on s, waited for
 template <class F> double timed(hipStream_t s, F launch)

@@ -52,6 +52,9 @@ inline int budget_diffs(const Options &o, int len)
     return o.fnr > 0.0 ? cal_maxdiff(len, 0.02, o.fnr) : o.max_diff;
 }
 
+// an integer knob from the environment: v is left alone unless the name is set
+inline bool env_int(const char *name, int &v) { const char *e = std::getenv(name); if (e) v = std::atoi(e); return e != nullptr; }
+
 // `-n` argument of `bwa aln`: a value containing '.' is a false-negative rate, otherwise a count
 inline void set_stock_n(Options &o, const char *s)
 {

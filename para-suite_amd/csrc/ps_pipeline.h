@@ -1,4 +1,5 @@
-// ps_pipeline.h -- batch pipeline behind the C ABI (host orchestration of the gfx950 kernels).
+// ps_pipeline.h -- batch pipeline behind the C ABI (host orchestration of the gfx950 kernels): the one interface of
+// ps_pipeline.hip (context, batch set-up), ps_search.hip (search stage) and ps_samse.hip (selection, locate).
 #pragma once
 #include <functional>
 #include <map>
@@ -28,7 +29,7 @@ struct DevCigar { int64_t g; int32_t n; uint32_t c[PS_HIT_CIGAR]; };
 struct SubRead { int64_t g = 0, easy_before = 0, hard_before = 0; uint8_t cls = 0; const AlnRec *alns = nullptr; int32_t n_alns = 0; Hit hit; };   // alns: into Batch::sub_alns or a Bin's overflow list
 
 struct Timing {
-    double ms_width = 0, ms_backtrack = 0, ms_compact = 0, ms_select = 0, ms_sa2pos = 0, ms_refine = 0, ms_host_post = 0, ms_total = 0, ms_classify = 0, ms_rows = 0, ms_sel_hard = 0, ms_sel_easy = 0;
+    double ms_width = 0, ms_backtrack = 0, ms_select = 0, ms_sa2pos = 0, ms_refine = 0, ms_host_post = 0, ms_total = 0, ms_classify = 0, ms_sel_hard = 0, ms_sel_easy = 0;
     int n_width_launches = 0, n_backtrack_launches = 0;
     double bt_begin_ms = 0, bt_end_ms = 0;   // first search launch's start / last one's end on the context's clock (overlapping batches: the union)
 };
@@ -73,6 +74,7 @@ struct Ctx {
     hipEvent_t ref_event = nullptr;  // the context's clock: recorded once at creation
     Index ix;
     Options opt;
+    int cus = 256;                 // compute units of the device, read once by attach_device()
     int bt_blocks = 0;             // grid of the backtracking kernel (0 = 4 blocks per CU)
     uint32_t pool_cap[3] = {16384, 65535, 2000064};   // stack entries per lane: 16-byte narrow tiers, then the wide tier
     int aln_cap[3] = {8, 256, 65536};
@@ -92,7 +94,7 @@ struct Ctx {
     // A context in two steps: options and knobs (no device call: ps_map's parser needs nothing else and starts before the runtime is
     // up, which takes 0.2-0.3 s in a fresh process), then the device side (stream, clock).
     explicit Ctx(int device);      // reads the tuning knobs from the environment (PS_FETCH_MIN, PS_N_BIG, ...)
-    void attach_device();          // needs a HIP device; a second call does nothing
+    void attach_device();          // needs a HIP device (stream, clock, CU count); a second call does nothing
     void set_stock(const char *n_arg);                                            // bwa aln's -n
     void set_profile(const char *ep, const char *ip, const char *x_arg);          // the two profile files and -X
     void set_options(const char *mm, const char *ep, const char *ip) { if (ep && ep[0]) set_profile(ep, ip, mm); else set_stock(mm && mm[0] ? mm : "0.04"); }   // a mapping call's three arguments
@@ -107,7 +109,7 @@ struct Bin {
     bool ragged = false;                      // more than one length present
     std::vector<int32_t> lens; DevBuf<int32_t> d_lens;     // bin-local; d_lens allocated only when ragged
     std::vector<int32_t> ids;                 // global read index of every local read
-    DevBuf<uint32_t> bases, nmask, w; DevBuf<uint8_t> cwb, cswb, status; DevBuf<AlnRec> alns; DevBuf<int32_t> n_aln;
+    DevBuf<uint32_t> bases, nmask;
     RawVec<uint32_t> h_bases, h_nmask;        // host copy (tier re-runs gather from it); every word is written by the packing threads, none zero-filled first
     DevBuf<int32_t> d_ids;                     // ids on the device (bin-local -> input order)
     DevBuf<AlnRec> d_alns; DevBuf<int32_t> d_n_aln; DevBuf<uint8_t> d_status; int aln_cap = 0;   // first-tier hit lists stay in HBM

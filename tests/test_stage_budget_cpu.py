@@ -12,7 +12,7 @@ import subprocess
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "para-suite_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-UNITS = ["ps_kernels.hip", "ps_effort.hip", "ps_stage.hip", "ps_pipeline.hip"]
+UNITS = ["ps_kernels.hip", "ps_effort.hip", "ps_stage.hip", "ps_search.hip", "ps_samse.hip"]
 
 # every kernel the two in-flight batches run between their search launches: mangled-name fragment -> what it is
 STAGE_KERNELS = {

@@ -116,6 +116,7 @@ void load_fasta(const char *path, RefSeq &ref)
         c.len += (int32_t)sp.n_seq;
     }
     { int64_t off = 0; for (Contig &c : ref.contigs) { c.offset = off; off += c.len; } }
+    if (l_pac == 0) throw Error(std::string("no bases in ") + path + " (headers only): nothing to index");     // an empty text has no suffix to sort
     ref.l_pac = l_pac;
     ref.pac.assign((size_t)l_pac / 4 + 2, 0);
     // ---- pass 2: pack (the first and last byte of a piece may be shared with its neighbours)

@@ -37,6 +37,7 @@ struct Blk { uint32_t x[16]; };  // cnt[4] + lo[6] + hi[6]
 #define PS_AS_GLOBAL(T, p) ((const __attribute__((address_space(1))) T *)(p))
 #define PS_AS_GLOBAL_W(T, p) ((__attribute__((address_space(1))) T *)(p))
 typedef uint32_t ps_u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t ps_u32x2 __attribute__((ext_vector_type(2)));
 #endif
 
 // A per-lane index the optimiser may not fold into loop-invariant addresses.  The stage kernels that must start beside a
@@ -286,6 +287,7 @@ PS_HD int jump_levels_for(bwtint seq_len) { int k = 0; while (k < PS_JUMP_MAX_LE
 struct BtHot {
     const OccBlock *blocks; bwtint primary;
     const uint32_t *jump; uint32_t jump_levels;
+    uint32_t skip_levels;            // jump_levels where barren steps inside the table are crossed at once (ps_narrow.h: nt_skip), else 0
     uint32_t L2lo[4], L2hi;          // C array of the FM index: low words, bit 32 of L2[c] at bit c (bit 4: bit 32 of n, the root's base)
     uint32_t s_pk[5], u_pk[5];       // substitution costs, one word per read symbol (byte c = text symbol)
     uint32_t p0, p1, p2, p3;
@@ -322,6 +324,8 @@ inline bool bt_hot_make(const BtArgs &a, BtHot &h)
     const Model &md = a.md;
     h.blocks = a.ix.blocks; h.primary = a.ix.primary; h.L2hi = 0;
     h.jump = a.ix.jump; h.jump_levels = a.ix.jump ? (uint32_t)a.ix.jump_levels : 0u;
+    // (nt_skip compares bound bytes with the differences the budget still pays for, a number it takes to be below 128)
+    h.skip_levels = (a.no_skip || (((uint32_t)md.max_units * (uint32_t)md.inv_c_min) >> 16) > 127u) ? 0u : h.jump_levels;
     for (int c = 0; c < 4; ++c) { h.L2lo[c] = (uint32_t)a.ix.L2[c]; h.L2hi |= (uint32_t)((a.ix.L2[c] >> 32) & 1ull) << c; }
     h.L2hi |= (uint32_t)((a.ix.seq_len >> 32) & 1ull) << 4;
     for (int c = 0; c < 5; ++c) { h.s_pk[c] = md.s_mm_pk[c]; h.u_pk[c] = md.u_mm_pk[c]; }

@@ -107,7 +107,7 @@ __device__ __forceinline__ void pin_hot(BtHot &h, const BtHot &k)
 {
     h.blocks = reinterpret_cast<const OccBlock *>(pin64(reinterpret_cast<unsigned long long>(k.blocks)));
     h.primary = pin64(k.primary);
-    h.jump = reinterpret_cast<const uint32_t *>(pin64(reinterpret_cast<unsigned long long>(k.jump))); h.jump_levels = pin32(k.jump_levels);
+    h.jump = reinterpret_cast<const uint32_t *>(pin64(reinterpret_cast<unsigned long long>(k.jump))); h.jump_levels = pin32(k.jump_levels); h.skip_levels = pin32(k.skip_levels);
 #pragma unroll
     for (int c = 0; c < 4; ++c) h.L2lo[c] = pin32(k.L2lo[c]);
     h.L2hi = pin32(k.L2hi);

@@ -378,9 +378,10 @@ PS_HD void nt_pop(NLane &L, BtMem &m)
 // M_EXPAND for the lanes that go on, 0 for the others), nt_step_occ (the memory step), nt_tail (exact extension or
 // expansion and pushes).
 template <bool STATS, bool NB32>
-PS_HD int nt_head(const BtArgs &a, const BtHot &h, NLane &L, LaneStats &st, BtMem &m, int fetch_r, bool serve_hit)
+PS_HD int nt_head(const BtArgs &a, const BtHot &h, NLane &L, LaneStats &st, BtMem &m, int fetch_r, bool serve_hit, int &rem_out)
 {
     int mode = nl_mode(L.ctl);
+    rem_out = 0;
     if (mode == M_EXIT || mode == M_GROW) return 0;
     if (STATS) ++st.iters;
     if (mode == M_HIT) {
@@ -412,6 +413,7 @@ PS_HD int nt_head(const BtArgs &a, const BtHot &h, NLane &L, LaneStats &st, BtMe
         if (score > nl_best_score(L) + h.s_stop()) { nt_finish_read(a, L); return 0; }
         const int rem = nl_max_units(L) - nt_units(h, L.wa, L.wb);
         if (rem < 0) return 0;
+        rem_out = rem;
         const int mleft = (int)(ps_mul24((uint32_t)rem, h.inv_c_min) >> 16);     // rem / c_min
         if (i1 > 0 && mleft < (int)(m.cw[i1 - 1] & 0x7f)) return 0;
         if (i1 == 0) { L.ctl = nl_set_mode(L.ctl, M_HIT); return 0; }
@@ -606,14 +608,164 @@ PS_HD void nt_tail(const BtHot &h, NLane &L, LaneStats &st, BtMem &m, const NtSt
     L.n_phantom += phantom;
 }
 
+// ---- barren steps inside the jump table's levels, crossed at once ------------------------------------------------
+// An expansion is BARREN when its position allows no difference (nt_tail: allow_diff false): it can only follow its match child.
+// It stores nothing, counts no phantom, records no hit and changes no bound, so between two barren steps the lane's stack, budget
+// and best score stand still, and every check nt_head would repeat comes out as it did.  While the entry is inside the table's
+// levels it is (string index, width), and the index after t more matching bases is a shift and an OR: nt_skip moves the entry over
+// the run of barren positions in front of it, and the normal step then runs on the entry it lands on, in the same iteration.  An
+// entry that would die inside the run (an N in the read, a string the text does not hold, a bound the budget no longer pays for) is
+// dropped, as the step that kills it would drop it.  A run is at most NT_SKIP_MAX positions per iteration -- one word of bound
+// bytes; the next iteration carries a longer one on (on the host lane machine, 8 Mbp and 50-bp PAR-CLIP reads, 4 positions leave
+// 84.2 % of the iterations, 8 positions 83.6 %, at twice the byte arithmetic).  Exact extension (M_EXACT), every step of which is
+// barren, is left as it is: 2 % of the iterations, and the skip would pay for it with selects in every step.
+#ifndef PS_TABLE_SKIP
+#define PS_TABLE_SKIP 1       // 0: compiled out (A/B builds; at run time PS_SKIP=0, BtArgs::no_skip)
+#endif
+static const int NT_SKIP_MAX = 4;
+struct NtSkip { uint32_t ck, cl; };      // the landing string's own interval bounds, out of its parent's slot; ck == NT_NO_SKIP: the lane did not skip
+static const uint32_t NT_NO_SKIP = 0xFFFFFFFFu;          // no count of one symbol reaches 2^32 - 1
+
+// bytes e-4 .. e-1 (e-1 on top) of a byte array held in 4-byte words: hi = word e>>2, lo = the word below it
+PS_HD uint32_t nt_bytes_below(uint32_t hi, uint32_t lo, uint32_t e)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_alignbyte(hi, lo, e & 3u);
+#else
+    const uint32_t sh = 8u * (e & 3u);
+    return sh ? (hi << (32u - sh)) | (lo >> sh) : lo;
+#endif
+}
+// bits sh .. sh+31 of hi:lo (sh < 32)
+PS_HD uint32_t nt_bits_from(uint32_t hi, uint32_t lo, uint32_t sh)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __builtin_amdgcn_alignbit(hi, lo, sh);
+#else
+    return sh ? (hi << (32u - sh)) | (lo >> sh) : lo;
+#endif
+}
+PS_HD uint32_t nt_clz(uint32_t x)            // 32 for 0
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return (uint32_t)__clz((int)x);
+#else
+    return x ? (uint32_t)__builtin_clz(x) : 32u;
+#endif
+}
+PS_HD uint32_t nt_brev(uint32_t x)
+{
+#ifdef __HIP_DEVICE_COMPILE__
+    return __brev(x);
+#else
+    x = ((x & 0x55555555u) << 1) | ((x >> 1) & 0x55555555u); x = ((x & 0x33333333u) << 2) | ((x >> 2) & 0x33333333u);
+    x = ((x & 0x0f0f0f0fu) << 4) | ((x >> 4) & 0x0f0f0f0fu); x = ((x & 0x00ff00ffu) << 8) | ((x >> 8) & 0x00ff00ffu);
+    return (x << 16) | (x >> 16);
+#endif
+}
+// byte-wise "bound >= v" over a word of bound bytes (low 7 bits: the bound): bit 7 of ((w & 0x7f7f7f7f) + nt_ge_key(v))
+PS_HD uint32_t nt_ge_key(int v)
+{
+    const uint32_t u = (uint32_t)(v > 128 ? 128 : v);
+#ifdef __HIP_DEVICE_COMPILE__
+    return 0x80808080u - __builtin_amdgcn_perm(u, u, 0u);      // the low byte in all four (one byte permute; as shifts and ORs the compiler makes it a 32-bit multiply, quarter rate)
+#else
+    return 0x80808080u - u * 0x01010101u;
+#endif
+}
+
+// rem: the budget the entry has left, as nt_head worked it out at the pop (0 where it did not pop: the entry is then left alone)
+PS_HD int nt_skip(const BtHot &h, NLane &L, const BtMem &m, int mode, int rem, NtSkip &sk)
+{
+    sk.ck = NT_NO_SKIP; sk.cl = 0;
+    const int len = nl_len(L), i1 = nw_i(L.wa);
+    const int d = nt_depth(len, L.wa, L.wb);
+    int t = (int)h.skip_levels - 1 - d;              // every entry on the way, the one landed on included, is still a table entry
+    t = t > NT_SKIP_MAX ? NT_SKIP_MAX : t;
+    t = t > i1 - 1 ? i1 - 1 : t;                     // position 0 always allows differences
+    // mleft == 0: after one match step the entry may turn to exact extension (nt_head), left to the normal step.  A full stack:
+    // the expansion asks for a larger one, or gives the read up, before it looks at anything (nt_tail) -- that step is not barren
+    const int mleft = (int)(ps_mul24((uint32_t)rem, h.inv_c_min) >> 16);
+    const uint32_t cap = (L.ctl & NL_BIG) ? h.big_cap : h.pool_cap;
+    if (mode != M_EXPAND || t <= 0 || mleft == 0 || nl_bump(L) + 9u > cap) return mode;
+    // One straight piece of code, everything it reads from local memory asked for up front.  Position p = i, i-1, .. is barren iff
+    // D(p-1) >= mleft, or inside the seed Ds(pp-1) >= m_seed; its match child is dropped by its pop iff D(p-1) > mleft.  Four
+    // bound bytes, byte i-1 on top; what lies below byte 0 is cut off by t <= i.
+    const uint32_t e = (uint32_t)(i1 - 1);
+    const uint32_t *cw32 = reinterpret_cast<const uint32_t *>(m.cw);
+    const int w0 = (int)(e >> 2);
+    const uint32_t x0 = cw32[w0], x1 = cw32[w0 > 0 ? w0 - 1 : 0];
+    const int r0 = len - i1;                         // the read bases consumed: read positions r0 .. r0 + t - 1
+    const int qb = r0 >> 4, qb_last = ((len + 15) >> 4) - 1;
+    const uint32_t rb_lo = m.rb[qb], rb_hi = m.rb[qb < qb_last ? qb + 1 : qb_last];
+    uint32_t nlo, nhi;
+    if (lm_nmask_in_regs(h.len())) { const bool up = r0 >= 32; nlo = up ? L.rn1 : L.rn0; nhi = up ? 0u : L.rn1; }
+    else { const int qn = r0 >> 5, qn_last = ((len + 31) >> 5) - 1; nlo = m.rn[qn]; nhi = m.rn[qn < qn_last ? qn + 1 : qn_last]; }
+    const uint32_t sum = (nt_bytes_below(x0, x1, e) & 0x7f7f7f7fu) + nt_ge_key(mleft);
+    uint32_t barren = sum & 0x80808080u;
+    const uint32_t kills = (sum - 0x01010101u) & 0x80808080u;        // bound >= mleft + 1 (no byte of sum is 0 while mleft < 128: bt_hot_make switches the skip off for larger budgets)
+    if (h.use_seed()) {
+        const int off = len - h.seed_len(), ii = (int)e - off;
+        const uint32_t vs = (uint32_t)((off > 0 && ii > 0) ? ii : 0);    // seed positions below this one (the read's own seed rule: none in a read no longer than the seed)
+        const int e_un = nl_max_units(L) - rem, srem = h.seed_units() - e_un;
+        const int m_seed = srem <= 0 ? 0 : (int)(ps_mul24((uint32_t)srem, h.inv_c_min) >> 16);
+        const uint32_t *cs32 = reinterpret_cast<const uint32_t *>(m.csw);
+        const int s0 = (int)(vs >> 2);
+        const uint32_t y0 = cs32[s0], y1 = cs32[s0 > 0 ? s0 - 1 : 0];
+        const uint32_t valid = vs >= 4u ? 0xFFFFFFFFu : ~(0xFFFFFFFFu >> (8u * vs));      // the top vs bytes
+        barren |= ((nt_bytes_below(y0, y1, vs) & 0x7f7f7f7fu) + nt_ge_key(m_seed)) & valid & 0x80808080u;
+    }
+    // the contiguous run from the top: the bounds need not be monotone (nt_hit's shadow step rewrites them)
+    const int run = (int)(nt_clz(barren ^ 0x80808080u) >> 3);
+    t = t > run ? run : t;
+    if (t == 0) return mode;
+    const bool dead = (int)(nt_clz(kills) >> 3) < t || (nt_bits_from(nhi, nlo, (uint32_t)(r0 & 31)) & ((1u << t) - 1u)) != 0u;      // ... or an N among the bases
+    uint32_t y = nt_brev(nt_bits_from(rb_hi, rb_lo, (uint32_t)(2 * (r0 & 15))));     // the first base consumed on top
+    y = ((y & 0x55555555u) << 1) | ((y >> 1) & 0x55555555u);                   // ... with the two bits of every base in order again
+    const uint32_t sidx = (L.kr << (2 * t)) | (~y >> (32 - 2 * t));           // text symbol = 3 - read base
+    const uint32_t c = sidx & 3u;
+    // the landing string exists iff it is a non-empty child of its parent's slot (an empty string's slot is all zero: no child)
+    // (an entry that dies in the run takes the same way, as a select and not as a branch: what it loads is a slot of the table too)
+    const uint32_t *ps = h.jump + (size_t)((jump_level_off(d + t - 1) + (sidx >> 2)) * (uint32_t)PS_JUMP_SLOT_WORDS + 2u * c);     // the whole table is less than 2^30 words
+#ifdef __HIP_DEVICE_COMPILE__
+    const ps_u32x2 v = *PS_AS_GLOBAL(ps_u32x2, ps);
+    sk.ck = v.x; sk.cl = v.y;
+#else
+    sk.ck = ps[0]; sk.cl = ps[1];
+#endif
+    L.kr = sidx;
+    L.wa = (L.wa & NW_KEEP) + (uint32_t)(i1 - t);    // exactly what t match steps leave: state M, no last difference
+    L.wb = (L.wb & ~NW_C_MASK) | (c << 6);
+    if (dead) L.ctl = nl_set_mode(L.ctl, M_POP);
+    return dead ? 0 : mode;
+}
+// the landing string's interval has arrived (its load was issued before the step's own): an empty one drops the entry
+PS_HD int nt_skip_land(NLane &L, const NtSkip &sk, int mode)
+{
+    if (sk.ck == NT_NO_SKIP) return mode;
+    if (sk.ck >= sk.cl) { L.ctl = nl_set_mode(L.ctl, M_POP); return 0; }
+    L.lr = sk.cl - sk.ck;
+    return mode;
+}
+
 template <bool STATS, bool NB32>
 PS_HD void nt_iter(const BtArgs &a, const BtHot &h, NLane &L, LaneStats &st, BtMem &m, int fetch_r, bool serve_hit, NtClock *clk = nullptr)
 {
     PS_USTAMP(clk, 0);                                   // read hand-out, stack moves (the kernel loop), up to here
-    const int mode = nt_head<STATS, NB32>(a, h, L, st, m, fetch_r, serve_hit);
+    int rem = 0;
+    int mode = nt_head<STATS, NB32>(a, h, L, st, m, fetch_r, serve_hit, rem);
     PS_USTAMP(clk, 1);                                   // hits, new reads, the pop and its checks
+    NtSkip sk;
+    sk.ck = NT_NO_SKIP;
+    if (PS_TABLE_SKIP && mode) mode = nt_skip(h, L, m, mode, rem, sk);
     NtStep q;
     if (mode) nt_step_occ<STATS>(h, L, st, m, q);
+    if (PS_TABLE_SKIP) mode = nt_skip_land(L, sk, mode);
+#if PS_TABLE_SKIP && defined(__HIP_DEVICE_COMPILE__)
+    // the entry is in its four registers again here: without this fence the compiler carries the parts the landing is made of
+    // into the expansion and puts the entry together there -- 114 registers instead of 111, one allocation granule too many (ps_budget.h)
+    asm volatile("" : "+v"(L.kr), "+v"(L.lr), "+v"(L.wa), "+v"(L.wb), "+v"(L.ctl), "+v"(mode));
+#endif
 #if defined(PS_STAMPS) && defined(__HIP_DEVICE_COMPILE__)
     if (STATS && clk && mode) asm volatile("" :: "v"(q.ck[0]), "v"(q.cl[0]), "v"(q.ck[3]), "v"(q.cl[3]));
 #endif

@@ -18,6 +18,7 @@ struct SearchKnobs {
     int order = 1, order_min = 4096, order_restart = 0 /* 0: an average mismatch of the model */, order_wpin = 16, order_cap = 255, order_scale = 8;
     int max_per_cu = PS_SEARCH_WAVES;   // workgroups per CU the kernel's registers allow (ps_kernels.hip: PS_BT_WAVES)
     bool cap = true; int cap_bias = 0;  // the first tier spares entries by the estimate; tests: estimates too low by that much, so that the restart path runs
+    bool skip = true;                   // barren steps inside the jump table's levels are crossed in one iteration (ps_narrow.h: nt_skip)
     int fetch_min = 8, hit_min = 1;     // tuning: the context's values unless set at search time
 };
 inline SearchKnobs search_knobs_from_env(int ctx_fetch_min, int ctx_hit_min)
@@ -33,6 +34,7 @@ inline SearchKnobs search_knobs_from_env(int ctx_fetch_min, int ctx_hit_min)
     if (env_int("PS_MAX_PER_CU", v)) k.max_per_cu = v;
     if (env_int("PS_CAP", v)) k.cap = v != 0;
     if (env_int("PS_CAP_BIAS", v)) k.cap_bias = std::max(0, std::min(200, v));
+    if (env_int("PS_SKIP", v)) k.skip = v != 0;
     if (env_int("PS_FETCH_MIN", v)) k.fetch_min = std::max(1, v);
     if (env_int("PS_HIT_MIN", v)) k.hit_min = std::max(1, v);
     return k;

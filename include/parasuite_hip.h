@@ -467,6 +467,50 @@ typedef struct {
 } ps_simulate_stats;
 int     ps_simulate_reads(const ps_simulate_opts *opts, ps_simulate_stats *stats /* may be NULL */);
 
+/* ---- after `clust`: the toolkit's `fetch -i SITES -r REF -o OUT` (bed == 0) and `fetchBed` (bed != 0) modes (Main.java:883-945) ----
+ * `new FetchSequencesForBindingSites().fetchSequences(ref, sites, out)` and `new FetchSequencesForBEDFile().fetchSequences(..)`
+ * (src/src/utils/pileupclusters/FetchSequencesForBindingSites.java, FetchSequencesForBEDFile.java): the reference sequence of
+ * every site of a table, gathered on the GPU from the index's packed forward strand.  ref_fa names an existing index as for
+ * ps_error_profile; only <ref_fa>.ann and <ref_fa>.pac are read (the same string serves a gzip-named reference: genome.fa.gz
+ * finds genome.fa.gz.ann), the FASTA itself is not opened and need not exist, and the .fai the Java insists on is not needed.
+ * The index keeps every run of non-ACGT letters with its character, and both Java classes upper-case every base they fetch
+ * (:64-68), so the soft-masking the index drops never reaches the output.  The rules are those of the Java as it is written,
+ * restated in plain Python in tests/java_fetch.py (from the FASTA text; no JVM is at hand to pin it to the jar):
+ *   lines      - end at "\n", "\r" or "\r\n" (BufferedReader.readLine); a last line without an end counts, an end at the end
+ *                of the file adds no line.  Line 1 is copied to the output, followed by "\n", in BOTH modes (:26-28): in
+ *                fetchBed a first BED record is consumed as the header and never fetched.  Every further line is split on
+ *                TAB, trailing empty fields dropped (String.split);
+ *   fetch      - (the cluster table of `clust`) field 1 is the contig, taken as it is; fields 2 and 3 are start and end,
+ *                read by Integer.parseInt; field 4 equal to "-" means reverse, anything else forward.  The sequence REPLACES
+ *                FIELD 11 -- on a `clust` table the SeqLength column, not "Seqenece" -- and the fields are joined with TAB
+ *                and ended with "\n" (:70-73); fields that split dropped stay dropped;
+ *   fetchBed   - field 0 is the contig, with "chr" put in front unless it starts with it (:40-43); fields 1 and 2 go to
+ *                getSubsequenceAt UNCHANGED, so BED's 0-based half-open pair is read as 1-based inclusive: one base longer
+ *                and shifted; field 4 -- BED's score column, not its strand column -- equal to "-" means reverse.  The
+ *                output is ">" + field 3 + "\n" + sequence + "\n";
+ *   sequence   - bases start..end of the contig, 1-based and inclusive; for a reverse site SequenceUtil.reverseComplement:
+ *                the order reversed, A C G T (either case) swapped, every other character kept; then every character
+ *                through toUpperCase.  A base inside a hole is the hole's character, upper-cased (n -> N; R stays R, on
+ *                the reverse strand too);
+ *   empty      - (SAMException caught, :59-61) a site is left empty when start > end + 1 (in Java ints: end + 1 wraps), when
+ *                the contig is not in the index, or when end > contig length; start == end + 1 is a legal empty sequence.
+ *                In fetch an empty sequence still replaces field 11, so a line of twelve fields ends in a TAB.
+ *   - site starting before base 1 (htsjdk reads bytes before the contig): empty sequence (n_before_start).
+ * Deviations, all where the Java dies or misleads: an empty sites file (the Java writes the text "null"); a data line with
+ * fewer than 12 fields in fetch or fewer than 5 in fetchBed, a blank line among them (uncaught ArrayIndexOutOfBounds); a start
+ * or end that Integer.parseInt refuses (caught outside the loop, the writer never closed: an 8 KB-granular torso remains);
+ * out_file equal to an input; a missing index; no HIP device -- each is an error that names the 1-based line or the file, and
+ * nothing is left behind: the output is written under <out_file>.fetch-tmp and renamed.  PS_VERBOSE=1 prints the stage times.
+ * PS_FETCH_PIECE: bytes of sequence gathered per piece (default 256 MiB, at most 4 GiB, rounded up to a multiple of 16; the
+ * pieces are cut anywhere, inside a site too, and the output does not depend on the cut). */
+typedef struct {
+    uint64_t n_lines, n_sites, n_reverse, n_bases, n_hole_bases;        /* lines read (header included); data lines; strand "-"; bases written; of them from holes */
+    uint64_t n_inverted, n_no_contig, n_past_end, n_before_start;       /* sites left empty, by the first reason that applies, in this order */
+    uint64_t n_pieces;
+    double s_total, s_read, s_index, s_kernels, s_write;
+} ps_fetch_stats;
+int     ps_fetch_sequences(const char *ref_fa, const char *sites, const char *out_file, int bed, ps_fetch_stats *stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,7 +44,7 @@ EXPORTS = ["ps_version", "ps_last_error", "ps_index", "ps_map", "ps_ctx_open", "
            "ps_ctx_blob", "ps_ctx_meta", "ps_ctx_from_blobs", "ps_ctx_clone", "ps_ctx_fetch", "ps_ctx_export_blob", "ps_ctx_sa_lookup", "ps_ctx_order_sort", "ps_ctx_index_check", "ps_sam_to_bam", "ps_map_to_bam", "ps_bam_view", "ps_bam_sort", "ps_bam_index", "ps_batch_from_fastq",
            "ps_batch_from_codes", "ps_batch_free", "ps_batch_n", "ps_batch_search", "ps_batch_select_hard",
            "ps_batch_select_easy", "ps_batch_locate", "ps_batch_run", "ps_batch_write_sam", "ps_batch_n_aln",
-           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route", "ps_benchmark_reads", "ps_simulate_reads"]
+           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route", "ps_benchmark_reads", "ps_simulate_reads", "ps_fetch_sequences"]
 
 _LIB = None
 
@@ -458,6 +458,22 @@ def ps_simulate_reads(transcripts_fa, out_prefix, error_profile, t2c_profile, t2
     st = SimulateStats()
     _chk(L.ps_simulate_reads(C.byref(o), C.byref(st)))
     return {f: getattr(st, f) for f, _ in SimulateStats._fields_}
+
+
+class FetchStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("n_lines", "n_sites", "n_reverse", "n_bases", "n_hole_bases", "n_inverted", "n_no_contig",
+                                          "n_past_end", "n_before_start", "n_pieces")] + \
+               [(k, C.c_double) for k in ("s_total", "s_read", "s_index", "s_kernels", "s_write")]
+
+
+def ps_fetch_sequences(ref_fa, sites, out_file, bed=False):
+    """FetchSequencesForBindingSites / FetchSequencesForBEDFile.fetchSequences, the `fetch` (bed false) and `fetchBed` modes:
+    the reference sequence of every site of a table, gathered on the GPU from the index of ref_fa (.ann and .pac; the FASTA is
+    not opened); writes out_file and returns the counters"""
+    L = lib(); L.ps_fetch_sequences.argtypes = [C.c_char_p] * 3 + [C.c_int, C.POINTER(FetchStats)]
+    st = FetchStats()
+    _chk(L.ps_fetch_sequences(ref_fa.encode(), sites.encode(), out_file.encode(), int(bool(bed)), C.byref(st)))
+    return {f: getattr(st, f) for f, _ in FetchStats._fields_}
 
 
 def ps_map_profiled(threads, mm,error_profile, indel_profile, ref_fa, reads, out_sam, min_mapq, max_read_len, profile_prefix):

@@ -470,6 +470,17 @@ int ps_simulate_reads(const ps_simulate_opts *opts, ps_simulate_stats *stats)
     PS_CATCH_INT
 }
 
+// The toolkit's `fetch` and `fetchBed` modes (Main.java:883-945): FetchSequencesForBindingSites / FetchSequencesForBEDFile.fetchSequences.
+// The output is written under a temporary name and renamed: an error leaves none.
+int ps_fetch_sequences(const char *ref_fa, const char *sites, const char *out_file, int bed, ps_fetch_stats *stats)
+{
+    PS_TRY
+        const int dev = first_device();
+        fetch_run(ref_fa, sites, out_file, bed != 0, dev, stats);
+        return 0;
+    PS_CATCH_INT
+}
+
 int ps_sam_to_bam(const char *sam, const char *bam, int min_mapq, int sort_by_coordinate, int write_index, int threads, ps_bam_stats *st)
 {
     PS_TRY

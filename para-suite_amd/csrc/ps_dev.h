@@ -97,6 +97,19 @@ struct RefTables {
     }
 };
 
+// beside RefTables, for a mode that writes reference text (ps_fetch): per hole its character, upper-cased -- all the index keeps
+// of a hole's text, and with the packed strand all of the FASTA but the case of a, c, g and t
+struct RefHoleChars {
+    DevBuf<uint8_t> chr;
+    RefHoleChars(const Index &ix, hipStream_t s)
+    {
+        std::vector<uint8_t> c;
+        for (const Hole &h : ix.ref.holes) c.push_back((uint8_t)(h.amb >= 'a' && h.amb <= 'z' ? h.amb - 32 : h.amb));
+        upload(chr, c, s);
+        PS_HIP(hipStreamSynchronize(s));
+    }
+};
+
 // text -> file, checked; remove_failed: a file that could be opened but not written whole is removed
 inline void write_text_file(const std::string &path, const std::string &text, bool remove_failed = false)
 {

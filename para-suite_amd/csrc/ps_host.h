@@ -143,4 +143,7 @@ std::string benchmark_text(const ps_benchmark_stats &st, const BenchmarkRatios &
 // ---- PAR-CLIP reads drawn from transcripts (ps_simulate.hip; bin/createSimulatedPARCLIPDataset.pl) ----
 void simulate_run(const ps_simulate_opts &opts, int device, ps_simulate_stats *stats);
 
+// ---- the sequences of binding sites, gathered from the index's packed strand (ps_fetch.hip; FetchSequencesForBindingSites, FetchSequencesForBEDFile) ----
+void fetch_run(const char *ref_fa, const char *sites, const char *out_file, bool bed, int device, ps_fetch_stats *stats);
+
 }  // namespace ps

@@ -27,6 +27,17 @@ struct ProfRef {              // reference bases of one record with its holes
         if (k < n_holes && hole_off[k] <= p) return -1;
         return (pac[p >> 2] >> ((~p & 3) << 1)) & 3;
     }
+    // the same as text, for the modes that write sequence (ps_fetch): the base as a letter -- its complement with `comp` --
+    // and inside a hole the hole's upper-cased character, which has no complement
+    const uint8_t *hole_chr = nullptr;
+    __device__ int letter_at(int64_t p, bool comp) const
+    {
+        int k = h;
+        while (k < n_holes && hole_off[k] + hole_len[k] <= p) ++k;
+        if (k < n_holes && hole_off[k] <= p) return -(int)hole_chr[k];     // < 0: from a hole
+        const int code = (pac[p >> 2] >> ((~p & 3) << 1)) & 3;
+        return (0x54474341u >> ((comp ? 3 - code : code) << 3)) & 0xff;   // "ACGT"
+    }
 };
 
 }  // namespace ps

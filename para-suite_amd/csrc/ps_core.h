@@ -284,6 +284,7 @@ PS_HD size_t jump_words(int levels) { return (size_t)jump_level_off(levels) * PS
 // levels worth having: below them an interval is still wider than a fraction of a block on average
 PS_HD int jump_levels_for(bwtint seq_len) { int k = 0; while (k < PS_JUMP_MAX_LEVELS && (seq_len >> (2 * k)) >= 48) ++k; return k; }
 
+static const int PS_CHASE_MIN2 = 16;   // lanes of a wave that must want a second chase step for the wave to take it (PS_CHASE_MIN2 at run time)
 struct BtHot {
     const OccBlock *blocks; bwtint primary;
     const uint32_t *jump; uint32_t jump_levels;
@@ -293,6 +294,8 @@ struct BtHot {
     uint32_t p0, p1, p2, p3;
     uint32_t inv_c_min, max_entries, pool_cap, n_reads, big_cap;
     uint32_t c_min;                  // the cheapest difference, in units
+    uint32_t chase;                  // 0: no chase; else barren steps below the table take their match child's step in the same iteration (ps_narrow.h: nt_chase),
+                                     // and a second one while this many lanes of the wave want it (above 64: never)
     PS_HD int len() const { return (int)(p0 & 0xffu); }
     PS_HD int seed_len() const { return (int)((p0 >> 8) & 0xffu); }
     PS_HD int indel_end_skip() const { return (int)((p0 >> 16) & 0xffu); }
@@ -342,6 +345,7 @@ inline bool bt_hot_make(const BtArgs &a, BtHot &h)
     h.p2 = (uint32_t)md.s_gapo_ins | ((uint32_t)md.s_gape << 8) | ((uint32_t)md.s_gapo_del << 16) | ((uint32_t)md.s_stop << 24);
     h.p3 = (uint32_t)md.u_gapo_ins | ((uint32_t)md.u_gape << 8) | ((uint32_t)md.u_gapo_del << 16) | ((uint32_t)md.n_buckets << 24);
     h.c_min = (uint32_t)md.c_min;
+    h.chase = a.no_chase ? 0u : (uint32_t)(a.chase_min2 > 0 ? a.chase_min2 : PS_CHASE_MIN2);
     h.inv_c_min = (uint32_t)md.inv_c_min; h.max_entries = (uint32_t)md.max_entries; h.pool_cap = a.pool_cap; h.n_reads = (uint32_t)a.n_reads; h.big_cap = a.big_cap;
     return ok;
 }

@@ -114,7 +114,7 @@ __device__ __forceinline__ void pin_hot(BtHot &h, const BtHot &k)
 #pragma unroll
     for (int c = 0; c < 5; ++c) { h.s_pk[c] = pin32(k.s_pk[c]); h.u_pk[c] = pin32(k.u_pk[c]); }
     h.p0 = pin32(k.p0); h.p1 = pin32(k.p1); h.p2 = pin32(k.p2); h.p3 = pin32(k.p3);
-    h.c_min = pin32(k.c_min);
+    h.c_min = pin32(k.c_min); h.chase = pin32(k.chase);
     h.inv_c_min = pin32(k.inv_c_min); h.max_entries = pin32(k.max_entries); h.pool_cap = pin32(k.pool_cap); h.n_reads = pin32(k.n_reads); h.big_cap = pin32(k.big_cap);
 }
 

@@ -116,6 +116,23 @@ PS_HD void blk_count4b(const Blk &b, int r, uint32_t cnt[4])
     cnt[1] = b.x[1] + (A - C); cnt[2] = b.x[2] + (B - C); cnt[3] = b.x[3] + C;
 }
 
+// occurrences of ONE symbol s among the first r (0..192) symbols of the block, plus its running count: blk_count4b's entry s.  Per
+// word the plane bits are taken as they are or inverted, so that symbol s reads 1,1; then the prefix mask and one popcount --
+// a third of the four-symbol count (the chase below needs no more: a barren step follows one symbol)
+PS_HD uint32_t blk_count1b(const Blk &b, int r, int s)
+{
+    uint32_t n = 0;
+    const int q = r >> 5;
+    const uint32_t part = (1u << (r & 31)) - 1u;
+    const bool b0 = (s & 1) != 0, b1 = (s & 2) != 0;
+#pragma unroll
+    for (int j = 0; j < 6; ++j) {
+        const uint32_t m = j < q ? 0xFFFFFFFFu : (j == q ? part : 0u), lo = b.x[4 + j], hi = b.x[10 + j];
+        n += ps_popc((b0 ? lo : ~lo) & (b1 ? hi : ~hi) & m);
+    }
+    return sel4s(b.x[0], b.x[1], b.x[2], b.x[3], s) + n;
+}
+
 #ifndef PS_OCC_COND
 #define PS_OCC_COND 1       // 1: the block of row k-1 is loaded only where it is not the block of row l (exec-masked load +
 #endif                     // sixteen selects); 0: always (measured 7 % slower: the redundant requests cost the L1 more than the selects cost)
@@ -447,8 +464,31 @@ PS_HD void nt_step_occ(const BtHot &h, NLane &L, LaneStats &st, BtMem &m, NtStep
     else nt_jump(h, depth, L.kr, q.ck, q.cl);
 }
 
+// An expansion at position i is BARREN when it allows no difference: a child with a difference, at position i, would have to
+// afford D(i-1) = bnd_same more of them out of the mleft - 1 it has left, or -- inside the seed -- Ds = s1 more out of m_seed - 1.
+// Position 0 always allows differences.  One predicate for the expansion (nt_tail) and for the chase (nt_chase), which asks it of
+// the match child: the two cannot drift apart.
+// (nt_tail asks the two halves one by one, between its tests for the match-only case.  The half is a macro: as an inline function
+// of its own hipcc 7.2 schedules the expansion differently, and the kernel built with -DPS_CHASE=0 is to be the parent's.)
+#define nt_barren_by(bound, left) ((bound) > (left) - 1)
+PS_HD bool nt_barren(int i, int bnd_same, int mleft, bool in_seed, int s1, int m_seed)
+{
+    return i > 0 && (nt_barren_by(bnd_same, mleft) || (in_seed && nt_barren_by(s1, m_seed)));
+}
+// differences the seed's budget still pays for (e_un: the units the entry has used)
+PS_HD int nt_m_seed(const BtHot &h, int e_un)
+{
+    const int srem = h.seed_units() - e_un;                  // seed budget, in units like the read budget
+    return srem <= 0 ? 0 : (int)(ps_mul24((uint32_t)srem, h.inv_c_min) >> 16);
+}
+
+#ifndef PS_CHASE
+#define PS_CHASE 1            // 0: the chase below the jump table compiled out (A/B builds; at run time PS_CHASE=0, BtArgs::no_chase)
+#endif
+
+// returns whether the expansion was barren (and ran to its end: no exact extension, no full stack)
 template <bool STATS, bool NB32>
-PS_HD void nt_tail(const BtHot &h, NLane &L, LaneStats &st, BtMem &m, const NtStep &q, int mode)
+PS_HD bool nt_tail(const BtHot &h, NLane &L, LaneStats &st, BtMem &m, const NtStep &q, int mode)
 {
     const int len = nl_len(L), i = q.i, s = q.s;
     const uint32_t cw_i = q.cw_i, cw_im1 = q.cw_im1, cs_i = q.cs_i, cs_im1 = q.cs_im1;
@@ -460,19 +500,19 @@ PS_HD void nt_tail(const BtHot &h, NLane &L, LaneStats &st, BtMem &m, const NtSt
     if (mode == M_EXACT) {            // no difference left: extend exactly, one base per iteration (upstream's
         if (STATS) ++st.exact;        // bwt_match_exact_alt: no bound is looked at again until the read's first base)
         L.ctl = nl_set_mode(L.ctl, M_POP);
-        if (s > 3) return;
+        if (s > 3) return false;
         const uint32_t ok = sel4(ck, s), ol = sel4(cl, s);
-        if (ok >= ol) return;
+        if (ok >= ol) return false;
         L.kr = ctm ? (L.kr << 2) | (uint32_t)s : ok + 1u; L.lr = ctm ? ol - ok : ol; L.wa -= 1u; L.wb = (L.wb & ~NW_C_MASK) | ((uint32_t)s << 6);     // --i; the rest of the entry stands
         L.ctl = nl_set_mode(L.ctl, i == 0 ? M_HIT : M_EXACT);
-        return;
+        return false;
     }
     if (STATS) ++st.nodes;
     const uint32_t cap = (L.ctl & NL_BIG) ? h.big_cap : h.pool_cap;
     if (nl_bump(L) + 9u > cap) {          // stack full: ask for a large slot once; if that is full too, the read goes to the next tier
-        if (!(L.ctl & NL_BIG) && h.has_big()) { L.ctl = nl_set_mode(L.ctl, M_GROW); return; }
+        if (!(L.ctl & NL_BIG) && h.has_big()) { L.ctl = nl_set_mode(L.ctl, M_GROW); return false; }
         // a stack of 65,535 entries (a large slot, or the second tier's private one) is the deepest a 16-bit link reaches: straight to the wide tier
-        L.ctl = nl_set_mode(nl_set_status(L.ctl, cap >= 65535u ? RS_OVERFLOW_DEEP : RS_OVERFLOW_POOL), M_POP); return;
+        L.ctl = nl_set_mode(nl_set_status(L.ctl, cap >= 65535u ? RS_OVERFLOW_DEEP : RS_OVERFLOW_POOL), M_POP); return false;
     }
     const int max_units = nl_max_units(L);
     const int e_un = nt_units(h, L.wa, L.wb), e_sc = nw_score(L.wb);
@@ -480,16 +520,16 @@ PS_HD void nt_tail(const BtHot &h, NLane &L, LaneStats &st, BtMem &m, const NtSt
     const uint32_t inv = h.inv_c_min;
     const int mleft = (int)(ps_mul24((uint32_t)rem, inv) >> 16);
     const int srem = h.seed_units() - e_un;                  // seed budget, in units like the read budget
-    const int m_seed = srem <= 0 ? 0 : (int)(ps_mul24((uint32_t)srem, inv) >> 16);
-    bool allow_diff = true, allow_M = true;
+    const int m_seed = srem <= 0 ? 0 : (int)(ps_mul24((uint32_t)srem, inv) >> 16);       // == nt_m_seed(h, e_un)
     const int bnd_same = i > 0 ? (int)(cw_im1 & 0x7f) : 0;   // D bound a child at position i must still afford
     const int bnd_del = (int)(cw_i & 0x7f);                   // ... and a deletion child (it stays at i+1)
+    bool allow_diff = true, allow_M = true;                  // allow_diff == !nt_barren(i, bnd_same, mleft, in_seed, s1, m_seed)
     if (i > 0) {
-        if (bnd_same > mleft - 1) allow_diff = false;
+        if (nt_barren_by(bnd_same, mleft)) allow_diff = false;
         else if (bnd_same == mleft - 1 && bnd_del == mleft - 1 && (cw_i & 0x80u)) allow_M = false;
         if (in_seed) {
             const int s1 = (int)(cs_im1 & 0x7f), s0 = (int)(cs_i & 0x7f);
-            if (s1 > m_seed - 1) allow_diff = false;
+            if (nt_barren_by(s1, m_seed)) allow_diff = false;
             else if (s1 == m_seed - 1 && s0 == m_seed - 1 && (cs_i & 0x80u)) allow_M = false;
         }
     }
@@ -601,11 +641,15 @@ PS_HD void nt_tail(const BtHot &h, NLane &L, LaneStats &st, BtMem &m, const NtSt
     }
 #undef NT_NEXT
     L.ctl = nl_set_mode(L.ctl, M_POP);
-    if (s < 4 && xk[3] < xl[3]) {      // the match child: parent's score, pushed last => the next pop: it stays in registers
+    // (the chase's early drop: a match child whose own pop check -- mleft < D(i-1), nt_head -- would drop it is not kept for an iteration
+    // that only discards it.  Its parent was barren then, so nothing has moved since the parent's own checks.)
+    const bool doomed = PS_CHASE && h.chase != 0u && bnd_same > mleft;
+    if (s < 4 && xk[3] < xl[3] && !doomed) {      // the match child: parent's score, pushed last => the next pop: it stays in registers
         L.kr = ctm ? (pkr << 2) | (uint32_t)s : xk[3] + 1u; L.lr = ctm ? xl[3] - xk[3] : xl[3]; L.wa = wa_keep + (uint32_t)i; L.wb = (L.wb & ~NW_C_MASK) | ((uint32_t)s << 6);
         L.ctl |= NL_HAVE_CUR;
     }
     L.n_phantom += phantom;
+    return !allow_diff;
 }
 
 // ---- barren steps inside the jump table's levels, crossed at once ------------------------------------------------
@@ -748,6 +792,46 @@ PS_HD int nt_skip_land(NLane &L, const NtSkip &sk, int mode)
     return mode;
 }
 
+// ---- barren steps below the jump table: the chase -----------------------------------------------------------------
+// Below the table's levels a barren step is still the largest class of iterations (on the host lane machine, 8 Mbp and 50-bp
+// PAR-CLIP reads: 60 % of them, in runs of 2.35 on average), and there the LF step itself has to be taken.  A lane whose expansion
+// was barren holds its match child in the entry registers; if the child's own expansion is barren too, the lane takes the child's
+// step in the same iteration, for the child's ONE read base: one block, the count of one symbol at its two rows, and the grandchild
+// is the entry the next iteration starts from.  nt_skip's argument holds: between two barren steps the stack, n_phantom, the budget,
+// the best score and the bounds stand still, so every check nt_head would repeat for the child comes out as it did for the parent
+// (the virtual stack size, the status, the score against the best one); the child's bound check is the one new check, and nt_tail
+// has made it (the early drop).  Left to the normal step: a child inside the table (nt_skip's), at position 1 (its child is a hit,
+// position 0 always allows differences), with no difference left to pay for (it may turn to exact extension), on an N, and one
+// whose two rows lie in different blocks (5 % of the Occ pairs).  The Occ counters count the chased step as nt_occ would.
+// Returns whether the lane holds a chased entry that is still alive (a second chase step may follow: nt_iter).
+template <bool STATS>
+PS_HD bool nt_chase(const BtHot &h, NLane &L, LaneStats &st, const BtMem &m, const NtStep &q)
+{
+    const int i1 = nw_i(L.wa);                       // the child's position word (q.i of its parent): its own step is at i1 - 1
+    if (!(L.ctl & NL_HAVE_CUR) || q.ctm || i1 < 2) return false;
+    const int len = nl_len(L), i = i1 - 1;
+    const int e_un = nt_units(h, L.wa, L.wb);        // the parent's: a match costs nothing
+    const int mleft = (int)(ps_mul24((uint32_t)(nl_max_units(L) - e_un), h.inv_c_min) >> 16);
+    const int ii = i - (len - h.seed_len());
+    const bool in_seed = h.use_seed() && len > h.seed_len() && ii > 0;
+    const int bnd = (int)(m.cw[i - 1] & 0x7f), s1 = in_seed ? (int)(m.csw[ii - 1] & 0x7f) : 0;
+    const int s = nt_seq_at(m, L, i, len, h.len());
+    if (mleft == 0 || s > 3 || !nt_barren(i, bnd, mleft, in_seed, s1, nt_m_seed(h, e_un))) return false;
+    const bwtint base = nt_base(h, nw_c(L.wb));      // never the root: the child has consumed a symbol
+    int ol_ = 0, ok_ = 0;
+    const uint32_t bl = blk_of(row_to_stored(h.primary, base + L.lr), ol_), bk = blk_of(row_to_stored(h.primary, base + (bwtint)(L.kr - 1u)), ok_);
+    if (bk != bl) return false;
+    ++st.pairs; ++st.same;
+    if (STATS) ++st.nodes;
+    if (bnd > mleft) { L.ctl &= ~NL_HAVE_CUR; return false; }      // the grandchild's pop would drop it (the early drop of nt_tail, one step on): no need to look
+    Blk x;
+    load_blk(h.blocks, bl, x);
+    const uint32_t ck = blk_count1b(x, ok_ + 1, s), cl = blk_count1b(x, ol_ + 1, s);
+    if (ck >= cl) { L.ctl &= ~NL_HAVE_CUR; return false; }         // the text does not hold the string: the child dies as its own step would let it
+    L.kr = ck + 1u; L.lr = cl; L.wa -= 1u; L.wb = (L.wb & ~NW_C_MASK) | ((uint32_t)s << 6);
+    return true;
+}
+
 template <bool STATS, bool NB32>
 PS_HD void nt_iter(const BtArgs &a, const BtHot &h, NLane &L, LaneStats &st, BtMem &m, int fetch_r, bool serve_hit, NtClock *clk = nullptr)
 {
@@ -770,7 +854,22 @@ PS_HD void nt_iter(const BtArgs &a, const BtHot &h, NLane &L, LaneStats &st, BtM
     if (STATS && clk && mode) asm volatile("" :: "v"(q.ck[0]), "v"(q.cl[0]), "v"(q.ck[3]), "v"(q.cl[3]));
 #endif
     PS_USTAMP(clk, 2);                                   // the memory step
-    if (mode) nt_tail<STATS, NB32>(h, L, st, m, q, mode);
+    bool barren = false;
+    if (mode) barren = nt_tail<STATS, NB32>(h, L, st, m, q, mode);
+    bool chased = false;
+    if (PS_CHASE && h.chase != 0u && barren) chased = nt_chase<STATS>(h, L, st, m, q);
+#if PS_CHASE
+    {   // a second step of the run (the host lane machine: 0.73 -> 0.64 of the iterations), entered by the whole wave, and so only while
+        // at least h.chase of its lanes want it: every lane of the wave waits for the one more dependent load
+#ifdef __HIP_DEVICE_COMPILE__
+        const bool enough = __popcll(__ballot(chased)) >= (int)h.chase;
+#else
+        const bool enough = h.chase <= 64u;          // one lane at a time here: as a wave all of whose lanes want it
+#endif
+        if (enough && chased) nt_chase<STATS>(h, L, st, m, q);
+    }
+#endif
+    (void)chased;
     PS_USTAMP(clk, 3);                                   // exact extension / expansion and pushes
 }
 

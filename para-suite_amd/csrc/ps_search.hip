@@ -132,7 +132,7 @@ static void run_search(Batch &b, const SearchKnobs &kn, const Model &md, int n, 
     a.bases = d_bases; a.nmask = d_nmask; a.n_bw = (len + 15) / 16; a.n_mw = (len + 31) / 32;
     a.alns = alns; a.aln_cap = aln_cap; a.n_aln = n_aln; a.status = status;
     a.pool_cap = pool_cap; a.wide = wide ? 1 : 0; a.stats = b.d_stats.p + 1; a.fetch_min = kn.fetch_min; a.hit_min = kn.hit_min;
-    a.no_skip = kn.skip ? 0 : 1;
+    a.no_skip = kn.skip ? 0 : 1; a.no_chase = kn.chase ? 0 : 1; a.chase_min2 = kn.chase_min2;
     // width -> effort -> model -> sort -> search launch go to the stream back to back: the host reads the stage times only after
     // the search launch's own end (a wait after every stage put a host round trip, each behind a full machine, in front of the launch)
     EventPair t_width; std::optional<EventPair> t_order;

@@ -19,6 +19,8 @@ struct SearchKnobs {
     int max_per_cu = PS_SEARCH_WAVES;   // workgroups per CU the kernel's registers allow (ps_kernels.hip: PS_BT_WAVES)
     bool cap = true; int cap_bias = 0;  // the first tier spares entries by the estimate; tests: estimates too low by that much, so that the restart path runs
     bool skip = true;                   // barren steps inside the jump table's levels are crossed in one iteration (ps_narrow.h: nt_skip)
+    int chase_min2 = PS_CHASE_MIN2;     // lanes of a wave that must want the second chase step of an iteration (65: never)
+    bool chase = true;                  // ... and below them a barren step takes its match child's step in the same iteration (ps_narrow.h: nt_chase)
     int fetch_min = 8, hit_min = 1;     // tuning: the context's values unless set at search time
 };
 inline SearchKnobs search_knobs_from_env(int ctx_fetch_min, int ctx_hit_min)
@@ -35,6 +37,8 @@ inline SearchKnobs search_knobs_from_env(int ctx_fetch_min, int ctx_hit_min)
     if (env_int("PS_CAP", v)) k.cap = v != 0;
     if (env_int("PS_CAP_BIAS", v)) k.cap_bias = std::max(0, std::min(200, v));
     if (env_int("PS_SKIP", v)) k.skip = v != 0;
+    if (env_int("PS_CHASE", v)) k.chase = v != 0;
+    if (env_int("PS_CHASE_MIN2", v)) k.chase_min2 = std::max(1, std::min(65, v));
     if (env_int("PS_FETCH_MIN", v)) k.fetch_min = std::max(1, v);
     if (env_int("PS_HIT_MIN", v)) k.hit_min = std::max(1, v);
     return k;

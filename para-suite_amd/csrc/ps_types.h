@@ -115,6 +115,8 @@ struct BtArgs {
     const uint8_t *est; const uint16_t *est_ab;       // the effort estimate the order was made from (est: the predicted score of the best hit, in budget units); est_ab, optional (profiling): its two scans
     int cap_est;                                      // first tier, profile costs: children that can only matter if the best hit is worse than est are not stored (ps_narrow.h: nt_tail); 1 + what tests subtract from est
     int no_skip;                                      // 0: entries inside the jump table's levels cross their barren steps in one iteration (ps_narrow.h: nt_skip); 1: off (PS_SKIP=0)
+    int no_chase;                                     // 0: a barren step below the table takes its match child's step in the same iteration (ps_narrow.h: nt_chase); 1: off (PS_CHASE=0)
+    int chase_min2;                                   // lanes of a wave that must want a second chase step for the wave to take it (0: the default, PS_CHASE_MIN2; above 64: one step only)
     uint32_t *read_iters;                             // optional per-read profile (narrow tiers' counting kernel), PS_RI_WORDS words per read: iterations spent | stack slots used |
                                                       // D bound of the whole read, of the seed <<8, the estimate's two scans <<16, <<24 | best score, final budget <<8, hits <<16 | 16 words: the D bounds
     int hit_min;                                      // lanes with a pending hit a wave collects before it records them

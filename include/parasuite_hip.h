@@ -60,6 +60,48 @@ int ps_index(const char *ref_fa);
 int ps_map(int threads, const char *mm, const char *error_profile, const char *indel_profile,
            const char *ref_fa, const char *fastq, const char *out_sam);
 
+/* ---- the search options of `bwa aln` and `bwa samse` beyond -n / -X ----------------------------------------------------------
+ * Defaults are upstream's (BWA 0.7.x gap_opt_t; samse -n 3): with them, or with NULL, every call computes what it computed before
+ * these options existed.  A value is accepted where the result is exactly upstream's rule; anything else is refused before any
+ * launch with the field and its limit in ps_last_error() -- never clamped into a different result:
+ *   max_gap_opens       0..7   the narrow stack entry counts opens in 3 bits, and 2*7 + 1 CIGAR operations fit a ps_hit; -o 8 is refused
+ *   max_gap_extensions  ..15   the launch header's 4 bits; -e 16 is refused.  Every value below 1 is the k-difference mode
+ *   indel_end_skip      0..    255 and up mean "no gap anywhere": no read is longer than 250 bp
+ *   max_del_occ         0..255
+ *   seed_len            1..    from the read length on: no seed
+ *   max_seed_diff       0..4095 (stock), 0..511 (profile costs count a difference as 8 units; 12 bits of units in the launch header)
+ *   max_entries         1..2000000   what the largest search tier holds, and upstream's default
+ *   s_mm, s_gapo, s_gape  0..255 each; together with -n they also decide the number of score buckets, at most PS_MAX_BUCKETS = 128:
+ *                       a table past that fails at ps_batch_from_fastq / ps_batch_from_codes / ps_map_opts, as a -n out of range does
+ *   max_top2            0..    255 and up take the wide search stack
+ *   max_alt_hits        0..    0: no XA tag
+ * A launch whose gap limits add up to more than 7 (-o 2 and up in the k-difference mode, -e 7 and up) takes the wide search stack,
+ * whose entries count in bytes.  A gapped hit whose CIGAR comes out of the banded alignment with more than 16 operations fails the
+ * call (16 are what a ps_hit holds).
+ * Not built: -q read trimming and -N (the oracle has neither); the shim refuses them.  ps_map_to_bam, ps_map_profiled and
+ * ps_map_route keep the defaults: ps_route_opts has no size field to grow by. */
+typedef struct {
+    uint32_t struct_size;          /* sizeof(ps_search_opts): a caller built against a shorter struct still works, the fields it lacks keep their defaults */
+    int32_t max_gap_opens;         /* aln -o  [1]  */
+    int32_t max_gap_extensions;    /* aln -e  [-1]: < 1 = k-difference mode (at most 6 extensions, each counts as a difference);
+                                      >= 1 = that many, and they do not count as differences */
+    int32_t indel_end_skip;        /* aln -i  [5]  */
+    int32_t max_del_occ;           /* aln -d  [10] */
+    int32_t seed_len;              /* aln -l  [32]; a value >= the read length means no seed */
+    int32_t max_seed_diff;         /* aln -k  [2]  */
+    int32_t max_entries;           /* aln -m  [2000000] */
+    int32_t s_mm, s_gapo, s_gape;  /* aln -M -O -E [3 11 4]; stock mode only: the profile's costs replace them */
+    int32_t max_top2;              /* aln -R  [30] */
+    int32_t max_alt_hits;          /* samse -n [3] */
+} ps_search_opts;
+void ps_search_opts_default(ps_search_opts *);
+/* host only (needs no device): 0 if every field lies in its range, else 1 and ps_last_error() names the field and its limit.
+ * profile_mode != 0: the ranges under an error profile (max_seed_diff).  NULL: the defaults, 0 */
+int  ps_search_opts_check(const ps_search_opts *, int profile_mode);
+/* ps_map with search options; NULL: ps_map.  The options reach every device worker of the streaming pass */
+int  ps_map_opts(int threads, const char *mm, const char *error_profile, const char *indel_profile,
+                 const char *ref_fa, const char *fastq, const char *out_sam, const ps_search_opts *opts);
+
 /* ---- staged interface (same code path as ps_map; used by the argv shim, tests and bench.py) ---- */
 typedef struct ps_ctx ps_ctx;
 typedef struct ps_batch ps_batch;
@@ -72,6 +114,10 @@ void    ps_ctx_close(ps_ctx *);
 int     ps_ctx_set_stock(ps_ctx *, const char *n_arg);               /* bwa aln -n */
 int     ps_ctx_set_profile(ps_ctx *, const char *error_profile, const char *indel_profile, const char *x_arg);
 int     ps_ctx_set_profile_matrix(ps_ctx *, const double P[16], double ins_rate, double del_rate, int x);
+/* the search options are a part of the context of their own: ps_ctx_set_stock / ps_ctx_set_profile* replace the cost part and keep
+ * them, in either order of calls.  NULL: back to the defaults.  Checked here under the cost part in force, and again by a later
+ * ps_ctx_set_profile* (max_seed_diff 512..4095 is stock only); batches made afterwards search with them */
+int     ps_ctx_set_search(ps_ctx *, const ps_search_opts *);
 int     ps_ctx_set_tiers(ps_ctx *, const uint32_t pool_cap[3], const int32_t aln_cap[3], int bt_blocks);
 /* measurement runs: the search kernel of the following launches counts its search steps, pushes, pops ... and walks the plain Occ
  * blocks (no jump table): the counts are those of the reference algorithm (ps_batch_kstats, which = 1).  The default kernel

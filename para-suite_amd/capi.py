@@ -33,6 +33,32 @@ class KStats(C.Structure):
                                           "exact_steps")]
 
 
+class SearchOpts(C.Structure):
+    """ps_search_opts: the search options of `bwa aln` / `bwa samse` beyond -n / -X, upstream's defaults unless named:
+    SearchOpts(max_gap_opens=2, seed_len=20).  Ranges: include/parasuite_hip.h; check() asks the library (host only)."""
+    _fields_ = [("struct_size", C.c_uint32)] + [(k, C.c_int32) for k in (
+        "max_gap_opens", "max_gap_extensions", "indel_end_skip", "max_del_occ", "seed_len", "max_seed_diff", "max_entries",
+        "s_mm", "s_gapo", "s_gape", "max_top2", "max_alt_hits")]
+
+    def __init__(self, **kw):
+        super().__init__()
+        lib().ps_search_opts_default(C.byref(self))
+        for k, v in kw.items():
+            if k not in dict(self._fields_) or k == "struct_size":
+                raise TypeError("SearchOpts has no option " + k)
+            setattr(self, k, int(v))
+
+    def check(self, profile_mode=False):
+        _chk(lib().ps_search_opts_check(C.byref(self), 1 if profile_mode else 0))
+
+
+def _search_ptr(search):
+    """a SearchOpts, a dict of its fields, or None (the defaults)"""
+    if search is None:
+        return None
+    return C.byref(search if isinstance(search, SearchOpts) else SearchOpts(**search))
+
+
 ALN_DTYPE = np.dtype([("k", "<u8"), ("l", "<u8"), ("score", "<u2"), ("units", "<u2"), ("n_mm", "u1"), ("n_gapo", "u1"),
                       ("n_gape", "u1"), ("n_ins", "u1"), ("n_del", "u1"), ("pad", "u1", 7)])
 HIT_DTYPE = np.dtype([("pos", "<i8"), ("sa", "<u8"), ("type", "<i4"), ("strand", "<i4"), ("mapq", "<i4"), ("n_mm", "<i4"),
@@ -40,6 +66,7 @@ HIT_DTYPE = np.dtype([("pos", "<i8"), ("sa", "<u8"), ("type", "<i4"), ("strand",
                       ("c2", "<i4"), ("n_cigar", "<i4"), ("n_multi", "<i4"), ("cigar", "<u4", 16)], align=True)
 
 EXPORTS = ["ps_version", "ps_last_error", "ps_index", "ps_map", "ps_ctx_open", "ps_ctx_build", "ps_ctx_close",
+           "ps_search_opts_default", "ps_search_opts_check", "ps_ctx_set_search", "ps_map_opts",
            "ps_ctx_set_stock", "ps_ctx_set_profile", "ps_ctx_set_profile_matrix", "ps_ctx_set_tiers", "ps_ctx_set_stats", "ps_ctx_set_lanes", "ps_ctx_info",
            "ps_ctx_blob", "ps_ctx_meta", "ps_ctx_from_blobs", "ps_ctx_clone", "ps_ctx_fetch", "ps_ctx_export_blob", "ps_ctx_sa_lookup", "ps_ctx_order_sort", "ps_ctx_index_check", "ps_sam_to_bam", "ps_map_to_bam", "ps_bam_view", "ps_bam_sort", "ps_bam_index", "ps_batch_from_fastq",
            "ps_batch_from_codes", "ps_batch_free", "ps_batch_n", "ps_batch_search", "ps_batch_select_hard",
@@ -61,6 +88,11 @@ def lib():
     L.ps_last_error.restype = C.c_char_p
     L.ps_index.argtypes = [C.c_char_p]
     L.ps_map.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
+    L.ps_map_opts.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P(SearchOpts)]
+    L.ps_search_opts_default.argtypes = [P(SearchOpts)]
+    L.ps_search_opts_default.restype = None
+    L.ps_search_opts_check.argtypes = [P(SearchOpts), C.c_int]
+    L.ps_ctx_set_search.argtypes = [C.c_void_p, P(SearchOpts)]
     L.ps_ctx_open.argtypes = [C.c_char_p, C.c_int]
     L.ps_ctx_open.restype = C.c_void_p
     L.ps_ctx_build.argtypes = [C.c_char_p, C.c_int, C.c_int]
@@ -160,6 +192,10 @@ class Ctx:
 
     def set_stock(self, n="0.04"):
         _chk(lib().ps_ctx_set_stock(self.h, str(n).encode()))
+
+    def set_search(self, search=None, **kw):
+        """the search options (SearchOpts, a dict, or keywords; None: the defaults): kept when set_stock / set_profile change the costs"""
+        _chk(lib().ps_ctx_set_search(self.h, _search_ptr(kw if search is None and kw else search)))
 
     def set_profile_files(self, ep, ip, x="-1"):
         _chk(lib().ps_ctx_set_profile(self.h, ep.encode(), ip.encode() if ip else None, str(x).encode()))
@@ -488,10 +524,14 @@ def ps_index(ref_fa):
     _chk(lib().ps_index(ref_fa.encode()))
 
 
-def ps_map(threads, mm, error_profile, indel_profile, ref_fa, fastq, out_sam):
-    _chk(lib().ps_map(int(threads), str(mm).encode(), error_profile.encode() if error_profile else None,
-                      indel_profile.encode() if indel_profile else None, ref_fa.encode(), fastq.encode(),
-                      out_sam.encode()))
+def ps_map(threads, mm, error_profile, indel_profile, ref_fa, fastq, out_sam, search=None):
+    """search: a SearchOpts or a dict of its fields (`ps_map_opts`); None: `ps_map`"""
+    args = (int(threads), str(mm).encode(), error_profile.encode() if error_profile else None,
+            indel_profile.encode() if indel_profile else None, ref_fa.encode(), fastq.encode(), out_sam.encode())
+    if search is None:
+        _chk(lib().ps_map(*args))
+    else:
+        _chk(lib().ps_map_opts(*args, _search_ptr(search)))
 
 
 class BamStats(C.Structure):

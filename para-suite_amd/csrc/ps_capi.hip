@@ -83,10 +83,20 @@ int ps_ctx_set_stock(ps_ctx *x, const char *n_arg) { PS_TRY x->c.set_stock(n_arg
 int ps_ctx_set_profile_matrix(ps_ctx *x, const double P[16], double ins, double del, int xarg)
 {
     PS_TRY
-        Options o; profile_costs(o, P, ins, del, xarg); x->c.opt = o; return 0;
+        x->c.set_profile_matrix(P, ins, del, xarg); return 0;
     PS_CATCH_INT
 }
 int ps_ctx_set_profile(ps_ctx *x, const char *ep, const char *ip, const char *x_arg) { PS_TRY x->c.set_profile(ep, ip, x_arg); return 0; PS_CATCH_INT }
+void ps_search_opts_default(ps_search_opts *o) { if (o) search_opts_default(*o); }
+int ps_search_opts_check(const ps_search_opts *o, int profile_mode)
+{
+    PS_TRY
+        std::string err;
+        if (!search_opts_check(o, profile_mode != 0, err)) throw Error(err);
+        return 0;
+    PS_CATCH_INT
+}
+int ps_ctx_set_search(ps_ctx *x, const ps_search_opts *o) { PS_TRY x->c.set_search(o); return 0; PS_CATCH_INT }
 // SA[row] for arbitrary rows of the BW matrix (LF walk to a sampled row: the kernel the samse stage uses): index checks
 // every row of the index against the text (ps_kernels.hip: k_index_check): out = rows visited (must be seq_len + 1), BWT symbols that differ
 // from the text, SA samples that differ from the position counted along the LF cycle, longest arc between two samples
@@ -338,6 +348,13 @@ int ps_map(int threads, const char *mm, const char *error_profile, const char *i
 {
     PS_TRY
         map_to_sam(MapArgs{threads, mm, error_profile, indel_profile, ref_fa, fastq}, out_sam); return 0;
+    PS_CATCH_INT
+}
+int ps_map_opts(int threads, const char *mm, const char *error_profile, const char *indel_profile,
+                const char *ref_fa, const char *fastq, const char *out_sam, const ps_search_opts *opts)
+{
+    PS_TRY
+        map_to_sam(MapArgs{threads, mm, error_profile, indel_profile, ref_fa, fastq, opts}, out_sam); return 0;
     PS_CATCH_INT
 }
 int ps_map_profiled(int threads, const char *mm, const char *error_profile, const char *indel_profile,

@@ -200,6 +200,7 @@ Pass::Pass(MapJob &j) : job(j), nthr(j.a.threads > 0 ? j.a.threads : 1), set(j.r
     for (int g = 0; g < G; ++g) {
         if (!set.xs[g]) set.xs[g].reset(new Ctx(dev.devs[g]));
         ctx(g).set_options(job.a.mm, job.a.error_profile, job.a.indel_profile);
+        ctx(g).set_search(job.a.search);                   // after the cost part: checked under it.  Every device's context, so every worker
         ctx(g).host_threads = nthr;
         ctx(g).n_work = dev.workers[g];
     }

@@ -32,6 +32,53 @@ struct Options {
     int n_cost = 1, gapo_ins_cost = 1, gapo_del_cost = 1, gape_cost = 1;
 };
 
+// ---- the search options of `bwa aln` / `bwa samse` beyond -n / -X ----
+// A context keeps them apart from the cost part (-n, or the profile and -X): set_stock / set_profile replace the cost part, with_search()
+// lays the search part over it.  The public struct's conversion and range check: ps_search_opts.h.
+struct SearchPart {
+    int max_gapo = 1, max_gape = 6, mode_gape = 1;
+    int indel_end_skip = 5, max_del_occ = 10, max_entries = 2000000;
+    int seed_len = 32, max_seed_diff = 2, max_top2 = 30;
+    int s_mm = 3, s_gapo = 11, s_gape = 4;
+    int n_occ = 3;
+};
+static const int PS_MAX_GAPO = 7;           // the narrow stack entry counts gap opens in 3 bits; 2*7 + 1 CIGAR operations fit PS_HIT_CIGAR
+static const int PS_MAX_GAPE = 15;          // the launch header's 4 bits (ps_core.h: BtHot::p1)
+static const int PS_MAX_ENTRIES = 2000000;  // what the wide tier's stack holds (ps_pipeline.h: Ctx::pool_cap[2]) and upstream's own default
+
+// the cost part (a fresh Options after set_stock_n / profile_costs) with the search part laid over it.  -M/-O/-E are stock scores: under
+// a profile make_model takes the profile's costs and never reads them
+inline Options with_search(Options cost, const SearchPart &p)
+{
+    cost.max_gapo = p.max_gapo; cost.max_gape = p.max_gape; cost.mode_gape = p.mode_gape;
+    cost.indel_end_skip = p.indel_end_skip; cost.max_del_occ = p.max_del_occ; cost.max_entries = p.max_entries;
+    cost.seed_len = p.seed_len; cost.max_seed_diff = p.max_seed_diff; cost.max_top2 = p.max_top2;
+    cost.s_mm = p.s_mm; cost.s_gapo = p.s_gapo; cost.s_gape = p.s_gape;
+    cost.n_occ = p.n_occ;
+    return cost;
+}
+// The two parts of a context's options and the one place they are merged (ps_pipeline.h: Ctx is one of these).  Either setter leaves
+// the other part alone, so the order of ps_ctx_set_search and ps_ctx_set_stock / ps_ctx_set_profile does not matter.
+struct OptionParts {
+    Options opt;                   // what the batches read: the cost part (-n, or the profile and -X) with the search part laid over it
+    SearchPart search;             // kept when the cost part is replaced
+    bool set_cost(const Options &cost, std::string &err)
+    {
+        // the search part was in range when it was set; the one range that depends on the cost part is the seed's budget in the launch header
+        if (cost.profile && search.max_seed_diff * cost.unit > 4095) {
+            err = "ps_search_opts: max_seed_diff (aln -k) is " + std::to_string(search.max_seed_diff) + ", accepted under an error profile: 0 to " + std::to_string(4095 / cost.unit);
+            return false;
+        }
+        opt = with_search(cost, search);
+        return true;
+    }
+    void set_search(const SearchPart &p)                             // p: checked (ps_search_opts.h: search_part_from)
+    {
+        search = p;
+        opt = with_search(opt, search);                              // the cost fields of opt are the cost part: with_search writes the others
+    }
+};
+
 // smallest k whose Poisson(l*err) upper tail drops below thres (BWA's per-length difference budget)
 inline int cal_maxdiff(int l, double err, double thres)
 {
@@ -186,7 +233,12 @@ inline bool make_model(const Options &o, int len, Model &m, std::string &err)
         return false;
     }
     if (len > PS_MAX_LEN) { err = "read longer than PS_MAX_LEN (" + std::to_string(len) + " bp, at most " + std::to_string(PS_MAX_LEN) + ")"; return false; }
-    if (m.max_gapo > 7 || m.max_gape > 7) { err = "gap limits above 7 are not supported by the packed stack entry"; return false; }
+    // what the tiers hold: the narrow entry counts opens, extensions and inserted / deleted bases in 3 bits each (launch_is_wide sends a
+    // model with max_gapo + max_gape > 7 to the wide stack, whose counts are bytes), the launch header has 4 bits for either limit
+    if (m.max_gapo > PS_MAX_GAPO || m.max_gape > PS_MAX_GAPE) {
+        err = "gap limits: at most " + std::to_string(PS_MAX_GAPO) + " opens (-o) and " + std::to_string(PS_MAX_GAPE) + " extensions (-e) are supported";
+        return false;
+    }
     if (m.max_units / m.c_min > 126) { err = "difference budget too large"; return false; }
     return true;
 }

@@ -6,18 +6,19 @@
 #include <memory>
 #include <mutex>
 #include "ps_host.h"
+#include "ps_search_opts.h"
 #include "ps_reads.h"
 #include "ps_bam.h"
 
 namespace ps {
 
-static const int PS_HIT_CIGAR = 8;
+static const int PS_HIT_CIGAR = PS_MAX_CIGAR;   // what the banded alignment hands back and a ps_hit holds: 2 * max_gapo + 1 operations for every accepted -o
 struct Multi { int64_t pos; bwtint row; int32_t gap, mm, ref_shift, strand, n_cigar; uint32_t cigar[PS_MAX_CIGAR]; };
 struct Hit {
     int64_t pos; bwtint sa;
     int32_t type, strand, mapq, n_mm, n_gapo, n_gape, ref_shift, score, c1, c2, n_cigar;
     int32_t multi_begin, n_multi;
-    uint32_t cigar[PS_HIT_CIGAR];    // gapped main hits with more operations are rejected (needs max_gapo > 2)
+    uint32_t cigar[PS_HIT_CIGAR];    // a gapped hit whose alignment has more operations fails the call (ps_samse.hip: take_cigar)
 };
 
 static const uint8_t PS_CLS_HOST = 4;   // bit of a read's class (Batch::h_class): finished on the host (Batch::sub), not by the device records below
@@ -68,12 +69,11 @@ struct Work {
     ~Work() { if (stream) (void)hipStreamDestroy(stream); }
 };
 
-struct Ctx {
+struct Ctx : OptionParts {          // opt, search: the options in their two parts (ps_model.h)
     int device = 0;
     hipStream_t stream = nullptr;    // index build / load
     hipEvent_t ref_event = nullptr;  // the context's clock: recorded once at creation
     Index ix;
-    Options opt;
     int cus = 256;                 // compute units of the device, read once by attach_device()
     int bt_blocks = 0;             // grid of the backtracking kernel (0 = 4 blocks per CU)
     uint32_t pool_cap[3] = {16384, 65535, 2000064};   // stack entries per lane: 16-byte narrow tiers, then the wide tier
@@ -97,6 +97,8 @@ struct Ctx {
     void attach_device();          // needs a HIP device (stream, clock, CU count); a second call does nothing
     void set_stock(const char *n_arg);                                            // bwa aln's -n
     void set_profile(const char *ep, const char *ip, const char *x_arg);          // the two profile files and -X
+    void set_profile_matrix(const double P[16], double ins, double del, int x);
+    void set_search(const ps_search_opts *o);                                     // NULL: the defaults; throws what ps_search_opts_check names
     void set_options(const char *mm, const char *ep, const char *ip) { if (ep && ep[0]) set_profile(ep, ip, mm); else set_stock(mm && mm[0] ? mm : "0.04"); }   // a mapping call's three arguments
     ~Ctx();
 };

@@ -48,13 +48,25 @@ void Ctx::set_stock(const char *n_arg)
 {
     Options o; set_stock_n(o, n_arg);
     if (o.max_diff < 0 && !(o.fnr > 0.0)) throw Error("bad -n argument");
-    opt = o;
+    std::string err;
+    if (!set_cost(o, err)) throw Error(err);
 }
 void Ctx::set_profile(const char *ep, const char *ip, const char *x_arg)
 {
     double P[16], ins, del; std::string err;
     if (!read_profile_files(ep, ip, P, ins, del, err)) throw Error(err);
-    Options o; profile_costs(o, P, ins, del, x_arg ? std::atoi(x_arg) : -1); opt = o;
+    set_profile_matrix(P, ins, del, x_arg ? std::atoi(x_arg) : -1);
+}
+void Ctx::set_profile_matrix(const double P[16], double ins, double del, int x)
+{
+    Options o; profile_costs(o, P, ins, del, x);
+    std::string err;
+    if (!set_cost(o, err)) throw Error(err);
+}
+void Ctx::set_search(const ps_search_opts *in)
+{
+    std::string err;
+    if (!ps::set_search(*this, in, err)) throw Error(err);
 }
 Ctx::~Ctx() { if (ref_event) (void)hipEventDestroy(ref_event); if (stream) (void)hipStreamDestroy(stream); }
 void ctx_release_device(Ctx &c)

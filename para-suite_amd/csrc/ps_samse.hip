@@ -243,7 +243,7 @@ void batch_select_easy(Batch &b, int threads)
                 if (n_occ > 0) {                     // alternative hits (samse -n): only if all occurrences of all hits number <= n_occ+1
                     int tot = 0;
                     for (int k = 0; k < na; ++k) tot += (int)((uint64_t)(sr.alns[k].l - sr.alns[k].k) + 1ull);
-                    if (tot >= 0 && tot <= n_occ + 1)
+                    if (tot >= 0 && (long long)tot <= (long long)n_occ + 1)
                         for (int k = 0; k < na; ++k)
                             for (uint64_t row = sr.alns[k].k; row <= sr.alns[k].l; ++row) {
                                 Multi m; std::memset(&m, 0, sizeof m);
@@ -286,6 +286,18 @@ static int fix_cigar(uint32_t *cigar, int n, int64_t &rb)
     if ((cigar[n - 1] & 0xf) == 2) --n;                                            // trailing deletion dropped
     if (n > 0 && (cigar[0] & 0xf) == 2) { rb += cigar[0] >> 4; --n; std::memmove(cigar, cigar + 1, (size_t)n * 4); }
     return n;
+}
+
+// The cleaned-up CIGAR of a gapped hit as the batch keeps it.  The banded alignment hands back at most PS_MAX_CIGAR operations and drops
+// what does not fit: the rest then no longer spans the whole read (read_len bases) or the whole reference window (ref_len bases).
+// (Up to 2 * max_gapo + 1 operations come from the search; the alignment may trade two mismatches for one more gap.)
+static int take_cigar(uint32_t *cigar, int n, int64_t &rb, int read_len, int ref_len)
+{
+    static_assert(PS_HIT_CIGAR == PS_MAX_CIGAR, "a Hit holds what the banded alignment hands back");
+    int on_read = 0, on_ref = 0;
+    for (int j = 0; j < n; ++j) { const int l = (int)(cigar[j] >> 4), op = (int)(cigar[j] & 0xf); if (op != 2) on_read += l; if (op != 1) on_ref += l; }
+    if (n > 0 && (on_read != read_len || on_ref != ref_len)) throw Error("CIGAR with more than " + std::to_string(PS_HIT_CIGAR) + " operations (PS_HIT_CIGAR); lower -o");
+    return fix_cigar(cigar, n, rb);
 }
 
 // banded DP kernel over a list of items of one length bin; cigars come back to the host
@@ -362,8 +374,7 @@ void batch_locate(Batch &b)
             const int64_t g = gs[q];
             uint32_t *c = cig.data() + (size_t)q * PS_MAX_CIGAR;
             int64_t rb = b.h_fin[g].pos;
-            const int n_c = fix_cigar(c, nc[q], rb);
-            if (n_c > PS_HIT_CIGAR) throw Error("CIGAR with more than 8 operations (raise PS_HIT_CIGAR for max_gapo > 2)");
+            const int n_c = take_cigar(c, nc[q], rb, b.rs.len[g], b.rs.len[g] + b.h_sel[g].ref_shift);
             DevCigar dc; dc.g = g; dc.n = n_c; std::memcpy(dc.c, c, sizeof dc.c);
             b.dev_cigars.push_back(dc);
             b.h_fin[g].pos = rb;
@@ -436,15 +447,14 @@ void batch_locate(Batch &b)
                 uint32_t *c = cig.data() + (size_t)q * PS_MAX_CIGAR;
                 if (bk.multi < 0) {
                     int64_t rb = h.pos;
-                    h.n_cigar = fix_cigar(c, nc[q], rb);
-                    if (h.n_cigar > PS_HIT_CIGAR) throw Error("CIGAR with more than 8 operations (raise PS_HIT_CIGAR for max_gapo > 2)");
+                    h.n_cigar = take_cigar(c, nc[q], rb, b.rs.len[b.sub[bk.q].g], b.rs.len[b.sub[bk.q].g] + h.ref_shift);
                     std::memcpy(h.cigar, c, sizeof h.cigar);
                     h.pos = rb;
                     if (h.n_cigar == 0) h.type = 0;
                 } else {
                     Multi &m = b.multis[h.multi_begin + bk.multi];
                     int64_t rb = m.pos;
-                    m.n_cigar = fix_cigar(c, nc[q], rb);
+                    m.n_cigar = take_cigar(c, nc[q], rb, b.rs.len[b.sub[bk.q].g], b.rs.len[b.sub[bk.q].g] + m.ref_shift);
                     std::memcpy(m.cigar, c, sizeof m.cigar);
                     m.pos = rb;
                 }

@@ -33,6 +33,12 @@ class Mapping:
 
     def __init__(self):
         self._t0 = None
+        self.searchOptions = None
+
+    def setSearchOptions(self, search):
+        """the `bwa aln` / `bwa samse` options beyond -n / -X for executeMapping: a capi.SearchOpts, a dict of its fields, or None
+        (upstream's defaults).  The other routes (executeMappingToBam, executeMappingWithProfile, Main.map) keep the defaults."""
+        self.searchOptions = search
 
     def executeMapping(self, threads, reference, input, outputPrefix, mappingQualityFilter, additionalOptions):
         raise NotImplementedError
@@ -86,7 +92,7 @@ class BWAMapping(Mapping):
             self._call("bwa index " + reference, capi.ps_index, reference)
         self.setTimeStart()
         self._call("bwa aln -t %d -n %s %s %s | bwa samse" % (threads, additionalOptions, reference, input),
-                   capi.ps_map, threads, additionalOptions, None, None, reference, input, outputPrefix + ".sam")
+                   capi.ps_map, threads, additionalOptions, None, None, reference, input, outputPrefix + ".sam", self.searchOptions)
         self.seconds = self.calculatePassedTime()
 
     def executeMappingToBam(self, threads, reference, input, outputPrefix, mappingQualityFilter, additionalOptions, sortByCoordinateAndIndex=False):
@@ -133,7 +139,7 @@ class PARAsuiteMapping(Mapping):
         self._call("bwa parasuite -t %d -X %s -p %s -g %s %s %s | bwa samse" %
                    (threads, additionalOptions, self.errorProfileFilename, self.indelProfileFilename, reference, input),
                    capi.ps_map, threads, additionalOptions, self.errorProfileFilename, self.indelProfileFilename,
-                   reference, input, outputPrefix + ".sam")
+                   reference, input, outputPrefix + ".sam", self.searchOptions)
         self.seconds = self.calculatePassedTime()
 
     def executeMappingToBam(self, threads, reference, input, outputPrefix, mappingQualityFilter, additionalOptions, sortByCoordinateAndIndex=False):

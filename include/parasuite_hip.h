@@ -56,7 +56,9 @@ int ps_index(const char *ref_fa);
  * Deviations: (1) gzread hands out a truncated stream as if it ended there, so bwa maps half a file and exits 0; here an input
  * that ends inside a member (header, data or trailer) fails the call.  (2) gzread ignores bytes behind the last member; here
  * bytes behind a complete member that do not start another member fail the call.  Both, a CRC32 / ISIZE mismatch, invalid
- * deflate data, CM other than 8, reserved flag bits and a bad BGZF BSIZE are errors that name the file and the compressed byte. */
+ * deflate data, CM other than 8, reserved flag bits and a bad BGZF BSIZE are errors that name the file and the compressed byte.
+ * (3) A FASTQ text that was cut off behind the '+' line of its last record ("@name", one line of bases, "+..." and the end: bases
+ * and no quality line) fails the call and names the file and the read; kseq drops such a record without a word. */
 int ps_map(int threads, const char *mm, const char *error_profile, const char *indel_profile,
            const char *ref_fa, const char *fastq, const char *out_sam);
 
@@ -358,7 +360,7 @@ int     ps_map_profiled(int threads, const char *mm, const char *error_profile, 
  * call returns (the transcript pass takes over the genome passes' lanes), the weak reads go to the transcript pass from memory
  * (names as a second parse leaves them: one more trailing /1 or /2 removed), and no BAM is written to be read back.  Each pass is
  * a samse run of its own (its tie-break stream starts at 0).  ps_index runs for a reference whose .bwt is missing.  Nothing stays
- * resident when the call returns.
+ * resident when the call returns, unless a resident scope is open (below).
  * Errors before anything is touched: error_profile without refine (nothing to map), a missing reads_fq / ref_fa / out_prefix, an
  * output name that is one of the inputs, no HIP device.  FASTA reads with a transcript route fail as ps_extract_weak_reads does on
  * records without QUAL.  On any error ps_last_error() names the step ("first pass", "profile", "refine pass", "transcript pass",
@@ -384,6 +386,37 @@ typedef struct {
     uint32_t n_index_loads_genome, n_index_loads_transcripts, n_fastq_parses, pad_;
 } ps_route_stats;
 int     ps_map_route(const ps_route_opts *opts, ps_route_stats *stats /* may be NULL */);
+
+/* ---- the resident scope: indexes and lanes of work stay in HBM between calls ---------------------------------------------------
+ * Outside a scope every mapping call loads its index, allocates its search workspace and frees both before it returns.  Between
+ * ps_resident_begin and ps_resident_end (one scope per process, opt-in) ps_map, ps_map_opts, ps_map_to_bam, ps_map_profiled and
+ * ps_map_route find their index in HBM where an earlier call of the scope loaded it, find the device's lanes of work (streams,
+ * search workspace) allocated, and leave both in place; ps_map_route's "nothing stays resident" holds outside a scope only, and
+ * its n_index_loads_* count what THIS call read from files (0 for an index it found).  The output of a call is what it is
+ * outside a scope, byte for byte: the cost and search options are set per call, each call is a samse run of its own.
+ * An entry is kept under: the reference as realpath names it; the devices and workers per device (PARASUITE_GPUS,
+ * PARASUITE_GPU_IDS, PS_WORKERS_PER_GPU); and PS_JUMP, PS_JUMP_LEVELS, PS_POOL_CAP, PS_N_BIG, PS_BT_BLOCKS as they were read.  A
+ * call under another key makes another entry.  Beside the key an entry remembers device, inode, size and mtime (nanoseconds) of
+ * the four index files: a call that finds them changed closes the entry and loads afresh (n_stale_reloads); ps_index drops the
+ * entries of the path it is about to write.  At most max_references entries are held, the least recently used one is closed for
+ * a new one (n_evictions).  A device has ONE set of lanes whatever the number of entries: a call moves them to the entry it
+ * uses.  A call that fails, for whatever reason, drops every entry it used (n_dropped_after_error); the next call loads afresh.
+ * Everything that leaves -- evicted, stale, dropped, and all at ps_resident_end -- is closed on the calling thread before the
+ * operation returns (device memory freed, streams destroyed, the .pac unmapped): when ps_resident_end returns no thread of the
+ * library touches a device.  A process that exits inside a scope makes no device call from an exit handler.
+ * Calls inside a scope take their turn: a second thread's mapping call waits for the first's.  The staged ps_ctx_* interface,
+ * the analysis modes and the shims are not part of it.
+ * ps_resident_opts.struct_size as in ps_search_opts: a multiple of 4; a shorter struct keeps the defaults of the fields it lacks, a
+ * longer one is refused.  Status 1 with ps_last_error(): begin inside an open scope, end without one, max_references outside 1..8. */
+typedef struct { uint32_t struct_size; uint32_t max_references; /* [2]; 1..8 */ } ps_resident_opts;
+typedef struct {
+    uint32_t active, n_references;               /* a scope is open; entries held now */
+    uint64_t n_calls, n_index_loads, n_index_reuses, n_stale_reloads, n_evictions, n_dropped_after_error;
+    uint64_t bytes_index_resident;               /* sum of the blobs of the held entries, all devices */
+} ps_resident_stats;
+int     ps_resident_begin(const ps_resident_opts *);  /* NULL: defaults.  Needs no device, makes no device call */
+int     ps_resident_end(void);
+int     ps_resident_info(ps_resident_stats *);        /* any time; outside a scope: active 0, counters of the last scope */
 
 /* ---- after the mapping: the toolkit's `benchmark MAPPING OUT.stats READS.fastq` mode (Main.java:489-521) -------------------------
  * `new ValidateBenchmarkStatisticsPARCLIP().calculateBenchmarkStatistics(mapping, outStatistics, readsFile, onlyBound)`

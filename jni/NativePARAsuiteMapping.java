@@ -24,6 +24,11 @@ public class NativePARAsuiteMapping extends Mapping {
                                                int minMapq, int maxReadLength, String profilePrefix);
     /** ErrorProfiling.inferErrorProfile(false, false) on an existing SAM / BAM file (Main.java:327-334) */
     public static native int nativeErrorProfile(String mapping, String reference, int maxReadLength, String outPrefix);
+    /** the resident scope (ps_resident_begin / ps_resident_end): between the two, every executeMapping of the process finds its index and
+     *  the device's lanes of work in HBM where an earlier one left them.  Main opens it before its first executeMapping and ends it
+     *  after the last (jni/README.md); maxReferences 1..8, Main's genome and transcripts need 2.  Non-zero: nativeLastError() says why. */
+    public static native int nativeResidentBegin(int maxReferences);
+    public static native int nativeResidentEnd();
     private static native String nativeLastError();
 
     /* errorProfileFilename == null: the stock first pass (BWAMapping.java:51-75, `bwa aln -n mm`) */

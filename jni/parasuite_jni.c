@@ -46,6 +46,19 @@ JNIEXPORT jint JNICALL Java_mapping_NativePARAsuiteMapping_nativeErrorProfile(JN
     return rc;
 }
 
+/* the resident scope around Main's executeMapping calls: ps_resident_begin / ps_resident_end */
+JNIEXPORT jint JNICALL Java_mapping_NativePARAsuiteMapping_nativeResidentBegin(JNIEnv *e, jclass k, jint maxReferences)
+{
+    ps_resident_opts o;
+    o.struct_size = (uint32_t)sizeof o; o.max_references = (uint32_t)maxReferences;      /* a negative count is refused as out of range */
+    return ps_resident_begin(&o);
+}
+
+JNIEXPORT jint JNICALL Java_mapping_NativePARAsuiteMapping_nativeResidentEnd(JNIEnv *e, jclass k)
+{
+    return ps_resident_end();
+}
+
 JNIEXPORT jstring JNICALL Java_mapping_NativePARAsuiteMapping_nativeLastError(JNIEnv *e, jclass k)
 {
     return (*e)->NewStringUTF(e, ps_last_error());

@@ -71,7 +71,8 @@ EXPORTS = ["ps_version", "ps_last_error", "ps_index", "ps_map", "ps_ctx_open", "
            "ps_ctx_blob", "ps_ctx_meta", "ps_ctx_from_blobs", "ps_ctx_clone", "ps_ctx_fetch", "ps_ctx_export_blob", "ps_ctx_sa_lookup", "ps_ctx_order_sort", "ps_ctx_index_check", "ps_sam_to_bam", "ps_map_to_bam", "ps_bam_view", "ps_bam_sort", "ps_bam_index", "ps_batch_from_fastq",
            "ps_batch_from_codes", "ps_batch_free", "ps_batch_n", "ps_batch_search", "ps_batch_select_hard",
            "ps_batch_select_easy", "ps_batch_locate", "ps_batch_run", "ps_batch_write_sam", "ps_batch_n_aln",
-           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route", "ps_benchmark_reads", "ps_simulate_reads", "ps_fetch_sequences"]
+           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route", "ps_benchmark_reads", "ps_simulate_reads", "ps_fetch_sequences",
+           "ps_resident_begin", "ps_resident_end", "ps_resident_info"]
 
 _LIB = None
 
@@ -610,3 +611,52 @@ def ps_map_route(reads_fq, ref_fa, out_prefix, transcripts_fa=None, threads=8, r
     st = RouteStats()
     _chk(L.ps_map_route(C.byref(o), C.byref(st)))
     return _struct_dict(st)
+
+
+class ResidentOpts(C.Structure):
+    _fields_ = [("struct_size", C.c_uint32), ("max_references", C.c_uint32)]
+
+
+class ResidentStats(C.Structure):
+    _fields_ = [("active", C.c_uint32), ("n_references", C.c_uint32)] + \
+               [(k, C.c_uint64) for k in ("n_calls", "n_index_loads", "n_index_reuses", "n_stale_reloads", "n_evictions",
+                                          "n_dropped_after_error", "bytes_index_resident")]
+
+
+def ps_resident_begin(max_references=2):
+    L = lib(); L.ps_resident_begin.argtypes = [C.POINTER(ResidentOpts)]
+    o = ResidentOpts(C.sizeof(ResidentOpts), int(max_references))
+    _chk(L.ps_resident_begin(C.byref(o)))
+
+
+def ps_resident_end():
+    _chk(lib().ps_resident_end())
+
+
+def ps_resident_info():
+    """ps_resident_stats as a dict; any time: outside a scope active is 0 and the counters are the last scope's"""
+    L = lib(); L.ps_resident_info.argtypes = [C.POINTER(ResidentStats)]
+    st = ResidentStats()
+    _chk(L.ps_resident_info(C.byref(st)))
+    return {f: int(getattr(st, f)) for f, _ in ResidentStats._fields_}
+
+
+class resident:
+    """with capi.resident(max_references=2): ... -- the mapping calls inside keep their indexes and the device's lanes of work
+    in HBM from call to call (include/parasuite_hip.h: the resident scope).  The scope is ended on every way out of the block,
+    an exception included; ps_resident_info() afterwards still shows the scope's counters."""
+
+    def __init__(self, max_references=2):
+        self.max_references = max_references
+
+    def __enter__(self):
+        ps_resident_begin(self.max_references)
+        return self
+
+    def __exit__(self, exc_type, exc, tb):
+        ps_resident_end()
+        return False
+
+    @staticmethod
+    def info():
+        return ps_resident_info()

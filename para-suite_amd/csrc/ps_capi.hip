@@ -72,6 +72,7 @@ void ps_ctx_close(ps_ctx *x) { delete x; }
 int ps_index(const char *ref_fa)
 {
     PS_TRY
+        resident_invalidate(ref_fa);                 // inside a resident scope: the entries of this path go before its files are written
         ps_ctx *x = ps_ctx_build(ref_fa, 0, 1);
         if (!x) return 1;
         delete x;
@@ -378,6 +379,17 @@ int ps_map_to_bam(int threads, const char *mm, const char *error_profile, const 
     PS_CATCH_INT
 }
 int ps_map_route(const ps_route_opts *o, ps_route_stats *stats_out) { PS_TRY map_route(o, stats_out); return 0; PS_CATCH_INT }
+
+// The resident scope: between begin and end the five mapping calls above keep their indexes and lanes of work in HBM (ps_map.hip).
+int ps_resident_begin(const ps_resident_opts *o) { PS_TRY resident_begin(o); return 0; PS_CATCH_INT }
+int ps_resident_end(void) { PS_TRY resident_end(); return 0; PS_CATCH_INT }
+int ps_resident_info(ps_resident_stats *out)
+{
+    PS_TRY
+        if (!out) throw Error("ps_resident_info: no place for the result");
+        resident_info(*out); return 0;
+    PS_CATCH_INT
+}
 
 // page-locked host buffers the library keeps between calls (ps_pipeline.h, PinBuf): given back to the system
 void ps_release_host_cache(void) { try { trash_collect(); pin_cache_release(); } catch (...) {} }

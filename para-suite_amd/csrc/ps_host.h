@@ -77,6 +77,7 @@ struct Index {
 };
 void index_build(const char *fa, Index &ix, hipStream_t s);        // GPU suffix sorting (ps_index.hip)
 void index_build_jump(Index &ix, hipStream_t s);                    // the view must be complete (blocks, primary, L2); PS_JUMP_LEVELS overrides the depth
+int  jump_levels_stated();                                          // PS_JUMP_LEVELS as index_build_jump takes it (0 to PS_JUMP_MAX_LEVELS); -1: not stated, the depth follows from the text
 void index_save(const Index &ix, const std::string &prefix);
 void index_load(const std::string &prefix, Index &ix, hipStream_t s);
 // a second copy of a resident index on another device, over xGMI (hipMemcpyPeerAsync); the caller has made dst_device current

@@ -376,10 +376,15 @@ void Index::refresh_view()
     view.jump = jump_levels > 0 ? jump.p : nullptr; view.jump_levels = jump_levels;
 }
 
+int jump_levels_stated()
+{
+    const char *e = std::getenv("PS_JUMP_LEVELS");
+    return e ? std::max(0, std::min(PS_JUMP_MAX_LEVELS, std::atoi(e))) : -1;
+}
 void index_build_jump(Index &ix, hipStream_t s)
 {
-    int levels = jump_levels_for(ix.view.seq_len);
-    if (const char *e = std::getenv("PS_JUMP_LEVELS")) levels = std::max(0, std::min(PS_JUMP_MAX_LEVELS, std::atoi(e)));
+    int levels = jump_levels_stated();
+    if (levels < 0) levels = jump_levels_for(ix.view.seq_len);
     ix.jump_levels = 0; ix.view.jump = nullptr; ix.view.jump_levels = 0;
     if (levels == 0) return;
     ix.jump.alloc(jump_words(levels));

@@ -19,4 +19,11 @@ void map_profiled(const MapArgs &a, const char *out_sam, int min_mapq, int max_r
 void map_to_bam(const MapArgs &a, const char *out_bam, int min_mapq, bool sort_by_coordinate, bool write_index, BamStats *stats);
 void map_route(const ps_route_opts *o, ps_route_stats *stats_out);
 
+// The resident scope (ps_resident.h keeps the books, ps_map.hip the contexts): between begin and end the four calls above take
+// their contexts from the scope's entries and leave them open.  begin makes no device call.
+void resident_begin(const ps_resident_opts *o);
+void resident_end();
+void resident_info(ps_resident_stats &out);
+void resident_invalidate(const char *ref_fa);      // ps_index is about to write the index files of ref_fa: its entries are closed
+
 }  // namespace ps

@@ -30,6 +30,7 @@
 #include "ps_inflate.h"
 #include "ps_map.h"
 #include "ps_map_plan.h"
+#include "ps_resident.h"
 
 namespace ps {
 namespace {
@@ -134,8 +135,8 @@ struct MapJob {
     std::vector<ReadSet> *reads = nullptr; // the input, already parsed, instead of the file a.reads (consumed)
     bool bam_out = false;                  // the piece plan's: the records are compressed, which wants early pieces
     std::vector<std::unique_ptr<PassOut>> outs;
-    CtxSet *resident = nullptr;            // ps_map_route: the contexts are taken from there (made and loaded by the first pass that finds none) and left open
-    CtxSet *lanes_from = nullptr;          // the lanes of work (streams, search workspace) of these contexts, which search no more, move to this pass's contexts on the same devices
+    CtxSet *resident = nullptr;            // ps_map_route, the resident scope: the contexts are taken from there (made and loaded by the first pass that finds none) and left open
+    std::vector<CtxSet *> lanes_from;      // the lanes of work (streams, search workspace) of these contexts, which search no more, move to this pass's contexts on the same devices
     int64_t n_reads = 0; double s_parse = 0, s_index = 0, s_write = 0, s_profile = 0;      // results
 };
 
@@ -176,14 +177,29 @@ struct Pass {
 
 int env_mb(const char *name) { const char *e = std::getenv(name); return e ? std::max(1, std::atoi(e)) : 0; }
 
-Pass::Pass(MapJob &j) : job(j), nthr(j.a.threads > 0 ? j.a.threads : 1), set(j.resident ? *j.resident : own), preloaded(j.resident && j.resident->loaded)
+// the devices and workers of a pass, from the environment (also a part of the resident scope's key)
+DevicePlan devices_from_env()
 {
     int per_dev = 1, want = 1, have = 1;
     if (const char *e = std::getenv("PS_WORKERS_PER_GPU")) per_dev = std::atoi(e);
     if (const char *e = std::getenv("PARASUITE_GPUS")) want = std::max(1, std::atoi(e));
     const char *ids = std::getenv("PARASUITE_GPU_IDS");
     if (!ids && want > 1 && (hipGetDeviceCount(&have) != hipSuccess || have < 1)) throw Error("no HIP device available");   // one device: found out (loudly) when the worker attaches it
-    dev = plan_devices(ids, want, per_dev, have, (int)Ctx::N_WORK);
+    return plan_devices(ids, want, per_dev, have, (int)Ctx::N_WORK);
+}
+// the lanes of work that `from` holds go to the contexts of `to` on the same devices, where those have none
+void move_lanes(CtxSet &from, CtxSet &to)
+{
+    for (auto &t : to.xs) for (auto &f : from.xs) {
+        if (!t || !f || t.get() == f.get() || f->device != t->device) continue;
+        std::lock_guard<std::mutex> l1(f->work_mu), l2(t->work_mu);
+        for (int w = 0; w < (int)Ctx::N_WORK; ++w) if (f->work[w] && !t->work[w]) t->work[w] = std::move(f->work[w]);
+    }
+}
+
+Pass::Pass(MapJob &j) : job(j), nthr(j.a.threads > 0 ? j.a.threads : 1), set(j.resident ? *j.resident : own), preloaded(j.resident && j.resident->loaded)
+{
+    dev = devices_from_env();
     G = (int)dev.devs.size(); n_workers = dev.n_workers();
     struct stat st;
     const size_t file_bytes = !job.reads && ::stat(job.a.reads, &st) == 0 && st.st_size > 0 && !is_gzip_file(job.a.reads) ? (size_t)st.st_size : 0;   // compressed: the text's size is unknown
@@ -204,13 +220,7 @@ Pass::Pass(MapJob &j) : job(j), nthr(j.a.threads > 0 ? j.a.threads : 1), set(j.r
         ctx(g).host_threads = nthr;
         ctx(g).n_work = dev.workers[g];
     }
-    if (job.lanes_from && job.lanes_from->xs.size() == (size_t)G)
-        for (int g = 0; g < G; ++g) {
-            Ctx &from = *job.lanes_from->xs[g], &to = ctx(g);
-            if (from.device != to.device) continue;
-            std::lock_guard<std::mutex> l1(from.work_mu), l2(to.work_mu);
-            for (int w = 0; w < (int)Ctx::N_WORK; ++w) if (from.work[w] && !to.work[w]) to.work[w] = std::move(from.work[w]);
-        }
+    for (CtxSet *from : job.lanes_from) if (from && from != &set) move_lanes(*from, set);
 }
 
 // the parser (starts at once)
@@ -376,7 +386,136 @@ void Pass::run()
                          G, dev.workers[0], since(), t_index, t_index_all, t_parse, busy, t_workers, job.s_write, t_release, job.s_profile, t_written, t_release_dev, t_closed);
 }
 
+// ---- the resident scope -------------------------------------------------------------------------------------------------------
+// The entries (ps_resident.h) hold the CtxSet a pass takes as MapJob::resident.  Calls inside a scope take their turn (call_mu is
+// held for the whole call); mu guards the books, so that ps_resident_info answers while a call runs.
+typedef ResidentCache<CtxSet> Residents;
+struct ResidentScope { std::mutex call_mu, mu; Residents cache; };
+// Everything a set holds goes back before this returns, on the calling thread: device memory (blobs, jump table, the lanes'
+// workspace), then streams, events and the mapped .pac.  The lanes of the devices an heir shares move to it first.
+void close_set(CtxSet &gone, CtxSet *heir)
+{
+    trash_collect();
+    if (heir) move_lanes(gone, *heir);
+    for (auto &c : gone.xs) if (c && c->stream) { try { ctx_release_device(*c); } catch (...) {} }     // no stream: the device side was never attached
+    gone.xs.clear(); gone.loaded = false;
+}
+ResidentScope &scope()                     // never destroyed: a process that exits inside a scope makes no device call from an exit handler
+{
+    static ResidentScope *s = [] { ResidentScope *x = new ResidentScope(); x->cache.close = close_set; return x; }();
+    return *s;
+}
+ResidentKnobs knobs_from_env()
+{
+    ResidentKnobs k;
+    const Ctx probe(0);                    // PS_POOL_CAP, PS_N_BIG, PS_BT_BLOCKS as a context of the pass reads them (no device call)
+    k.pool_cap = (int)probe.pool_cap[0]; k.n_big = probe.n_big; k.bt_blocks = probe.bt_blocks;
+    k.jump_levels = jump_levels_stated();  // as index_build_jump reads it
+    if (const char *e = std::getenv("PS_JUMP")) k.jump = std::atoi(e) == 0 ? 0 : 1;     // as launch_backtrack reads it
+    return k;
+}
+uint64_t index_blob_bytes(const CtxSet &s)
+{
+    uint64_t b = 0;
+    for (const auto &c : s.xs) if (c) b += c->ix.blocks.n * sizeof(OccBlock) + c->ix.sa.n * sizeof(uint32_t) + c->ix.pac.n;
+    return b;
+}
+// A mapping call's part in the scope.  Outside a scope it does nothing and holds nothing.  Inside, entry() looks a reference up
+// (pinned for the call), lend() hands it to a pass, done() settles a call that ended well; a call that ends any other way drops
+// every entry it used when this goes out of scope.
+struct ResidentUse {
+    ResidentScope &rs = scope();
+    std::unique_lock<std::mutex> turn{rs.call_mu};
+    bool on = false, settled = false;
+    struct Used { Residents::Entry *e; int loads_before; };
+    std::vector<Used> used;
+    ResidentUse()
+    {
+        { std::lock_guard<std::mutex> l(rs.mu); on = rs.cache.active; if (on) ++rs.cache.n.n_calls; }
+        if (!on) turn.unlock();
+    }
+    Residents::Entry *entry(const char *ref_fa)
+    {
+        const DevicePlan plan = devices_from_env();
+        const ResidentKey key = resident_key(ref_fa, plan, knobs_from_env());
+        const ResidentIdent id = resident_ident(ref_fa);
+        std::lock_guard<std::mutex> l(rs.mu);
+        Residents::Entry *e = rs.cache.acquire(key, id, [&plan](CtxSet &s) {         // the contexts exist at once, so that they can inherit lanes: options only, no device call
+            s.xs.resize(plan.devs.size());
+            for (size_t g = 0; g < plan.devs.size(); ++g) s.xs[g].reset(new Ctx(plan.devs[g]));
+        });
+        for (const Used &u : used) if (u.e == e) return e;
+        used.push_back(Used{e, e->payload.n_index_loads});
+        return e;
+    }
+    void lend(Residents::Entry *e, MapJob &job)
+    {
+        job.resident = &e->payload; job.lanes_from.clear();
+        std::lock_guard<std::mutex> l(rs.mu);
+        for (Residents::Entry *f : rs.cache.take_lanes(e)) job.lanes_from.push_back(&f->payload);
+    }
+    void settle(bool ok)
+    {
+        if (!on || settled) return;
+        settled = true;
+        std::lock_guard<std::mutex> l(rs.mu);
+        for (const Used &u : used) {
+            rs.cache.n.n_index_loads += (uint64_t)(u.e->payload.n_index_loads - u.loads_before);
+            if (ok) {
+                u.e->bytes = index_blob_bytes(u.e->payload);
+                if (!u.e->id.complete()) u.e->id = resident_ident(u.e->key.path);      // the pass built the index files itself
+                rs.cache.release(u.e);
+            } else rs.cache.drop(u.e);
+        }
+    }
+    void done() { settle(true); }
+    ~ResidentUse() { settle(false); }
+};
+// one pass of a mapping call that is a single pass: inside a scope over the entry of its reference
+void run_single(MapJob &job)
+{
+    ResidentUse use;
+    if (use.on) use.lend(use.entry(job.a.ref_fa), job);
+    Pass(job).run();
+    use.done();
+}
+
 }  // namespace
+
+void resident_begin(const ps_resident_opts *o)
+{
+    ps_resident_opts r; std::string err;
+    if (!resident_opts_read(o, r, err)) throw Error(err);
+    ResidentScope &s = scope();
+    std::lock_guard<std::mutex> t(s.call_mu), l(s.mu);
+    if (!s.cache.begin(r.max_references, err)) throw Error(err);
+}
+void resident_end()
+{
+    ResidentScope &s = scope();
+    std::string err;
+    std::lock_guard<std::mutex> t(s.call_mu), l(s.mu);
+    const bool open = s.cache.active;
+    if (open) trash_collect();             // what calls before the scope left to be freed: no thread of the library is left behind
+    if (!s.cache.end(err)) throw Error(err);
+}
+void resident_info(ps_resident_stats &out)
+{
+    ResidentScope &s = scope();
+    std::lock_guard<std::mutex> l(s.mu);
+    const ResidentCounters &n = s.cache.n;
+    std::memset(&out, 0, sizeof out);
+    out.active = s.cache.active ? 1 : 0; out.n_references = (uint32_t)s.cache.entries.size();
+    out.n_calls = n.n_calls; out.n_index_loads = n.n_index_loads; out.n_index_reuses = n.n_index_reuses; out.n_stale_reloads = n.n_stale_reloads;
+    out.n_evictions = n.n_evictions; out.n_dropped_after_error = n.n_dropped_after_error; out.bytes_index_resident = s.cache.bytes();
+}
+void resident_invalidate(const char *ref_fa)
+{
+    ResidentScope &s = scope();
+    { std::lock_guard<std::mutex> l(s.mu); if (!s.cache.active) return; }
+    std::lock_guard<std::mutex> t(s.call_mu), l(s.mu);
+    s.cache.invalidate(resident_path(ref_fa));
+}
 
 void trash_add(std::thread &&t) { Trash &x = trash(); std::lock_guard<std::mutex> l(x.mu); x.th.push_back(std::move(t)); if (!x.hooked) { x.hooked = true; std::atexit(trash_collect); } }
 void trash_collect() { Trash &x = trash(); std::vector<std::thread> all; { std::lock_guard<std::mutex> l(x.mu); all.swap(x.th); } for (auto &t : all) if (t.joinable()) t.join(); }
@@ -385,7 +524,7 @@ void map_to_sam(const MapArgs &a, const char *out_sam)
 {
     MapJob job; job.a = a;
     job.outs.emplace_back(new SamText(out_sam, a.threads > 0 ? a.threads : 1, job.s_write));
-    Pass(job).run();
+    run_single(job);
 }
 // ps_map + the error profile of its own alignments (those with MAPQ >= min_mapq: what the filtered BAM of the pass would
 // hold), counted from the records in memory while the SAM is being written: <profile_prefix>.errorprofile / .indelprofile
@@ -395,7 +534,7 @@ void map_profiled(const MapArgs &a, const char *out_sam, int min_mapq, int max_r
     MapJob job; job.a = a;
     job.outs.emplace_back(new SamText(out_sam, nthr, job.s_write));
     job.outs.emplace_back(new ProfileOut(min_mapq, max_read_len, profile_prefix, nthr, job.s_profile));
-    Pass(job).run();
+    run_single(job);
 }
 // ps_map with the records going straight into a BAM file: what PARAsuiteMapping.java:102-152 makes of <prefix>.sam with three
 // samtools calls (view -bS, view -q, and -- Mapping.java:85-108 -- sort + index), without the 2 GB of SAM text in between.  Records
@@ -408,7 +547,7 @@ void map_to_bam(const MapArgs &a, const char *out_bam, int min_mapq, bool sort_b
     if (const char *e = std::getenv("PS_BAM_LEVEL")) bo.level = std::atoi(e);
     MapJob job; job.a = a; job.bam_out = true;
     job.outs.emplace_back(new BamRecords(bo, out_bam, a.threads > 0 ? a.threads : 1, job.s_write));
-    Pass(job).run();
+    run_single(job);
 }
 
 // ---- the whole `map` mode (Main.java:249-420) in one call ---------------------------------------------------------------------
@@ -458,7 +597,8 @@ bool has(const char *s) { return s && s[0]; }
 // the call's state between its passes, and one pass of it
 struct Route {
     const ps_route_opts &o; const int threads, gm; int bam_level = 1;
-    RouteFiles files; CtxSet genome, transcripts;
+    RouteFiles files; CtxSet genome, transcripts;   // the call's own contexts: open from pass to pass, closed when it returns
+    ResidentUse use; Residents::Entry *eg = nullptr, *et = nullptr; int g_loads0 = 0, t_loads0 = 0;    // inside a resident scope: the scope's entries instead, which stay
     std::vector<ReadSet> kept, weak; size_t kept_bytes = 0, keep_bound = (size_t)8192 << 20; bool kept_all = true;
     uint64_t n_weak = 0;
     BamFile G, T;
@@ -487,6 +627,16 @@ struct Route {
         files.publish(t, out); if (!by_name) files.publish(t + ".bai", out + ".bai");
         bs_out.n_in = bs.n_in; bs_out.n_out = bs.n_out; bs_out.bam_bytes = bs.bam_bytes;
     }
+    // the contexts of a pass; the transcript pass takes over the lanes of work of the genome passes
+    void lend(MapJob &job, bool to_transcripts)
+    {
+        if (!use.on) { job.resident = to_transcripts ? &transcripts : &genome; if (to_transcripts) job.lanes_from = {&genome}; return; }
+        Residents::Entry *&e = to_transcripts ? et : eg;
+        if (!e) { e = use.entry(to_transcripts ? o.transcripts_fa : o.ref_fa); (to_transcripts ? t_loads0 : g_loads0) = e->payload.n_index_loads; }
+        use.lend(e, job);
+    }
+    const CtxSet &genome_set() const { return eg ? eg->payload : genome; }
+    const CtxSet &transcript_set() const { return et ? et->payload : transcripts; }
     void close() { transcripts.xs.clear(); genome.xs.clear(); }
 };
 }
@@ -535,7 +685,7 @@ void map_route(const ps_route_opts *o, ps_route_stats *stats_out)
         std::string ep = given ? o->error_profile : "", ip = has(o->indel_profile) ? o->indel_profile : "";
         if (first_pass) {
             const auto t0 = clk::now();
-            MapJob job; job.resident = &r.genome;
+            MapJob job; r.lend(job, false);
             if (refine) {
                 const std::string prefix = files.open(f_bwa + ".profile");
                 files.tmp.push_back(prefix + ".errorprofile"); files.tmp.push_back(prefix + ".indelprofile");
@@ -558,7 +708,7 @@ void map_route(const ps_route_opts *o, ps_route_stats *stats_out)
         if (refine) {
             step = "refine pass";
             const auto t0 = clk::now();
-            MapJob job; job.resident = &r.genome;
+            MapJob job; r.lend(job, false);
             if (first_pass && r.kept_all) job.reads = &r.kept; else ++st.n_fastq_parses;
             if (with_t) job.outs.emplace_back(new PieceFn([&r](Batch &b) { r.weak_of(b); }));
             r.pass(job, para_mm, ep.c_str(), ip.empty() ? nullptr : ip.c_str(), o->ref_fa, f_para, gm, false, with_t ? &r.G : nullptr, st.refine);
@@ -570,20 +720,21 @@ void map_route(const ps_route_opts *o, ps_route_stats *stats_out)
             step = "transcript pass";
             const auto t0 = clk::now();
             st.extract.n_records = st.n_reads; st.extract.n_weak = r.n_weak; st.extract.n_kept = st.n_reads - r.n_weak;
-            MapJob job; job.resident = &r.transcripts; job.reads = &r.weak; job.lanes_from = &r.genome;
+            MapJob job; r.lend(job, true); job.reads = &r.weak;
             r.pass(job, refine ? para_mm : bwa_mm, refine ? ep.c_str() : nullptr, refine && !ip.empty() ? ip.c_str() : nullptr, o->transcripts_fa, f_tr, tm, true, &r.T, st.transcript);
             st.s_index_transcripts = job.s_index; st.s_transcript = secs_since(t0);
             step = "combine";
             const auto t1 = clk::now();
-            const int dev = r.genome.xs[0]->device;                    // the first device of the passes
+            const int dev = r.genome_set().xs[0]->device;                    // the first device of the passes
             const std::string t = files.open(f_comb); files.tmp.push_back(t + ".bai");
             combine_records(r.G, r.T, f_tr.c_str(), t.c_str(), true, true, threads, dev, &st.combine);
             files.publish(t, f_comb); files.publish(t + ".bai", f_comb + ".bai");
             st.s_combine = secs_since(t1);
         }
         step = "closing";
-        st.n_index_loads_genome = (uint32_t)r.genome.n_index_loads; st.n_index_loads_transcripts = (uint32_t)r.transcripts.n_index_loads;
+        st.n_index_loads_genome = (uint32_t)(r.genome_set().n_index_loads - r.g_loads0); st.n_index_loads_transcripts = (uint32_t)(r.transcript_set().n_index_loads - r.t_loads0);
         r.close();
+        r.use.done();
     } catch (const std::exception &e) {
         const std::string m = e.what();
         r.close();

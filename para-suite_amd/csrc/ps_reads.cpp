@@ -210,6 +210,26 @@ static void parser_times(int threads)
         std::fprintf(stderr, "[parasuite-hip]     parser: reading %.0f ms, cutting %.0f ms, parsing on %d threads %.0f ms, placing the threads' parts %.0f ms (sums over the windows)\n", 1e3 * g_t_fread, 1e3 * g_t_cut, threads, 1e3 * g_t_par, 1e3 * g_t_merge);
     g_t_fread = g_t_cut = g_t_par = g_t_merge = 0;
 }
+// A FASTQ input that was cut off behind the '+' line of its last record: "@name", one sequence line, "+..." and the end.  The record
+// has bases and no quality line, and the input fails the call (the parser would make up qualities for it).  b[0, n) is the end of
+// the input from a record start on; only this plain shape is recognised, every other end of an input is parsed as it was.
+static void refuse_cut_off_fastq(const char *b, size_t n, const char *path)
+{
+    size_t e = n;
+    while (e > 0 && !std::isgraph((unsigned char)b[e - 1])) --e;              // blanks and line ends behind the last line
+    auto line_start = [&](size_t end) { size_t s = end; while (s > 0 && b[s - 1] != '\n') --s; return s; };
+    if (e == 0) return;
+    const size_t l1 = line_start(e);                                          // the last line: a '+' line?
+    if (b[l1] != '+' || l1 < 2) return;
+    const size_t l2 = line_start(l1 - 1);                                     // before it: one line of bases
+    if (l2 < 2 || l2 == l1 - 1 || b[l2] == '+' || b[l2] == '@') return;
+    const size_t l3 = line_start(l2 - 1);                                     // before that: the header
+    if (b[l3] != '@' || record_end(b, l3, n, true) != 0) return;
+    size_t m = l3 + 1;
+    while (m < l2 && !std::isspace((unsigned char)b[m])) ++m;
+    throw Error(std::string(path) + ": the last FASTQ record (" + std::string(b + l3 + 1, m - l3 - 1) + ") is cut off after its '+' line: it has no quality line");
+}
+
 void load_reads(const char *path, ReadSet &rs, int threads)
 {
     rs = ReadSet();
@@ -255,8 +275,9 @@ void load_reads_chunked(const char *path, int threads, size_t chunk_bytes, const
             if (last == 0) continue;                                               // nothing to cut at: the window grows
             cut = last;
         }
+        if (eof && cut && mark == '@') refuse_cut_off_fastq(buf.data(), cut, path);
         if (cut) {
-            const size_t tiny = cur / 8;                                                                        // an end of the input not worth a launch of its own
+            const size_t tiny = cur / 8;                                                                       // an end of the input not worth a launch of its own
             const bool to_the_end = sized && (size_t)std::max<off_t>(0, text_bytes - file_at) + have <= tiny;  // this window and all behind it
             if (acc_bytes && acc_bytes + cut > cur + fine && !to_the_end) flush();    // this window would take the piece well over its size (a window that had to grow)
             const bool first_window = acc.n == 0;

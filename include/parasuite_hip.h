@@ -32,7 +32,11 @@ const char *ps_last_error(void);
  * <ref_fa>.bwt exists, PARAsuiteMapping.java:45-46).  Suffix sorting runs on the GPU.
  * ref_fa: FASTA as plain text, gzip (RFC 1952, concatenated members too) or BGZF, told apart by its first two bytes, as bwa
  * reads it through gzopen.  The index files are named after the path as given (genome.fa.gz.bwt, ...), as `bwa index` names
- * them; every call that takes ref_fa takes the same string.  Deviations: as for the reads of ps_map. */
+ * them; every call that takes ref_fa takes the same string.  Deviations: as for the reads of ps_map.
+ * Output files on failure, for this call and every call below that writes files: outputs
+ * are written under <name>.<mode>-tmp and renamed when complete; on error no output of the call exists under its final or its
+ * temporary name, a file from before the call is either untouched or fully replaced, and an output that is one of the call's
+ * inputs is refused.  Not so the streamed SAM / BAM of ps_map, ps_map_opts, ps_map_profiled and ps_map_to_bam: written in place. */
 int ps_index(const char *ref_fa);
 
 /* `bwa parasuite` (or `bwa aln` when error_profile is NULL) + `bwa samse` fused: FASTQ in, SAM out.

@@ -5,7 +5,6 @@
 // processes and three rewrites of the data for.  Formats follow the public SAM/BAM specification (SAMv1:
 // BGZF blocks of at most 64 KiB with the BC extra field, BAM records, binning index with 16 kb linear index);
 // integer tags take the smallest type as htslib's SAM parser does.  Host code only (zlib), no device work.
-#include <sys/stat.h>
 #include <zlib.h>
 #include <algorithm>
 #include <cctype>
@@ -392,11 +391,7 @@ static void write_bai(const std::string &bai_path, const Data &d, const Layout &
         for (uint64_t v : x.lin) put64(bai, v);
     }
     put64(bai, n_no_coor);
-    FILE *bi = std::fopen(bai_path.c_str(), "wb");
-    if (!bi) throw Error("cannot write " + bai_path);
-    bool ok = std::fwrite(bai.data(), 1, bai.size(), bi) == bai.size();
-    ok = (std::fclose(bi) == 0) && ok;
-    if (!ok) throw Error("short write on " + bai_path);
+    write_text_file(bai_path, bai);
 }
 
 // ---- Data (records in d.recs order) -> BGZF file (+ .bai)
@@ -588,16 +583,21 @@ void sam_to_bam(const char *sam_path, const char *bam_path, int min_mapq, bool s
 {
     threads = clamp_threads(threads);
     if (write_index && !sort_by_coordinate) throw Error("a .bai index needs coordinate-sorted output");
+    OutFiles files(".bam-tmp"); const std::string t = add_bam(files, bam_path, write_index);
+    files.refuse_inputs({sam_path}, "ps_sam_to_bam: ");
     Data d;
     load_sam(sam_path, min_mapq, threads, d);
     if (sort_by_coordinate) { header_sorted(d.text, "coordinate"); sort_records(d, false); }
-    write_bam(d, bam_path, write_index, threads, stats);
+    write_bam(d, t.c_str(), write_index, threads, stats);
+    files.publish_all(); files.keep();
 }
 
 // `samtools view -q <mapq> -b in.bam -o out.bam`
 void bam_view(const char *in_bam, const char *out_bam, int min_mapq, int threads, BamStats *stats)
 {
     threads = clamp_threads(threads);
+    OutFiles files(".bam-tmp"); const std::string t = files.add(out_bam);
+    files.refuse_inputs({in_bam}, "ps_bam_view: ");
     Data d;
     load_bam(in_bam, threads, d, nullptr, nullptr);
     if (min_mapq > 0) {
@@ -605,24 +605,30 @@ void bam_view(const char *in_bam, const char *out_bam, int min_mapq, int threads
         for (const Rec &r : d.recs) if (rec_mapq(d, r) >= min_mapq) keep.push_back(r);
         d.recs.swap(keep);
     }
-    write_bam(d, out_bam, false, threads, stats);
+    write_bam(d, t.c_str(), false, threads, stats);
+    files.publish_all(); files.keep();
 }
 
 // `samtools sort [-n] in.bam -o out.bam`
 void bam_sort(const char *in_bam, const char *out_bam, bool by_name, int threads, BamStats *stats)
 {
     threads = clamp_threads(threads);
+    OutFiles files(".bam-tmp"); const std::string t = files.add(out_bam);
+    files.refuse_inputs({in_bam}, "ps_bam_sort: ");
     Data d;
     load_bam(in_bam, threads, d, nullptr, nullptr);
     header_sorted(d.text, by_name ? "queryname" : "coordinate");
     sort_records(d, by_name);
-    write_bam(d, out_bam, false, threads, stats);
+    write_bam(d, t.c_str(), false, threads, stats);
+    files.publish_all(); files.keep();
 }
 
 // `samtools index in.bam`: <in.bam>.bai for a coordinate-sorted file, the file itself is not rewritten
 void bam_index(const char *bam, int threads)
 {
     threads = clamp_threads(threads);
+    OutFiles files(".bam-tmp"); const std::string t = files.add(std::string(bam) + ".bai");
+    files.refuse_inputs({bam}, "ps_bam_index: ");
     Data d; Blocks bk; std::vector<uint64_t> rec_u;
     load_bam(bam, threads, d, &bk, &rec_u);
     for (size_t i = 1; i < d.recs.size(); ++i) {
@@ -644,7 +650,8 @@ void bam_index(const char *bam, int threads)
     };
     Layout lay; lay.vbeg.resize(d.recs.size()); lay.vend.resize(d.recs.size());
     for (size_t i = 0; i < d.recs.size(); ++i) { lay.vbeg[i] = voff(rec_u[i]); lay.vend[i] = voff_end(rec_u[i] + d.recs[i].len); }
-    write_bai(std::string(bam) + ".bai", d, lay);
+    write_bai(t, d, lay);
+    files.publish_all(); files.keep();
 }
 
 static std::string header_sort_order(const std::string &text)
@@ -721,22 +728,15 @@ void load_rec_table(const char *path, unsigned columns, int threads, RecTable &o
     flatten_records(f, columns, nullptr, threads, out);
 }
 
-bool same_file(const char *a, const char *b)
-{
-    if (!std::strcmp(a, b)) return true;
-    struct stat sa, sb;
-    return stat(a, &sa) == 0 && stat(b, &sb) == 0 && sa.st_dev == sb.st_dev && sa.st_ino == sb.st_ino;
-}
-
-// ExtractWeakMappingReads.java:40-94.  The FASTQ text and the list of kept records are complete before either file is opened, so
-// an error (a weak record without SEQ or QUAL) leaves nothing behind.  The price is a second copy in memory of every weak read's
-// bases and qualities next to the encoded records; if that ever matters, check the error conditions in a first pass over the
-// records and stream the text in a second.
+// ExtractWeakMappingReads.java:40-94.  The FASTQ text and the list of kept records are complete before either file is written: a
+// second copy in memory of every weak read's bases and qualities next to the encoded records; if that ever matters, check the
+// error conditions in a first pass over the records and stream the text in a second.  An error leaves nothing behind (§4m).
 void extract_weak_reads(const char *path, const char *out_bam, const char *out_fastq, int mapq_threshold, int threads, ExtractStats *stats)
 {
     threads = clamp_threads(threads);
     if (!path || !out_bam || !out_fastq || !out_bam[0] || !out_fastq[0]) throw Error("ps_extract_weak_reads: mapping file, output BAM and output FASTQ are required");
-    if (same_file(path, out_bam) || same_file(path, out_fastq)) throw Error(std::string("ps_extract_weak_reads: the output may not be the input file ") + path + " (write to a new name and rename)");
+    OutFiles files(".extract-tmp"); const std::string t_bam = files.add(out_bam), t_fq = files.add(out_fastq);
+    files.refuse_inputs({path}, "ps_extract_weak_reads: ", " may not be the input file ");
     if (same_file(out_bam, out_fastq)) throw Error("ps_extract_weak_reads: the BAM and the FASTQ output are the same file");
     Data d;
     load_any(path, threads, d);
@@ -769,14 +769,9 @@ void extract_weak_reads(const char *path, const char *out_bam, const char *out_f
     const uint64_t n_records = d.recs.size();
     d.recs.swap(keep);
     BamStats bs;
-    try {
-        write_bam(d, out_bam, false, threads, &bs);
-        FILE *f = std::fopen(out_fastq, "wb");
-        if (!f) throw Error(std::string("cannot write ") + out_fastq);
-        bool ok = std::fwrite(fq.data(), 1, fq.size(), f) == fq.size();
-        ok = (std::fclose(f) == 0) && ok;
-        if (!ok) throw Error(std::string("short write on ") + out_fastq);
-    } catch (...) { std::remove(out_bam); std::remove(out_fastq); throw; }
+    write_bam(d, t_bam.c_str(), false, threads, &bs);
+    write_text_file(t_fq, fq);
+    files.publish_all(); files.keep();
     if (stats) { stats->n_records = n_records; stats->n_weak = n_weak; stats->n_kept = bs.n_out; stats->bam_bytes = bs.bam_bytes; }
 }
 

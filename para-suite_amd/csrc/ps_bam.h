@@ -4,6 +4,7 @@
 #include <string>
 #include <utility>
 #include <vector>
+#include "ps_outfiles.h"
 namespace ps {
 struct BamStats { uint64_t n_in = 0, n_out = 0, bam_bytes = 0; };
 // one encoded BAM record inside a buffer of records: reference id, 0-based position and end, flag, byte range [off, off + len)
@@ -37,7 +38,9 @@ public:
 private:
     struct Impl; Impl *p;
 };
-// all throw std::runtime_error; min_mapq: records with MAPQ below it are dropped (samtools view -q)
+// a BAM among a call's outputs, with the <path>.bai that BamSink and the writers below put beside the path they are given
+inline std::string add_bam(OutFiles &files, const std::string &bam, bool index) { const std::string t = files.add(bam); if (index) files.add(bam + ".bai", t + ".bai"); return t; }
+// all throw ps::Error; each owns its outputs (ps_outfiles.h) and refuses one that is its input.  min_mapq: records with MAPQ below it are dropped (samtools view -q)
 void sam_to_bam(const char *sam_path, const char *bam_path, int min_mapq, bool sort_by_coordinate, bool write_index, int threads, BamStats *stats);
 void bam_view(const char *in_bam, const char *out_bam, int min_mapq, int threads, BamStats *stats);     // samtools view -q Q -b
 void bam_sort(const char *in_bam, const char *out_bam, bool by_name, int threads, BamStats *stats);    // samtools sort [-n]
@@ -73,7 +76,6 @@ struct RecTable {
 // "more than 2^32 CIGAR operations" -- the caller puts its name in front.
 void flatten_records(const BamFile &f, unsigned columns, const std::vector<int32_t> *rows, int threads, RecTable &out);
 void load_rec_table(const char *sam_or_bam, unsigned columns, int threads, RecTable &out);   // load_records + flatten_records of all rows
-bool same_file(const char *a, const char *b);   // the same path, or two paths to one file (device and inode)
 struct ExtractStats { uint64_t n_records = 0, n_weak = 0, n_kept = 0, bam_bytes = 0; };
 // ExtractWeakMappingReads.extractReads: records with MAPQ < mapq_threshold -> four FASTQ lines each (read orientation restored),
 // the others -> out_bam with the input's header

@@ -228,7 +228,8 @@ void benchmark_run(const char *mapping_path, const char *out_path, const char *r
     const std::string who = "ps_benchmark_reads: ";
     if (!mapping_path || !mapping_path[0] || !out_path || !out_path[0] || !reads_path || !reads_path[0])
         throw Error(who + "mapping file, statistics file and reads file are required");
-    if (same_file(out_path, mapping_path) || same_file(out_path, reads_path)) throw Error(who + "the output may not be one of the inputs");
+    OutFiles files(".benchmark-tmp"); const std::string tmp_path = files.add(out_path);
+    files.refuse_inputs({mapping_path, reads_path}, who);
     require_device(device);                                                // before the files are read
     BmTimes tm; ps_benchmark_stats st{};
     size_t piece = kBmPiece;
@@ -360,7 +361,7 @@ void benchmark_run(const char *mapping_path, const char *out_path, const char *r
     const BenchmarkRatios rt = benchmark_ratios(st);
     const std::string text = benchmark_text(st, rt);
     st.precision = rt.precision; st.recall = rt.recall; st.accuracy = rt.accuracy;
-    try { write_text_file(out_path, text, true); } catch (const std::exception &e) { throw Error(who + e.what()); }
+    try { write_text_file(tmp_path, text); files.publish_all(); files.keep(); } catch (const std::exception &e) { throw Error(who + e.what()); }
     tm.write = ms_since(t0);
     if (stats) *stats = st;
     if (std::getenv("PS_VERBOSE"))

@@ -26,6 +26,20 @@ struct ps_batch { std::unique_ptr<Batch> b; };
 static_assert(sizeof(ps_aln) == sizeof(AlnRec), "ps_aln layout");
 static void put(ps_bam_stats *st, const BamStats &s) { if (st) { st->n_in = s.n_in; st->n_out = s.n_out; st->bam_bytes = s.bam_bytes; } }
 static int first_device() { const char *e = std::getenv("PARASUITE_GPU_IDS"); return e ? std::atoi(e) : 0; }     // the calls that use one device
+// what ps_error_profile (quals 0: the mapper's two files) and ps_error_profile_full (1, 2: all six) do: count, write, publish together
+static void profile_files(const std::string &who, const char *mapping, const char *ref_fa, int max_len, const char *out_prefix, int quals, ProfileCounts &c, double *ms_parse)
+{
+    static const char *const ext[6] = {".errorprofile", ".indelprofile", ".errorprofile.vcf", ".qualityPerMismatch", ".indels", ".qualities"};
+    if (!mapping || !ref_fa) throw Error(who + "mapping and reference are required");
+    const std::string ref = ref_fa, prefix = out_prefix && out_prefix[0] ? out_prefix : mapping, tmp = prefix + ".profile-tmp";
+    OutFiles files(".profile-tmp");
+    for (int k = 0; k < (quals ? 6 : 2); ++k) files.add(prefix + ext[k], tmp + ext[k]);
+    files.refuse_inputs({mapping, ref_fa, (ref + ".ann").c_str(), (ref + ".pac").c_str()}, who);
+    error_profile_count(mapping, ref_fa, max_len, first_device(), 8, c, quals, ms_parse);
+    error_profile_write(c, tmp);
+    if (quals) error_profile_write_extra(c, tmp);
+    files.publish_all(); files.keep();
+}
 
 extern "C" {
 
@@ -396,15 +410,14 @@ void ps_release_host_cache(void) { try { trash_collect(); pin_cache_release(); }
 
 int ps_parse_check(const char *reads_path, int threads, uint64_t chunk_bytes, uint64_t out[4]) { PS_TRY parse_check(reads_path, threads, (size_t)chunk_bytes, out); return 0; PS_CATCH_INT }
 
+// The modes below publish their output files one way (ps_outfiles.h): an error leaves none of them.
 // Error-profile estimation from a mapping (the stage between the two passes of a --refine run, Main.java:320-340): what
 // `new ErrorProfiling(mapping, reference, maxReadLength).inferErrorProfile(false, false)` writes for the mapper.
 int ps_error_profile(const char *mapping_sam_or_bam, const char *ref_fa, int max_read_len, const char *out_prefix)
 {
     PS_TRY
         ProfileCounts c;
-        const int dev = first_device();
-        error_profile_count(mapping_sam_or_bam, ref_fa, max_read_len, dev, 8, c);
-        error_profile_write(c, out_prefix && out_prefix[0] ? out_prefix : mapping_sam_or_bam);
+        profile_files("ps_error_profile: ", mapping_sam_or_bam, ref_fa, max_read_len, out_prefix, 0, c, nullptr);
         if (std::getenv("PS_VERBOSE"))
             std::fprintf(stderr, "[parasuite-hip] ps_error_profile: %llu records, %llu counted (%llu unmapped, %llu duplicate, %llu without position, %llu with indels, %llu skipped)\n",
                          c.n_records, c.n_processed, c.n_unmapped, c.n_duplicate, c.n_start_zero, c.n_indel_reads, c.n_skipped);
@@ -413,19 +426,14 @@ int ps_error_profile(const char *mapping_sam_or_bam, const char *ref_fa, int max
 }
 
 // All six files of ErrorProfiling.inferErrorProfile(infer_qualities, false) -- the toolkit's `error` mode (Main.java:560-597):
-// the two above, byte for byte, and .errorprofile.vcf, .qualityPerMismatch, .indels, .qualities.  Nothing is written unless
-// every count was taken.
+// the two above, byte for byte, and .errorprofile.vcf, .qualityPerMismatch, .indels, .qualities.
 int ps_error_profile_full(const char *mapping_sam_or_bam, const char *ref_fa, int max_read_len, const char *out_prefix,
                           int infer_qualities, ps_profile_stats *stats)
 {
     PS_TRY
         ProfileCounts c;
-        const int dev = first_device();
         double ms_parse = 0;
-        error_profile_count(mapping_sam_or_bam, ref_fa, max_read_len, dev, 8, c, infer_qualities ? 2 : 1, &ms_parse);
-        const std::string prefix = out_prefix && out_prefix[0] ? out_prefix : mapping_sam_or_bam;
-        error_profile_write(c, prefix);
-        error_profile_write_extra(c, prefix);
+        profile_files("ps_error_profile_full: ", mapping_sam_or_bam, ref_fa, max_read_len, out_prefix, infer_qualities ? 2 : 1, c, &ms_parse);
         if (stats) {
             stats->n_records = c.n_records; stats->n_counted = c.n_processed; stats->n_unmapped = c.n_unmapped; stats->n_duplicate = c.n_duplicate;
             stats->n_start_zero = c.n_start_zero; stats->n_indel_reads = c.n_indel_reads; stats->n_skipped = c.n_skipped;
@@ -440,8 +448,7 @@ int ps_error_profile_full(const char *mapping_sam_or_bam, const char *ref_fa, in
     PS_CATCH_INT
 }
 
-// The toolkit's `clust` mode (Main.java:601-639): PileupClusters.calculateReadPileups, its six files.  Nothing is written unless
-// every count was taken.
+// The toolkit's `clust` mode (Main.java:601-639): PileupClusters.calculateReadPileups, its six files.
 int ps_pileup_clusters(const char *mapping_sam_or_bam, const char *ref_fa, const char *out_file, const char *snp_vcf,
                        int min_read_coverage, const char *site_prefix, ps_cluster_stats *stats)
 {
@@ -464,8 +471,7 @@ int ps_extract_weak_reads(const char *mapping_sam_or_bam, const char *out_bam, c
     PS_CATCH_INT
 }
 
-// Step 5 of `map -t` and the `comb` mode (Main.java:438-488): CombineGenomeTranscript.combine.  The output is opened only after
-// every device stage has completed and every lifted record is built: an error before that leaves no file.
+// Step 5 of `map -t` and the `comb` mode (Main.java:438-488): CombineGenomeTranscript.combine.
 int ps_combine_genome_transcript(const char *genome_bam, const char *transcript_bam, const char *out_bam, int sort_by_coordinate,
                                  int write_index, int threads, ps_combine_stats *stats)
 {
@@ -476,8 +482,7 @@ int ps_combine_genome_transcript(const char *genome_bam, const char *transcript_
     PS_CATCH_INT
 }
 
-// The toolkit's `benchmark` mode (Main.java:489-521): ValidateBenchmarkStatisticsPARCLIP.calculateBenchmarkStatistics.  The file is
-// opened only after both counting passes: an error before that leaves none.
+// The toolkit's `benchmark` mode (Main.java:489-521): ValidateBenchmarkStatisticsPARCLIP.calculateBenchmarkStatistics.
 int ps_benchmark_reads(const char *mapping_sam_or_bam, const char *out_statistics, const char *reads_fq, ps_benchmark_stats *stats)
 {
     PS_TRY
@@ -487,8 +492,7 @@ int ps_benchmark_reads(const char *mapping_sam_or_bam, const char *out_statistic
     PS_CATCH_INT
 }
 
-// The toolkit's `simulate` mode (Main.java:684-802): bin/createSimulatedPARCLIPDataset.pl.  The five files are written under
-// temporary names after every kernel has run and renamed together: an error leaves none.
+// The toolkit's `simulate` mode (Main.java:684-802): bin/createSimulatedPARCLIPDataset.pl.  The five files are renamed together.
 int ps_simulate_reads(const ps_simulate_opts *opts, ps_simulate_stats *stats)
 {
     PS_TRY
@@ -500,7 +504,6 @@ int ps_simulate_reads(const ps_simulate_opts *opts, ps_simulate_stats *stats)
 }
 
 // The toolkit's `fetch` and `fetchBed` modes (Main.java:883-945): FetchSequencesForBindingSites / FetchSequencesForBEDFile.fetchSequences.
-// The output is written under a temporary name and renamed: an error leaves none.
 int ps_fetch_sequences(const char *ref_fa, const char *sites, const char *out_file, int bed, ps_fetch_stats *stats)
 {
     PS_TRY

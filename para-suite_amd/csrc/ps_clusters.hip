@@ -650,11 +650,16 @@ void pileup_clusters_run(const char *mapping, const char *ref_fa, const char *ou
 {
     if (!mapping || !ref_fa || !out_file || !out_file[0]) throw Error("ps_pileup_clusters: mapping, reference and output file are required");
     ClResult r;
+    const std::string out = out_file, sp = site_prefix && site_prefix[0] ? site_prefix : mapping, ref = ref_fa;
+    const std::pair<std::string, const std::string *> texts[6] = {{out, &r.out}, {out + ".ccr.fasta", &r.fasta}, {out + ".ccr.tsv", &r.tsv}, {out + ".report", &r.report},
+                                                                  {sp + ".sitefrequency.tsv", &r.sitefreq}, {sp + ".sitepositions.tsv", &r.sitepos}};
+    OutFiles files(".clusters-tmp");
+    for (const auto &x : texts) files.add(x.first);
+    files.refuse_inputs({mapping, ref_fa, (ref + ".ann").c_str(), (ref + ".pac").c_str(), snp_vcf}, "ps_pileup_clusters: ");
     pileup_clusters(mapping, ref_fa, snp_vcf, min_cov, device, 8, r);
-    const std::string out = out_file, sp = site_prefix && site_prefix[0] ? site_prefix : mapping;
     const auto t0 = HostClock::now();
-    write_text_file(out, r.out); write_text_file(out + ".ccr.fasta", r.fasta); write_text_file(out + ".ccr.tsv", r.tsv); write_text_file(out + ".report", r.report);
-    write_text_file(sp + ".sitefrequency.tsv", r.sitefreq); write_text_file(sp + ".sitepositions.tsv", r.sitepos);
+    for (const auto &x : texts) write_text_file(files.tmp(x.first), *x.second);
+    files.publish_all(); files.keep();
     r.ms_text += ms_since(t0);
     if (stats) *stats = r.st;
     if (std::getenv("PS_VERBOSE"))

@@ -198,7 +198,8 @@ void combine_run(const char *genome_path, const char *transcript_path, const cha
                  int threads, int device, ps_combine_stats *stats)
 {
     if (!genome_path || !transcript_path || !out_bam || !out_bam[0]) throw Error("ps_combine_genome_transcript: genomic mapping, transcript mapping and output file are required");
-    if (same_file(out_bam, genome_path) || same_file(out_bam, transcript_path)) throw Error("ps_combine_genome_transcript: the output may not be one of the inputs");
+    OutFiles files(".combine-tmp"); const std::string t = add_bam(files, out_bam, write_index);
+    files.refuse_inputs({genome_path, transcript_path}, "ps_combine_genome_transcript: ");
     if (write_index && !sort_by_coordinate) throw Error("a .bai index needs coordinate-sorted output");
     require_device(device);                                                // before the files are read
     const auto t0 = HostClock::now();
@@ -210,12 +211,13 @@ void combine_run(const char *genome_path, const char *transcript_path, const cha
         other.join();
         if (!err.empty()) throw Error(err);
     }
-    combine_records(G, T, transcript_path, out_bam, sort_by_coordinate, write_index, threads, device, stats, ms_since(t0));
+    combine_records(G, T, transcript_path, t.c_str(), sort_by_coordinate, write_index, threads, device, stats, ms_since(t0));
+    files.publish_all(); files.keep();
 }
 
 // the same on records in memory (both are consumed): the files' loader above, or ps_map_route's passes, which hand over what they
 // have just written.  transcript_path: what the error messages call the transcript mapping.  The caller has checked the
-// arguments (combine_run above; ps_map_route always asks for the sorted, indexed form on a device it has used).
+// arguments (combine_run above; ps_map_route always asks for the sorted, indexed form on a device it has used) and owns out_bam (§4m).
 void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const char *out_bam, bool sort_by_coordinate, bool write_index,
                      int threads, int device, ps_combine_stats *stats, double parse_ms)
 {
@@ -377,16 +379,14 @@ void combine_records(BamFile &G, BamFile &T, const char *transcript_path, const 
     // genomic records in file order, then the lifted ones
     t0 = HostClock::now();
     BamStats bst;
-    try {
-        BamSink sink(G.text, G.refs, out_bam, sort_by_coordinate, write_index, threads, 6);
-        std::vector<std::vector<BamRec>> grecs(G.enc.size());
-        for (const BamRec &r : G.recs) grecs[(size_t)r.part].push_back(r);
-        const uint64_t n_g = G.n();
-        G.recs.clear(); G.recs.shrink_to_fit();
-        sink.add(G.enc, grecs, n_g);
-        sink.add(bufs, brecs, st.n_lifted);
-        sink.finish(&bst);
-    } catch (...) { std::remove(out_bam); std::remove((std::string(out_bam) + ".bai").c_str()); throw; }
+    BamSink sink(G.text, G.refs, out_bam, sort_by_coordinate, write_index, threads, 6);
+    std::vector<std::vector<BamRec>> grecs(G.enc.size());
+    for (const BamRec &r : G.recs) grecs[(size_t)r.part].push_back(r);
+    const uint64_t n_g = G.n();
+    G.recs.clear(); G.recs.shrink_to_fit();
+    sink.add(G.enc, grecs, n_g);
+    sink.add(bufs, brecs, st.n_lifted);
+    sink.finish(&bst);
     tm.write = ms_since(t0);
     st.bam_bytes = bst.bam_bytes;
     if (stats) *stats = st;

@@ -1,5 +1,5 @@
 // ps_dev.h -- what the host code of every analysis mode does around its kernels (ps_profile, ps_clusters, ps_combine,
-// ps_benchmark; the clock and the event timer serve the mapping stages too): a stream of its own, tables onto the device, a hipCUB call, times, the reference's tables, a text file.
+// ps_benchmark; the clock and the event timer serve the mapping stages too): a stream of its own, tables onto the device, a hipCUB call, times, the reference's tables (a text file: ps_outfiles.h).
 #pragma once
 #include <algorithm>
 #include <chrono>
@@ -7,6 +7,7 @@
 #include <map>
 #include "ps_host.h"
 #include "ps_bam.h"
+#include "ps_outfiles.h"
 
 namespace ps {
 
@@ -109,14 +110,5 @@ struct RefHoleChars {
         PS_HIP(hipStreamSynchronize(s));
     }
 };
-
-// text -> file, checked; remove_failed: a file that could be opened but not written whole is removed
-inline void write_text_file(const std::string &path, const std::string &text, bool remove_failed = false)
-{
-    FILE *f = std::fopen(path.c_str(), "wb");
-    if (!f) throw Error("cannot write " + path);
-    const bool ok = std::fwrite(text.data(), 1, text.size(), f) == text.size();
-    if (std::fclose(f) != 0 || !ok) { if (remove_failed) std::remove(path.c_str()); throw Error("cannot write " + path); }
-}
 
 }  // namespace ps

@@ -17,7 +17,6 @@
 //                   while the next is gathered: two buffers, one stream each
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
-#include <sys/stat.h>
 #include <algorithm>
 #include <climits>
 #include <cstdio>
@@ -108,15 +107,15 @@ struct FetchWiden { __host__ __device__ uint64_t operator()(int32_t v) const { r
 // up to field 11, and what is kept behind it), fetchBed ">" [a0, a1) "\n" sequence "\n" (field 3)
 struct FetchText { size_t a0, a1, b0, b1; };
 
-struct FetchOutput {                   // the output under its temporary name; renamed when complete, removed otherwise
-    std::string name, tmp; FILE *f = nullptr; std::string buf; bool done = false;
-    explicit FetchOutput(const std::string &out) : name(out), tmp(out + ".fetch-tmp")
+struct FetchOutput {                   // the buffered text of the output, written where the call's OutFiles says
+    const std::string tmp; FILE *f = nullptr; std::string buf;
+    explicit FetchOutput(const std::string &path) : tmp(path)
     {
         f = std::fopen(tmp.c_str(), "wb");
         if (!f) throw Error("cannot write " + tmp);
         buf.reserve((size_t)5 << 20);
     }
-    ~FetchOutput() { if (f) std::fclose(f); if (!done) std::remove(tmp.c_str()); }
+    ~FetchOutput() { if (f) std::fclose(f); }
     void flush()
     {
         if (!buf.empty() && std::fwrite(buf.data(), 1, buf.size(), f) != buf.size()) throw Error("cannot write " + tmp);
@@ -124,27 +123,13 @@ struct FetchOutput {                   // the output under its temporary name; r
     }
     void put(const void *p, size_t n) { buf.append((const char *)p, n); if (buf.size() >= ((size_t)4 << 20)) flush(); }
     void put(char c) { buf.push_back(c); }
-    void commit()
+    void close()
     {
         flush();
         const int rc = std::fclose(f); f = nullptr;
         if (rc != 0) throw Error("cannot write " + tmp);
-        if (std::rename(tmp.c_str(), name.c_str()) != 0) throw Error("cannot rename " + tmp + " to " + name);
-        done = true;
     }
 };
-
-void fetch_read_file(const char *path, std::vector<char> &data)
-{
-    FILE *f = std::fopen(path, "rb");
-    if (!f) throw Error(std::string("cannot open ") + path);
-    struct Closer { FILE *f; ~Closer() { std::fclose(f); } } closer{f};
-    struct stat sb;
-    if (fstat(fileno(f), &sb) == 0 && S_ISREG(sb.st_mode)) data.reserve((size_t)sb.st_size);   // one allocation for a regular file
-    std::vector<char> chunk((size_t)1 << 20); size_t got;
-    while ((got = std::fread(chunk.data(), 1, chunk.size(), f)) > 0) data.insert(data.end(), chunk.data(), chunk.data() + got);
-    if (std::ferror(f)) throw Error(std::string("cannot read ") + path);
-}
 
 }  // namespace
 
@@ -154,9 +139,10 @@ void fetch_run(const char *ref_fa, const char *sites_path, const char *out_path,
     const std::string who = "ps_fetch_sequences: ";
     if (!ref_fa || !ref_fa[0] || !sites_path || !sites_path[0] || !out_path || !out_path[0])
         throw Error(who + "reference, sites file and output file are required");
-    const std::string ref(ref_fa), tmp_name = std::string(out_path) + ".fetch-tmp";
-    for (const std::string &in : {std::string(sites_path), ref, ref + ".ann", ref + ".pac"})
-        if (same_file(out_path, in.c_str()) || same_file(tmp_name.c_str(), in.c_str())) throw Error(who + "the output may not be one of the inputs (" + in + ")");
+    const std::string ref(ref_fa);
+    OutFiles files(".fetch-tmp");
+    const std::string tmp_name = files.add(out_path);
+    files.refuse_inputs({sites_path, ref_fa, (ref + ".ann").c_str(), (ref + ".pac").c_str()}, who, " may not be one of the inputs: ");
     require_device(device);                                                // before the files are read
     const auto t_all = clk::now();
     ps_fetch_stats st{};
@@ -173,8 +159,7 @@ void fetch_run(const char *ref_fa, const char *sites_path, const char *out_path,
 
     // ---- the sites file: lines, then every data line on its own
     t0 = clk::now();
-    std::vector<char> data;
-    fetch_read_file(sites_path, data);
+    const std::string data = read_whole_file(sites_path);
     const char *d = data.data(); const size_t nd = data.size();
     std::vector<size_t> line_b, line_e;                                    // BufferedReader.readLine: "\n", "\r" or "\r\n"
     size_t next_lf = SIZE_MAX;
@@ -281,7 +266,7 @@ void fetch_run(const char *ref_fa, const char *sites_path, const char *out_path,
             PS_HIP(hipMemcpyAsync(pin[slot].p, dev[slot].p, (size_t)(p1 - p0), hipMemcpyDeviceToHost, q));
         };
         const auto w0 = clk::now();
-        FetchOutput out(out_path);
+        FetchOutput out(tmp_name);
         out.put(d + line_b[0], line_e[0] - line_b[0]); out.put('\n');
         ms_write += ms_since(w0);
         size_t site = 0; uint64_t done = 0; bool open = false;             // the writer: `done` bases of `site` are out, its lead too when `open`
@@ -312,7 +297,7 @@ void fetch_run(const char *ref_fa, const char *sites_path, const char *out_path,
         }
         if (site != n) throw Error(who + "internal: the stream ended before the last site");
         const auto w2 = clk::now();
-        out.commit();
+        out.close(); files.publish_all(); files.keep();
         ms_write += ms_since(w2);
     }
     unsigned long long holes = 0;

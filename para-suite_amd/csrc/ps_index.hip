@@ -689,14 +689,15 @@ template <class T> static void read_dev(LoadStage &st, const std::string &path, 
     if (!ok) throw Error("truncated " + path);
 }
 
+// renamed together, .ann last: a save that was cut off leaves no whole-looking index, a .pac that is mapped is replaced, not truncated (§4m)
 void index_save(const Index &ix, const std::string &prefix)
 {
-    write_dev(prefix + ".bwt", MAGIC_BWT, ix.blocks);
-    write_dev(prefix + ".sa", "PSSA0002", ix.sa);
-    write_dev(prefix + ".pac", "PSPAC001", ix.pac);
-    std::ofstream a(prefix + ".ann", std::ios::binary);
-    a << index_meta_serialize(ix);
-    if (!a.good()) throw Error("cannot write " + prefix + ".ann");
+    OutFiles files(".index-tmp");
+    write_dev(files.add(prefix + ".bwt"), MAGIC_BWT, ix.blocks);
+    write_dev(files.add(prefix + ".sa"), "PSSA0002", ix.sa);
+    write_dev(files.add(prefix + ".pac"), "PSPAC001", ix.pac);
+    write_text_file(files.add(prefix + ".ann"), index_meta_serialize(ix));
+    files.publish_all(); files.keep();
 }
 
 // the .pac file mapped for the host side; if it cannot be mapped, read into ref.pac

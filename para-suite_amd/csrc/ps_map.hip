@@ -62,14 +62,7 @@ struct SamText : PassOut {
     SamText(const char *p, int n, double &t) : path(p), nthr(n), busy(t) {}
     void start() override { const int fd = ::open(path, O_WRONLY | O_CREAT | O_TRUNC, 0644); if (fd >= 0) ::close(fd); }    // an output file that exists is emptied now: giving back 2 GB of cached pages takes 0.3 s
     void piece(Batch &b) override { Charge c{busy}; batch_write_sam(b, path, first, PS_PG_LINE, nthr, !first, &scratch); first = false; }
-    void empty(const Ctx &c) override            // the header alone, as upstream's samse prints it before its read loop
-    {
-        const std::string h = sam_header(c.ix.ref, PS_PG_LINE);
-        FILE *f = std::fopen(path, "wb");
-        if (!f) throw Error(std::string("cannot write ") + path);
-        const bool ok = std::fwrite(h.data(), 1, h.size(), f) == h.size();
-        if (std::fclose(f) != 0 || !ok) throw Error(std::string("short write on ") + path);
-    }
+    void empty(const Ctx &c) override { write_text_file(path, sam_header(c.ix.ref, PS_PG_LINE)); }   // the header alone, as upstream's samse prints it before its read loop
 };
 
 // ps_map_to_bam: records go out as BAM, no SAM text at all.  by_name, keep (ps_map_route): sorted by read name; the sorted records also stay in memory
@@ -556,17 +549,6 @@ void map_to_bam(const MapArgs &a, const char *out_bam, int min_mapq, bool sort_b
 // counted from its records in memory (ps_map_profiled's path); the weak reads of the last genomic pass go to the transcript pass as a
 // ReadSet, not as FASTQ text; the sorted records of the last genomic pass and of the transcript pass stay in memory for the lift.
 namespace {
-struct RouteFiles {                    // outputs are written under a temporary name and renamed when their step is done; a failed call removes both kinds
-    std::vector<std::string> tmp, made;
-    static std::string tmp_name(const std::string &name) { return name + ".route-tmp"; }
-    std::string open(const std::string &name) { const std::string t = tmp_name(name); tmp.push_back(t); return t; }
-    void publish(const std::string &t, const std::string &name)
-    {
-        if (std::rename(t.c_str(), name.c_str()) != 0) throw Error("cannot rename " + t + " to " + name);
-        made.push_back(name);
-    }
-    void drop() { for (const std::string &f : tmp) std::remove(f.c_str()); for (const std::string &f : made) std::remove(f.c_str()); }
-};
 size_t readset_bytes(const ReadSet &rs)
 {
     return rs.len.size() * 4 + rs.off.size() * 8 + rs.name_off.size() * 8 + rs.seq.size() + rs.qual.size() + rs.names.size();
@@ -597,12 +579,12 @@ bool has(const char *s) { return s && s[0]; }
 // the call's state between its passes, and one pass of it
 struct Route {
     const ps_route_opts &o; const int threads, gm; int bam_level = 1;
-    RouteFiles files; CtxSet genome, transcripts;   // the call's own contexts: open from pass to pass, closed when it returns
+    OutFiles &files; CtxSet genome, transcripts;    // the call's outputs (published step by step); its own contexts: open from pass to pass, closed when it returns
     ResidentUse use; Residents::Entry *eg = nullptr, *et = nullptr; int g_loads0 = 0, t_loads0 = 0;    // inside a resident scope: the scope's entries instead, which stay
     std::vector<ReadSet> kept, weak; size_t kept_bytes = 0, keep_bound = (size_t)8192 << 20; bool kept_all = true;
     uint64_t n_weak = 0;
     BamFile G, T;
-    Route(const ps_route_opts &opts, int thr, int mapq_genomic) : o(opts), threads(thr), gm(mapq_genomic)
+    Route(const ps_route_opts &opts, int thr, int mapq_genomic, OutFiles &outs) : o(opts), threads(thr), gm(mapq_genomic), files(outs)
     {
         if (const char *e = std::getenv("PS_ROUTE_KEEP_MB")) keep_bound = (size_t)std::max(0, std::atoi(e)) << 20;
         if (const char *e = std::getenv("PS_BAM_LEVEL")) bam_level = std::atoi(e);
@@ -620,11 +602,11 @@ struct Route {
     void pass(MapJob &job, const char *mm, const char *ep, const char *ip, const char *ref, const std::string &out, int min_mapq, bool by_name, BamFile *keep_recs, ps_bam_stats &bs_out)
     {
         BamStats bs; BamOut bo; bo.min_mapq = min_mapq; bo.sort = !by_name; bo.index = !by_name; bo.by_name = by_name; bo.keep = keep_recs; bo.stats = &bs; bo.level = bam_level;
-        const std::string t = files.open(out); if (!by_name) files.tmp.push_back(t + ".bai");
+        const std::string t = files.tmp(out);
         job.a = MapArgs{threads, mm, ep, ip, ref, o.reads_fq}; job.bam_out = true;
         job.outs.emplace(job.outs.begin(), new BamRecords(bo, t.c_str(), threads, job.s_write));
         Pass(job).run();
-        files.publish(t, out); if (!by_name) files.publish(t + ".bai", out + ".bai");
+        files.publish(out); if (!by_name) files.publish(out + ".bai");
         bs_out.n_in = bs.n_in; bs_out.n_out = bs.n_out; bs_out.bam_bytes = bs.bam_bytes;
     }
     // the contexts of a pass; the transcript pass takes over the lanes of work of the genome passes
@@ -659,26 +641,18 @@ void map_route(const ps_route_opts *o, ps_route_stats *stats_out)
     const std::string f_bwa = P + ".BWA-genomic.bam", f_para = P + ".PARAsuite-genomic.bam", f_comb = P + ".combined.bam";
     const std::string f_tr = P + (refine ? ".PARAsuite-transcript.bam" : ".BWA-transcript.bam");
     const std::string f_ep = f_bwa + ".errorprofile", f_ip = f_bwa + ".indelprofile";
-    {
-        // every name the call writes: the outputs, and the temporary name each is written under (RouteFiles::open)
-        std::vector<std::string> outs;
-        auto bam = [&](const std::string &f, bool index) { outs.push_back(f); outs.push_back(RouteFiles::tmp_name(f)); if (index) { outs.push_back(f + ".bai"); outs.push_back(RouteFiles::tmp_name(f) + ".bai"); } };
-        if (first_pass) {
-            bam(f_bwa, true);
-            if (refine) for (const char *x : {".errorprofile", ".indelprofile"}) { outs.push_back(f_bwa + x); outs.push_back(RouteFiles::tmp_name(f_bwa + ".profile") + x); }
-        }
-        if (refine) bam(f_para, true);
-        if (with_t) { bam(f_tr, false); bam(f_comb, true); }
-        const char *ins[] = {o->reads_fq, o->ref_fa, o->transcripts_fa, o->error_profile, o->indel_profile};
-        for (const std::string &f : outs) for (const char *in : ins)
-            if (has(in) && same_file(f.c_str(), in)) throw Error("ps_map_route: the output " + f + " would overwrite the input " + in);
-    }
+    OutFiles files(".route-tmp");          // every output of the steps this call will run; ProfileOut writes <prefix>.errorprofile and .indelprofile
+    const std::string profile_tmp = f_bwa + ".profile.route-tmp";
+    if (first_pass) add_bam(files, f_bwa, true);
+    if (first_pass && refine) { files.add(f_ep, profile_tmp + ".errorprofile"); files.add(f_ip, profile_tmp + ".indelprofile"); }
+    if (refine) add_bam(files, f_para, true);
+    if (with_t) { add_bam(files, f_tr, false); add_bam(files, f_comb, true); }
+    files.refuse_inputs({o->reads_fq, o->ref_fa, o->transcripts_fa, o->error_profile, o->indel_profile}, "ps_map_route: ");
     { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error("ps_map_route: no HIP device available: parasuite-hip has no CPU path"); }
 
     const auto t_begin = clk::now();
     ps_route_stats st; std::memset(&st, 0, sizeof st);
-    Route r(*o, threads, gm);
-    RouteFiles &files = r.files;
+    Route r(*o, threads, gm, files);
     std::string step = "first pass";
     try {
         const bool weak_after_first = with_t && !refine;
@@ -686,11 +660,7 @@ void map_route(const ps_route_opts *o, ps_route_stats *stats_out)
         if (first_pass) {
             const auto t0 = clk::now();
             MapJob job; r.lend(job, false);
-            if (refine) {
-                const std::string prefix = files.open(f_bwa + ".profile");
-                files.tmp.push_back(prefix + ".errorprofile"); files.tmp.push_back(prefix + ".indelprofile");
-                job.outs.emplace_back(new ProfileOut(gm, max_len, prefix, threads, job.s_profile));
-            }
+            if (refine) job.outs.emplace_back(new ProfileOut(gm, max_len, profile_tmp, threads, job.s_profile));
             if (weak_after_first) job.outs.emplace_back(new PieceFn([&r](Batch &b) { r.weak_of(b); }));
             else if (refine) job.outs.emplace_back(new PieceFn([&r](Batch &b) { r.keep(b); }));
             r.pass(job, bwa_mm, nullptr, nullptr, o->ref_fa, f_bwa, gm, false, weak_after_first ? &r.G : nullptr, st.first);
@@ -699,8 +669,7 @@ void map_route(const ps_route_opts *o, ps_route_stats *stats_out)
             if (refine) {
                 step = "profile";
                 const auto t1 = clk::now();
-                const std::string prefix = RouteFiles::tmp_name(f_bwa + ".profile");
-                files.publish(prefix + ".errorprofile", f_ep); files.publish(prefix + ".indelprofile", f_ip);
+                files.publish(f_ep); files.publish(f_ip);
                 ep = f_ep; ip = f_ip;
                 st.s_profile = secs_since(t1);
             }
@@ -726,20 +695,19 @@ void map_route(const ps_route_opts *o, ps_route_stats *stats_out)
             step = "combine";
             const auto t1 = clk::now();
             const int dev = r.genome_set().xs[0]->device;                    // the first device of the passes
-            const std::string t = files.open(f_comb); files.tmp.push_back(t + ".bai");
-            combine_records(r.G, r.T, f_tr.c_str(), t.c_str(), true, true, threads, dev, &st.combine);
-            files.publish(t, f_comb); files.publish(t + ".bai", f_comb + ".bai");
+            combine_records(r.G, r.T, f_tr.c_str(), files.tmp(f_comb).c_str(), true, true, threads, dev, &st.combine);
+            files.publish(f_comb); files.publish(f_comb + ".bai");
             st.s_combine = secs_since(t1);
         }
         step = "closing";
         st.n_index_loads_genome = (uint32_t)(r.genome_set().n_index_loads - r.g_loads0); st.n_index_loads_transcripts = (uint32_t)(r.transcript_set().n_index_loads - r.t_loads0);
         r.close();
         r.use.done();
+        files.keep();
     } catch (const std::exception &e) {
         const std::string m = e.what();
         r.close();
-        files.drop();
-        throw Error("ps_map_route: " + step + ": " + m);
+        throw Error("ps_map_route: " + step + ": " + m);      // what the call wrote goes with `files`
     }
     st.s_total = secs_since(t_begin);
     if (stats_out) *stats_out = st;

@@ -296,17 +296,7 @@ namespace {
 
 using Text = std::string;
 
-Text sim_read_file(const std::string &who, const char *path)
-{
-    FILE *f = std::fopen(path, "rb");
-    if (!f) throw Error(who + "cannot open " + path);
-    Text out; char buf[1 << 16]; size_t k;
-    while ((k = std::fread(buf, 1, sizeof buf, f)) > 0) out.append(buf, k);
-    const bool bad = std::ferror(f) != 0;
-    std::fclose(f);
-    if (bad) throw Error(who + "cannot read " + path);
-    return out;
-}
+Text sim_read_file(const std::string &who, const char *path) { try { return read_whole_file(path); } catch (const std::exception &e) { throw Error(who + e.what()); } }
 // <FH> and chomp: lines end at "\n" only, a last line without one counts
 std::vector<Text> sim_lines(const Text &data)
 {
@@ -439,27 +429,6 @@ void sim_load_profiles(const std::string &who, const ps_simulate_opts &o, SimPar
 }
 
 Text sim_perl_num(double v) { char b[40]; std::snprintf(b, sizeof b, "%.15g", v); return b; }
-
-// the five outputs under temporary names; renamed together, or all removed
-struct SimOutputs {
-    std::vector<std::string> final_names, tmp_names; size_t renamed = 0; bool done = false;
-    ~SimOutputs()
-    {
-        if (done) return;
-        for (size_t i = 0; i < tmp_names.size(); ++i) std::remove(i < renamed ? final_names[i].c_str() : tmp_names[i].c_str());
-    }
-    void write(const std::string &name, const Text &text)
-    {
-        final_names.push_back(name); tmp_names.push_back(name + ".sim-tmp");
-        write_text_file(tmp_names.back(), text);
-    }
-    void commit()
-    {
-        for (; renamed < tmp_names.size(); ++renamed)
-            if (std::rename(tmp_names[renamed].c_str(), final_names[renamed].c_str()) != 0) throw Error("cannot write " + final_names[renamed]);
-        done = true;
-    }
-};
 
 void sim_scan(hipStream_t s, const DevBuf<unsigned long long> &in, DevBuf<unsigned long long> &out)
 {
@@ -654,12 +623,10 @@ void simulate_run(const ps_simulate_opts &o, int device, ps_simulate_stats *stat
                      "\nnumer snps generated: " + std::to_string(st.n_snps) + "\n\nSome parameters:\nselect_prob=" + sim_perl_num(P.select_read) +
                      "\nread bound by RBP probability: " + sim_perl_num(P.bound_prob) + "\n";
     {
-        SimOutputs out; const std::string prefix = o.out_prefix;
-        try {
-            out.write(prefix + ".fastq", fastq); out.write(prefix + ".clusters", clusters); out.write(prefix + "_snps.vsf", vsf);
-            out.write(prefix + ".log", log); out.write(prefix + ".err", err);
-            out.commit();
-        } catch (const std::exception &e) { throw Error(who + e.what()); }
+        OutFiles files(".sim-tmp"); const std::string prefix = o.out_prefix;      // the five outputs: renamed together, or all removed
+        const std::pair<const char *, const Text *> texts[5] = {{".fastq", &fastq}, {".clusters", &clusters}, {"_snps.vsf", &vsf}, {".log", &log}, {".err", &err}};
+        try { for (const auto &x : texts) write_text_file(files.add(prefix + x.first), *x.second); files.publish_all(); files.keep(); }
+        catch (const std::exception &e) { throw Error(who + e.what()); }
     }
     st.s_write = ms_since(t0) / 1e3; st.s_total = ms_since(t_all) / 1e3;
     if (stats) *stats = st;

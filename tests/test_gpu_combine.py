@@ -116,6 +116,26 @@ def test_errors_write_nothing(tmp_path, name):
     assert sorted(p.name for p in tmp_path.iterdir()) == ["g.sam", "t.sam"]
 
 
+def test_a_failed_call_leaves_the_output_from_before(tmp_path):
+    """the output files exist before a call that fails on its input: they are still there with their old bytes, and no temporary is"""
+    import capi
+    head, body = ERRORS[sorted(ERRORS)[0]]
+    g, t = _write(str(tmp_path / "g.sam"), g_header() + GENOME_RECS), _write(str(tmp_path / "t.sam"), head + body)
+    noq = _write(str(tmp_path / "noq.sam"), g_header() + "noq\t0\tchr1\t5\t3\t4M\t*\t0\t0\tACGT\t*\n")     # a weak record without QUAL
+    old = {n: ("from before: " + n).encode() for n in ("c.bam", "c.bam.bai", "k.bam", "w.fq")}
+    for n, text in old.items():
+        (tmp_path / n).write_bytes(text)
+    with pytest.raises(capi.PsError):
+        capi.ps_combine_genome_transcript(g, t, str(tmp_path / "c.bam"), sort_by_coordinate=True, write_index=True)
+    with pytest.raises(capi.PsError, match="noq has MAPQ below 10 and no QUAL"):
+        capi.ps_extract_weak_reads(noq, str(tmp_path / "k.bam"), str(tmp_path / "w.fq"), 10)
+    assert sorted(p.name for p in tmp_path.iterdir()) == sorted(["g.sam", "t.sam", "noq.sam"] + list(old))
+    assert {n: (tmp_path / n).read_bytes() for n in old} == old
+    with pytest.raises(capi.PsError, match="would overwrite the input"):
+        capi.ps_combine_genome_transcript(g, t, g)
+    assert open(g).read() == g_header() + GENOME_RECS
+
+
 def test_route_end_to_end(workdir):
     """ps_map_to_bam (genome, filter 0) -> ps_extract_weak_reads (10) -> ps_map_to_bam (transcripts, MAPQ 1) -> ps_bam_sort -n ->
     ps_combine_genome_transcript (sorted, indexed): (a) equals the restatement on the same two intermediate files, (b) lies

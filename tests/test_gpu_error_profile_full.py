@@ -157,3 +157,26 @@ def test_ragged_reads_and_too_long(workdir):
         capi.ps_error_profile_full(long_sam, fa, 250, os.path.join(d, "long_full"), True)
     assert str(e1.value) == str(e2.value)
     assert not [f for f in os.listdir(d) if f.startswith("long_")]
+
+
+def test_a_failure_on_the_last_file_leaves_none(workdir):
+    """<prefix>.qualities is taken by a directory: the call fails after every count was taken and none of the six files is left"""
+    import capi
+    d = os.path.join(workdir, "epf_late")
+    os.makedirs(d, exist_ok=True)
+    fa, sam, out = (os.path.join(d, n) for n in ("r.fa", "m.sam", "late"))
+    _index(fa, FA)
+    open(sam, "w").write(sam_text(RECORDS))
+    os.mkdir(out + ".qualities")
+    with pytest.raises(capi.PsError, match="cannot rename"):
+        capi.ps_error_profile_full(sam, fa, ML, out, True)
+    assert [f for f in os.listdir(d) if f.startswith("late")] == ["late.qualities"] and os.listdir(out + ".qualities") == []
+    os.rmdir(out + ".qualities")
+    capi.ps_error_profile_full(sam, fa, ML, out, True)                       # and with the name free, all six, no temporary
+    assert sorted(f for f in os.listdir(d) if f.startswith("late")) == sorted("late" + k for k in J.FILES)
+    named = os.path.join(d, "named.errorprofile")                            # a mapping under the name the profile would get
+    open(named, "w").write(sam_text(RECORDS))
+    for call in (capi.ps_error_profile, capi.ps_error_profile_full):
+        with pytest.raises(capi.PsError, match="would overwrite the input"):
+            call(named, fa, ML, named[:-len(".errorprofile")])
+    assert open(named).read() == sam_text(RECORDS) and [f for f in os.listdir(d) if f.startswith("named")] == ["named.errorprofile"]

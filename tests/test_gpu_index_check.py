@@ -78,3 +78,28 @@ def test_the_check_sees_a_damaged_index(multi):
         hb[2][100] ^= np.uint8(0x30)
     r = check(wrong_base)
     assert r["bad_symbols"] > 0, r
+
+
+def test_a_rebuild_that_fails_leaves_the_old_index(tmp_path):
+    """ps_index over a good index whose .ann name a directory has taken: the call fails and .bwt, .sa and .pac are the old files"""
+    import os
+    import capi
+    rng = np.random.default_rng(11)
+    fa = str(tmp_path / "g.fa")
+    open(fa, "w").write(">a\n%s\n>b\n%s\n" % tuple("".join("ACGT"[c] for c in rng.integers(0, 4, n)) for n in (1500, 700)))
+    capi.ps_index(fa)
+    assert sorted(os.listdir(tmp_path)) == ["g.fa", "g.fa.ann", "g.fa.bwt", "g.fa.pac", "g.fa.sa"]      # no temporary is left
+    old = {x: open(fa + x, "rb").read() for x in (".bwt", ".sa", ".pac", ".ann")}
+    ident = {x: os.stat(fa + x).st_ino for x in (".bwt", ".sa", ".pac")}
+    os.remove(fa + ".ann")
+    os.mkdir(fa + ".ann")
+    with pytest.raises(capi.PsError, match="cannot rename"):
+        capi.ps_index(fa)
+    assert sorted(os.listdir(tmp_path)) == ["g.fa", "g.fa.ann", "g.fa.bwt", "g.fa.pac", "g.fa.sa"] and os.path.isdir(fa + ".ann")
+    for x in (".bwt", ".sa", ".pac"):
+        assert open(fa + x, "rb").read() == old[x] and os.stat(fa + x).st_ino == ident[x], x
+    os.rmdir(fa + ".ann")
+    capi.ps_index(fa)                                    # the same text: the same four files, each a new file under the name
+    for x in old:
+        assert open(fa + x, "rb").read() == old[x], x
+    assert all(os.stat(fa + x).st_ino != ident[x] for x in ident)

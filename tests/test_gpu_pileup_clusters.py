@@ -276,3 +276,22 @@ def test_errors_write_nothing(hand):
     with pytest.raises(capi.PsError, match="reference"):
         capi.ps_pileup_clusters(unk, fa, os.path.join(d, "err_c.out"), None, 1, os.path.join(d, "err_c"))
     assert not [f for f in os.listdir(d) if f.startswith("err_") and not f.endswith(".sam")]
+
+
+def test_a_failure_on_the_fourth_file_leaves_none(hand):
+    """<out>.report is taken by a directory: the call fails after every count was taken, and none of the other five files is left"""
+    import capi
+    d, fa = hand
+    sam, out, sp = (os.path.join(d, n) for n in ("late.sam", "late.out", "late_sites"))
+    open(sam, "w").write(CASES["basic"][0])
+    os.mkdir(out + ".report")
+    with pytest.raises(capi.PsError, match="cannot rename"):
+        capi.ps_pileup_clusters(sam, fa, out, None, 1, sp)
+    assert sorted(f for f in os.listdir(d) if f.startswith("late")) == ["late.out.report", "late.sam"]
+    assert os.path.isdir(out + ".report") and os.listdir(out + ".report") == []
+    os.rmdir(out + ".report")
+    capi.ps_pileup_clusters(sam, fa, out, None, 1, sp)                      # and with the name free, all six, no temporary
+    assert sorted(f for f in os.listdir(d) if f.startswith("late")) == sorted(["late.sam"] + [os.path.basename(p) for p in _paths(out, sp).values()])
+    with pytest.raises(capi.PsError, match="would overwrite the input"):
+        capi.ps_pileup_clusters(sam, fa, sam, None, 1, sp)
+    assert open(sam).read() == CASES["basic"][0]

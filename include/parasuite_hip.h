@@ -85,7 +85,7 @@ int ps_map(int threads, const char *mm, const char *error_profile, const char *i
  * whose entries count in bytes.  A gapped hit whose CIGAR comes out of the banded alignment with more than 16 operations fails the
  * call (16 are what a ps_hit holds).
  * Not built: -q read trimming and -N (the oracle has neither); the shim refuses them.  ps_map_to_bam, ps_map_profiled and
- * ps_map_route keep the defaults: ps_route_opts has no size field to grow by. */
+ * ps_map_route keep the defaults; the route takes the options through ps_map_route_opts (ps_route_opts2.search). */
 typedef struct {
     uint32_t struct_size;          /* sizeof(ps_search_opts): a caller built against a shorter struct still works, the fields it lacks keep their defaults */
     int32_t max_gap_opens;         /* aln -o  [1]  */
@@ -294,6 +294,12 @@ int     ps_pileup_clusters(const char *mapping_sam_or_bam, const char *ref_fa, c
 typedef struct { uint64_t n_records, n_weak, n_kept, bam_bytes; } ps_extract_stats;
 int     ps_extract_weak_reads(const char *mapping_sam_or_bam, const char *out_bam, const char *out_fastq,
                               int mapq_threshold, int threads, ps_extract_stats *stats /* may be NULL */);
+/* The toolkit's `extractAligned -a MAPPING -o OUT` mode (Main.java:852-880), `ExtractNotMappedReads.extractReads`
+ * (src/src/utils/postprocessing/ExtractNotMappedReads.java:33-88): one line "@" + QNAME + "\n" per record of the SAM or BAM file, in
+ * file order, whatever the flags.  Host code; needs no GPU.  Written under <out_file>.names-tmp and renamed; an error leaves
+ * nothing behind, and an output that is the input is refused. */
+typedef struct { uint64_t n_records, out_bytes; } ps_names_stats;
+int     ps_extract_read_names(const char *mapping_sam_or_bam, const char *out_file, ps_names_stats *stats /* may be NULL */);
 /* Step 5 and the toolkit's `comb -g GENOMIC -t TRANSCRIPT -o OUT` mode (Main.java:438-488),
  * `new CombineGenomeTranscript().combine(genome, transcript, out)` (CombineGenomeTranscript.java:36-666): out_bam holds all
  * genomic records in file order, then the transcript hits lifted to genome coordinates in transcript-file order, under the
@@ -390,6 +396,50 @@ typedef struct {
     uint32_t n_index_loads_genome, n_index_loads_transcripts, n_fastq_parses, pad_;
 } ps_route_stats;
 int     ps_map_route(const ps_route_opts *opts, ps_route_stats *stats /* may be NULL */);
+/* The route with an options struct that can grow: everything ps_route_opts holds, and Main.java's --ref-refine and --unaligned and the
+ * search options.  struct_size as in ps_search_opts: a multiple of 4; a shorter struct keeps the defaults of the fields it lacks; a
+ * longer one is refused, and so is one that ends inside a pointer.  ps_map_route(o) is this call with ref_refine NULL,
+ * keep_unaligned 0 and search NULL: the same code, the same bytes.  <P> = out_prefix, Q = mapq_genomic, U = <P>.unaligned.fastq.
+ * ref_refine (--ref-refine, Main.java:219-225, :318): means something with refine only and is ignored without it (the Java assigns
+ *   it inside `if (isRefine)`).  The first pass maps against ref_fa; from then on everything uses ref_refine: the error profile of
+ *   the first-pass BAM is taken against it (:327-329; contigs matched by name, as ps_error_profile does, whose path on the written
+ *   file this is: it maps <ref_refine>.pac beside the index load), and the refine pass maps against it.  ps_index runs for it when its
+ *   .bwt is missing.  The transcript pass is unchanged.  NULL or "": ref_fa.  Each index is loaded once: n_index_loads_genome is 2
+ *   when the two references differ by realpath and 1 otherwise (1 also with a given error_profile: no pass maps against ref_fa
+ *   then, and only ref_refine is loaded).  A first-pass record on a contig ref_refine lacks fails the call at
+ *   step "profile", and nothing is left behind.
+ * keep_unaligned (--unaligned, :226-229, :354-357, :382-390, :405-407):
+ *   refine, no transcripts   the refine pass is written unfiltered (MAPQ 0) and sorted, then the extraction of :382-388 runs on the
+ *                            sorted file: U holds the records with MAPQ < Q in the sorted file's order, byte for byte what
+ *                            ps_extract_weak_reads writes from that file, and <P>.PARAsuite-genomic.bam the records it keeps, still
+ *                            sorted.  Deviation: the Java leaves the .bai it wrote before the rewrite, which no longer fits the
+ *                            file; here the .bai is written for the file as it ends up;
+ *   no refine, no transcripts  the first pass has already dropped MAPQ < Q (:284-291): U is created empty and the BAM is unchanged,
+ *                            as in the Java;
+ *   transcripts              as written, the second extraction (:382-388) runs on the already filtered BAM and overwrites U with
+ *                            nothing before the transcript pass reads it (:398), which then maps an empty file.  Deviation: the
+ *                            second extraction is not made; U of the first extraction (:299-302 or :371-374) is kept instead of
+ *                            removed (:405-407): what ps_extract_weak_reads writes there, in that file's (the input's) order.
+ *                            Every other file is what the call writes without the flag.
+ *   U is published like the route's other outputs and counts as an output where inputs and outputs are compared.
+ * search: the options of every mapping pass of the call (first, refine, transcript); NULL: the defaults.  Ranges and refusals are
+ *   those of ps_map_opts, checked before anything is touched (under the profile's ranges too when a profile pass will run); s_mm,
+ *   s_gapo and s_gape act on the stock-cost passes only.  "Issued one by one" above then reads ps_map_opts(.., search) +
+ *   ps_sam_to_bam where it says ps_map_to_bam.
+ * A resident scope treats this call as it treats ps_map_route. */
+typedef struct {
+    uint32_t struct_size;                            /* sizeof(ps_route_opts2) */
+    int32_t threads, refine, max_read_len, mapq_genomic, mapq_transcript;   /* as in ps_route_opts */
+    const char *reads_fq, *ref_fa, *out_prefix;
+    const char *transcripts_fa;
+    const char *bwa_mm, *parasuite_mm;
+    const char *error_profile, *indel_profile;
+    /* -- a struct_size up to here: ps_route_opts -- */
+    const char *ref_refine;                          /* --ref-refine; NULL or "": ref_fa */
+    const ps_search_opts *search;                    /* NULL: the defaults */
+    int32_t keep_unaligned, pad_;                    /* --unaligned */
+} ps_route_opts2;
+int     ps_map_route_opts(const ps_route_opts2 *opts, ps_route_stats *stats /* may be NULL */);
 
 /* ---- the resident scope: indexes and lanes of work stay in HBM between calls ---------------------------------------------------
  * Outside a scope every mapping call loads its index, allocates its search workspace and frees both before it returns.  Between

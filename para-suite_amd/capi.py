@@ -71,7 +71,7 @@ EXPORTS = ["ps_version", "ps_last_error", "ps_index", "ps_map", "ps_ctx_open", "
            "ps_ctx_blob", "ps_ctx_meta", "ps_ctx_from_blobs", "ps_ctx_clone", "ps_ctx_fetch", "ps_ctx_export_blob", "ps_ctx_sa_lookup", "ps_ctx_order_sort", "ps_ctx_index_check", "ps_sam_to_bam", "ps_map_to_bam", "ps_bam_view", "ps_bam_sort", "ps_bam_index", "ps_batch_from_fastq",
            "ps_batch_from_codes", "ps_batch_free", "ps_batch_n", "ps_batch_search", "ps_batch_select_hard",
            "ps_batch_select_easy", "ps_batch_locate", "ps_batch_run", "ps_batch_write_sam", "ps_batch_n_aln",
-           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route", "ps_benchmark_reads", "ps_simulate_reads", "ps_fetch_sequences",
+           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route", "ps_map_route_opts", "ps_extract_read_names", "ps_benchmark_reads", "ps_simulate_reads", "ps_fetch_sequences",
            "ps_resident_begin", "ps_resident_end", "ps_resident_info"]
 
 _LIB = None
@@ -611,6 +611,48 @@ def ps_map_route(reads_fq, ref_fa, out_prefix, transcripts_fa=None, threads=8, r
     st = RouteStats()
     _chk(L.ps_map_route(C.byref(o), C.byref(st)))
     return _struct_dict(st)
+
+
+class RouteOpts2(C.Structure):
+    """ps_route_opts2: ps_route_opts' fields behind a struct_size, then ref_refine, search and keep_unaligned"""
+    _fields_ = [("struct_size", C.c_uint32)] + \
+               [(k, C.c_int32) for k in ("threads", "refine", "max_read_len", "mapq_genomic", "mapq_transcript")] + \
+               [(k, C.c_char_p) for k in ("reads_fq", "ref_fa", "out_prefix", "transcripts_fa", "bwa_mm", "parasuite_mm",
+                                          "error_profile", "indel_profile", "ref_refine")] + \
+               [("search", C.POINTER(SearchOpts)), ("keep_unaligned", C.c_int32), ("pad_", C.c_int32)]
+
+
+ROUTE_OPTS_OLD_SIZE = RouteOpts2.ref_refine.offset          # a struct_size up to here holds what ps_route_opts holds
+
+
+def ps_map_route_opts(reads_fq, ref_fa, out_prefix, transcripts_fa=None, threads=8, refine=False, max_read_len=101, mapq_genomic=10,
+                      mapq_transcript=1, bwa_mm=None, parasuite_mm=None, error_profile=None, indel_profile=None, ref_refine=None,
+                      keep_unaligned=False, search=None, struct_size=None):
+    """ps_map_route with Main.java's --ref-refine and --unaligned and the search options of every pass (a SearchOpts, a dict of
+    its fields or None); struct_size: the size the struct claims (None: all of it)"""
+    enc = lambda v: str(v).encode() if v not in (None, "") else None
+    L = lib(); L.ps_map_route_opts.argtypes = [C.POINTER(RouteOpts2), C.POINTER(RouteStats)]
+    so = None if search is None else (search if isinstance(search, SearchOpts) else SearchOpts(**search))
+    o = RouteOpts2(C.sizeof(RouteOpts2) if struct_size is None else int(struct_size), int(threads), int(bool(refine)), int(max_read_len),
+                   int(mapq_genomic), int(mapq_transcript), enc(reads_fq), enc(ref_fa), enc(out_prefix), enc(transcripts_fa), enc(bwa_mm),
+                   enc(parasuite_mm), enc(error_profile), enc(indel_profile), enc(ref_refine),
+                   C.pointer(so) if so is not None else None, int(bool(keep_unaligned)), 0)
+    st = RouteStats()
+    _chk(L.ps_map_route_opts(C.byref(o), C.byref(st)))
+    return _struct_dict(st)
+
+
+class NamesStats(C.Structure):
+    _fields_ = [("n_records", C.c_uint64), ("out_bytes", C.c_uint64)]
+
+
+def ps_extract_read_names(mapping, out_file):
+    """ExtractNotMappedReads.extractReads, the `extractAligned` mode: "@" + QNAME per record of a SAM or BAM file, in file order
+    (host code, needs no GPU)"""
+    L = lib(); L.ps_extract_read_names.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(NamesStats)]
+    st = NamesStats()
+    _chk(L.ps_extract_read_names(mapping.encode(), out_file.encode(), C.byref(st)))
+    return {f: int(getattr(st, f)) for f, _ in NamesStats._fields_}
 
 
 class ResidentOpts(C.Structure):

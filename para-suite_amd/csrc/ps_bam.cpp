@@ -775,4 +775,20 @@ void extract_weak_reads(const char *path, const char *out_bam, const char *out_f
     if (stats) { stats->n_records = n_records; stats->n_weak = n_weak; stats->n_kept = bs.n_out; stats->bam_bytes = bs.bam_bytes; }
 }
 
+// ExtractNotMappedReads.java:33-88: "@" + QNAME, one line per record, in file order, whatever the flags
+void extract_read_names(const char *path, const char *out_file, int threads, NamesStats *stats)
+{
+    threads = clamp_threads(threads);
+    if (!path || !path[0] || !out_file || !out_file[0]) throw Error("ps_extract_read_names: mapping file and output file are required");
+    OutFiles files(".names-tmp"); const std::string t = files.add(out_file);
+    files.refuse_inputs({path}, "ps_extract_read_names: ", " may not be the input file ");
+    Data d;
+    load_any(path, threads, d);
+    std::string text;
+    for (const Rec &r : d.recs) { text.push_back('@'); text.append(rec_name(d, r)); text.push_back('\n'); }
+    write_text_file(t, text);
+    files.publish_all(); files.keep();
+    if (stats) { stats->n_records = d.recs.size(); stats->out_bytes = text.size(); }
+}
+
 }  // namespace ps

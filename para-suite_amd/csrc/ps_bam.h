@@ -80,4 +80,7 @@ struct ExtractStats { uint64_t n_records = 0, n_weak = 0, n_kept = 0, bam_bytes 
 // ExtractWeakMappingReads.extractReads: records with MAPQ < mapq_threshold -> four FASTQ lines each (read orientation restored),
 // the others -> out_bam with the input's header
 void extract_weak_reads(const char *sam_or_bam, const char *out_bam, const char *out_fastq, int mapq_threshold, int threads, ExtractStats *stats);
+struct NamesStats { uint64_t n_records = 0, out_bytes = 0; };
+// ExtractNotMappedReads.extractReads: "@" + QNAME + "\n" per record, in file order
+void extract_read_names(const char *sam_or_bam, const char *out_file, int threads, NamesStats *stats);
 }

@@ -393,6 +393,7 @@ int ps_map_to_bam(int threads, const char *mm, const char *error_profile, const 
     PS_CATCH_INT
 }
 int ps_map_route(const ps_route_opts *o, ps_route_stats *stats_out) { PS_TRY map_route(o, stats_out); return 0; PS_CATCH_INT }
+int ps_map_route_opts(const ps_route_opts2 *o, ps_route_stats *stats_out) { PS_TRY map_route_opts(o, stats_out); return 0; PS_CATCH_INT }
 
 // The resident scope: between begin and end the five mapping calls above keep their indexes and lanes of work in HBM (ps_map.hip).
 int ps_resident_begin(const ps_resident_opts *o) { PS_TRY resident_begin(o); return 0; PS_CATCH_INT }
@@ -467,6 +468,17 @@ int ps_extract_weak_reads(const char *mapping_sam_or_bam, const char *out_bam, c
         ExtractStats s;
         extract_weak_reads(mapping_sam_or_bam, out_bam, out_fastq, mapq_threshold, threads, &s);
         if (stats) { stats->n_records = s.n_records; stats->n_weak = s.n_weak; stats->n_kept = s.n_kept; stats->bam_bytes = s.bam_bytes; }
+        return 0;
+    PS_CATCH_INT
+}
+
+// The `extractAligned` mode (Main.java:852-880): ExtractNotMappedReads.extractReads.  Host code.
+int ps_extract_read_names(const char *mapping_sam_or_bam, const char *out_file, ps_names_stats *stats)
+{
+    PS_TRY
+        NamesStats s;
+        extract_read_names(mapping_sam_or_bam, out_file, 4, &s);
+        if (stats) { stats->n_records = s.n_records; stats->out_bytes = s.out_bytes; }
         return 0;
     PS_CATCH_INT
 }

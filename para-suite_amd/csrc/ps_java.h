@@ -70,6 +70,47 @@ PS_JAVA_HD bool java_parse_int(const uint8_t *s, uint32_t n, int32_t &v)
     return true;
 }
 
+inline bool java_parse_int(const std::string &s, int32_t &v) { return java_parse_int((const uint8_t *)s.data(), (uint32_t)s.size(), v); }
+
+// Boolean.parseBoolean: "true" in any letter case; everything else, the empty string included, is false
+inline bool java_parse_boolean(const std::string &s)
+{
+    static const char t[] = "true";
+    if (s.size() != 4) return false;
+    for (int i = 0; i < 4; ++i) if ((s[i] | 0x20) != t[i]) return false;
+    return true;
+}
+
+// Double.parseDouble on its decimal forms: white space at either end trimmed (String.trim: everything up to ' '), one optional sign,
+// "NaN", "Infinity", or digits with an optional point and exponent, one optional suffix d D f F.  Hexadecimal floating-point
+// literals, which the Java also reads, are refused
+inline bool java_parse_double(const std::string &text, double &v)
+{
+    size_t a = 0, b = text.size();
+    while (a < b && (unsigned char)text[a] <= ' ') ++a;
+    while (b > a && (unsigned char)text[b - 1] <= ' ') --b;
+    std::string s = text.substr(a, b - a);
+    if (s.empty()) return false;
+    size_t i = s[0] == '-' || s[0] == '+' ? 1 : 0;
+    const bool neg = s[0] == '-';
+    const std::string body = s.substr(i);
+    if (body == "NaN") { v = std::nan(""); return true; }
+    if (body == "Infinity") { v = neg ? -INFINITY : INFINITY; return true; }
+    if (body.size() > 1 && (body.back() == 'd' || body.back() == 'D' || body.back() == 'f' || body.back() == 'F')) s.pop_back();
+    bool digit = false;
+    for (size_t k = i; k < s.size(); ++k) {
+        const char c = s[k];
+        if (c >= '0' && c <= '9') digit = true;
+        else if (c != '.' && c != 'e' && c != 'E' && c != '+' && c != '-') return false;
+    }
+    if (!digit) return false;
+    char *end = nullptr;
+    const double x = std::strtod(s.c_str(), &end);
+    if (end != s.c_str() + s.size()) return false;
+    v = x;
+    return true;
+}
+
 // String.split(sep): trailing empty strings are dropped, an empty input is one empty string
 inline std::vector<std::string> java_split(const std::string &s, char sep)
 {

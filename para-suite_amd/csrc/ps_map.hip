@@ -20,6 +20,7 @@
 #include <functional>
 #include <map>
 #include <mutex>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -31,6 +32,8 @@
 #include "ps_map.h"
 #include "ps_map_plan.h"
 #include "ps_resident.h"
+#include "ps_search_opts.h"
+#include "ps_dev.h"
 
 namespace ps {
 namespace {
@@ -555,7 +558,9 @@ size_t readset_bytes(const ReadSet &rs)
 }
 // ExtractWeakMappingReads on a located piece: the reads whose record has MAPQ < threshold, as a second parse of their FASTQ text would return
 // them (the read as it was sequenced is what the ReadSet holds; the parser takes one more trailing /1 or /2 off the name)
-void gather_weak(const Batch &b, int threshold, ReadSet &w, uint64_t &n_weak)
+// fq (--unaligned): also the four FASTQ lines ps_extract_weak_reads writes for the record -- its name as the record carries it, the bases as
+// BAM's nibbles give them back (A C G T N), the read as it was sequenced
+void gather_weak(const Batch &b, int threshold, ReadSet &w, uint64_t &n_weak, std::string *fq)
 {
     const ReadSet &rs = b.rs;
     if (w.off.empty()) { w.off.push_back(0); w.name_off.push_back(0); }
@@ -565,6 +570,12 @@ void gather_weak(const Batch &b, int threshold, ReadSet &w, uint64_t &n_weak)
         size_t nl; const char *nm = rs.name(g, nl);
         if (rs.len[g] == 0) throw Error("extract: record " + std::string(nm, nl) + " has MAPQ below " + std::to_string(threshold) + " and no SEQ ('*'): it cannot be mapped again");
         if (!rs.has_qual) throw Error("extract: record " + std::string(nm, nl) + " has MAPQ below " + std::to_string(threshold) + " and no QUAL ('*'): it cannot be written as FASTQ");
+        if (fq) {
+            const int64_t l = rs.off[g + 1] - rs.off[g];
+            fq->push_back('@'); fq->append(nm, nl); fq->push_back('\n');
+            for (int64_t i = 0; i < l; ++i) { const uint8_t c = rs.seq[(size_t)(rs.off[g] + i)]; fq->push_back("ACGTN"[c < 4 ? c : 4]); }
+            fq->append("\n+\n"); fq->append(rs.qual.data() + rs.off[g], (size_t)l); fq->push_back('\n');
+        }
         if (nl > 2 && nm[nl - 2] == '/' && (nm[nl - 1] == '1' || nm[nl - 1] == '2')) nl -= 2;
         w.names.insert(w.names.end(), nm, nm + nl); w.name_off.push_back((int64_t)w.names.size());
         w.seq.insert(w.seq.end(), rs.seq.data() + rs.off[g], rs.seq.data() + rs.off[g + 1]);
@@ -578,18 +589,20 @@ bool has(const char *s) { return s && s[0]; }
 
 // the call's state between its passes, and one pass of it
 struct Route {
-    const ps_route_opts &o; const int threads, gm; int bam_level = 1;
-    OutFiles &files; CtxSet genome, transcripts;    // the call's outputs (published step by step); its own contexts: open from pass to pass, closed when it returns
-    ResidentUse use; Residents::Entry *eg = nullptr, *et = nullptr; int g_loads0 = 0, t_loads0 = 0;    // inside a resident scope: the scope's entries instead, which stay
+    const ps_route_opts2 &o; const int threads, gm; int bam_level = 1;
+    const char *const ref_genome, *const ref_refine;     // the reference of the genomic passes; that of the refine pass where it is another one (by realpath), else null
+    OutFiles &files; CtxSet genome, genome_refine, transcripts;    // the call's outputs (published step by step); its own contexts: open from pass to pass, closed when it returns
+    ResidentUse use; Residents::Entry *ent[3] = {nullptr, nullptr, nullptr}; int loads0[3] = {0, 0, 0};    // inside a resident scope: the scope's entries instead, which stay
     std::vector<ReadSet> kept, weak; size_t kept_bytes = 0, keep_bound = (size_t)8192 << 20; bool kept_all = true;
-    uint64_t n_weak = 0;
+    uint64_t n_weak = 0; std::string weak_fq;       // weak_fq: <P>.unaligned.fastq of a transcript route with keep_unaligned
     BamFile G, T;
-    Route(const ps_route_opts &opts, int thr, int mapq_genomic, OutFiles &outs) : o(opts), threads(thr), gm(mapq_genomic), files(outs)
+    enum Ref { kGenome = 0, kRefine = 1, kTranscripts = 2 };
+    Route(const ps_route_opts2 &opts, const char *rg, const char *rr, int thr, int mapq_genomic, OutFiles &outs) : o(opts), threads(thr), gm(mapq_genomic), ref_genome(rg), ref_refine(rr), files(outs)
     {
         if (const char *e = std::getenv("PS_ROUTE_KEEP_MB")) keep_bound = (size_t)std::max(0, std::atoi(e)) << 20;
         if (const char *e = std::getenv("PS_BAM_LEVEL")) bam_level = std::atoi(e);
     }
-    void weak_of(Batch &b) { weak.emplace_back(); gather_weak(b, gm, weak.back(), n_weak); }
+    void weak_of(Batch &b) { weak.emplace_back(); gather_weak(b, gm, weak.back(), n_weak, o.keep_unaligned ? &weak_fq : nullptr); }
     void keep(Batch &b)                    // the parsed piece stays for the profile pass, within the bound
     {
         if (!kept_all) return;
@@ -599,76 +612,113 @@ struct Route {
     }
     // one pass: a sorted BAM (+ index, or by name) under its temporary name, published when the pass is done.  job: the input source,
     // the contexts and the outputs that follow the records
-    void pass(MapJob &job, const char *mm, const char *ep, const char *ip, const char *ref, const std::string &out, int min_mapq, bool by_name, BamFile *keep_recs, ps_bam_stats &bs_out)
+    void pass(MapJob &job, const char *mm, const char *ep, const char *ip, const char *ref, const std::string &out, int min_mapq, bool by_name, BamFile *keep_recs, ps_bam_stats &bs_out,
+              bool publish = true)
     {
         BamStats bs; BamOut bo; bo.min_mapq = min_mapq; bo.sort = !by_name; bo.index = !by_name; bo.by_name = by_name; bo.keep = keep_recs; bo.stats = &bs; bo.level = bam_level;
         const std::string t = files.tmp(out);
-        job.a = MapArgs{threads, mm, ep, ip, ref, o.reads_fq}; job.bam_out = true;
+        job.a = MapArgs{threads, mm, ep, ip, ref, o.reads_fq, o.search}; job.bam_out = true;
         job.outs.emplace(job.outs.begin(), new BamRecords(bo, t.c_str(), threads, job.s_write));
         Pass(job).run();
-        files.publish(out); if (!by_name) files.publish(out + ".bai");
+        if (publish) { files.publish(out); if (!by_name) files.publish(out + ".bai"); }
         bs_out.n_in = bs.n_in; bs_out.n_out = bs.n_out; bs_out.bam_bytes = bs.bam_bytes;
     }
-    // the contexts of a pass; the transcript pass takes over the lanes of work of the genome passes
-    void lend(MapJob &job, bool to_transcripts)
+    // the contexts of a pass; a later reference takes over the lanes of work of the passes before it
+    const char *path_of(Ref w) const { return w == kTranscripts ? o.transcripts_fa : w == kRefine ? ref_refine : ref_genome; }
+    CtxSet &own_set(Ref w) { return w == kTranscripts ? transcripts : w == kRefine ? genome_refine : genome; }
+    void lend(MapJob &job, Ref w)
     {
-        if (!use.on) { job.resident = to_transcripts ? &transcripts : &genome; if (to_transcripts) job.lanes_from = {&genome}; return; }
-        Residents::Entry *&e = to_transcripts ? et : eg;
-        if (!e) { e = use.entry(to_transcripts ? o.transcripts_fa : o.ref_fa); (to_transcripts ? t_loads0 : g_loads0) = e->payload.n_index_loads; }
-        use.lend(e, job);
+        if (w == kRefine && !ref_refine) w = kGenome;
+        if (!use.on) {
+            job.resident = &own_set(w);
+            if (w == kRefine) job.lanes_from = {&genome}; else if (w == kTranscripts) job.lanes_from = {&genome, &genome_refine};
+            return;
+        }
+        if (!ent[w]) { ent[w] = use.entry(path_of(w)); loads0[w] = ent[w]->payload.n_index_loads; }
+        use.lend(ent[w], job);
     }
-    const CtxSet &genome_set() const { return eg ? eg->payload : genome; }
-    const CtxSet &transcript_set() const { return et ? et->payload : transcripts; }
-    void close() { transcripts.xs.clear(); genome.xs.clear(); }
+    const CtxSet &set_of(Ref w) const { return ent[w] ? ent[w]->payload : const_cast<Route *>(this)->own_set(w); }
+    int loads_of(Ref w) const { return set_of(w).n_index_loads - loads0[w]; }
+    void close() { transcripts.xs.clear(); genome_refine.xs.clear(); genome.xs.clear(); }
 };
+
+// the caller's struct as this library's (ps_search_opts' rules): the fields behind struct_size keep their defaults, all zero here
+void route_opts_read(const ps_route_opts2 *in, ps_route_opts2 &o)
+{
+    std::memset(&o, 0, sizeof o);
+    if (!in) throw Error("ps_map_route_opts: no options");
+    const size_t sz = in->struct_size, p0 = offsetof(ps_route_opts2, reads_fq), p1 = offsetof(ps_route_opts2, keep_unaligned);
+    if (sz < sizeof(uint32_t) || sz % sizeof(int32_t) != 0 || sz > sizeof o || (sz > p0 && sz < p1 && (sz - p0) % sizeof(void *) != 0))
+        throw Error("ps_map_route_opts: struct_size " + std::to_string(sz) + " must be a multiple of 4 from 4 to " + std::to_string(sizeof o) + " that does not end inside a pointer");
+    std::memcpy(&o, in, sz);
+    o.struct_size = (uint32_t)sizeof o;
 }
 
-void map_route(const ps_route_opts *o, ps_route_stats *stats_out)
+void route_run(const ps_route_opts2 &o, const std::string &who, ps_route_stats *stats_out)
 {
-    if (!o) throw Error("ps_map_route: no options");
-    if (!has(o->reads_fq)) throw Error("ps_map_route: the reads file (-q) is required");
-    if (!has(o->ref_fa)) throw Error("ps_map_route: the reference (-r) is required");
-    if (!has(o->out_prefix)) throw Error("ps_map_route: the output prefix (-o) is required");
-    const bool refine = o->refine != 0, with_t = has(o->transcripts_fa), given = has(o->error_profile);
-    if (given && !refine) throw Error("ps_map_route: an error profile without refine: nothing to map");
-    if (has(o->indel_profile) && !given) throw Error("ps_map_route: an indel profile without an error profile");
-    const int threads = o->threads > 0 ? o->threads : 1, max_len = o->max_read_len > 0 ? o->max_read_len : 101;
-    const int gm = o->mapq_genomic > 0 ? o->mapq_genomic : 10, tm = o->mapq_transcript > 0 ? o->mapq_transcript : 1;
-    const char *bwa_mm = has(o->bwa_mm) ? o->bwa_mm : "2", *para_mm = has(o->parasuite_mm) ? o->parasuite_mm : "-1";
-    if (max_len > 4096) throw Error("ps_map_route: maximum read length out of range");
-    const std::string P = o->out_prefix;
+    if (!has(o.reads_fq)) throw Error(who + "the reads file (-q) is required");
+    if (!has(o.ref_fa)) throw Error(who + "the reference (-r) is required");
+    if (!has(o.out_prefix)) throw Error(who + "the output prefix (-o) is required");
+    const bool refine = o.refine != 0, with_t = has(o.transcripts_fa), given = has(o.error_profile), keep_un = o.keep_unaligned != 0;
+    if (given && !refine) throw Error(who + "an error profile without refine: nothing to map");
+    if (has(o.indel_profile) && !given) throw Error(who + "an indel profile without an error profile");
+    const int threads = o.threads > 0 ? o.threads : 1, max_len = o.max_read_len > 0 ? o.max_read_len : 101;
+    const int gm = o.mapq_genomic > 0 ? o.mapq_genomic : 10, tm = o.mapq_transcript > 0 ? o.mapq_transcript : 1;
+    const char *bwa_mm = has(o.bwa_mm) ? o.bwa_mm : "2", *para_mm = has(o.parasuite_mm) ? o.parasuite_mm : "-1";
+    if (max_len > 4096) throw Error(who + "maximum read length out of range");
     const bool first_pass = !given;
+    if (o.search) {                        // a stock pass runs iff there is a first pass, a profile pass iff refine
+        std::string err;
+        if ((first_pass && !search_opts_check(o.search, false, err)) || (refine && !search_opts_check(o.search, true, err))) throw Error(who + err);
+    }
+    // --ref-refine (Main.java:318): without refine it is never read.  With a given profile no pass maps against ref_fa at all
+    const bool other_ref = refine && has(o.ref_refine) && resident_path(o.ref_refine) != resident_path(o.ref_fa);
+    const char *const ref_genome = other_ref && !first_pass ? o.ref_refine : o.ref_fa;
+    const char *const ref_refine = other_ref && first_pass ? o.ref_refine : nullptr;
+    const char *const ref_last = ref_refine ? ref_refine : ref_genome;     // what the refine pass maps against
+    const std::string P = o.out_prefix;
     const std::string f_bwa = P + ".BWA-genomic.bam", f_para = P + ".PARAsuite-genomic.bam", f_comb = P + ".combined.bam";
     const std::string f_tr = P + (refine ? ".PARAsuite-transcript.bam" : ".BWA-transcript.bam");
-    const std::string f_ep = f_bwa + ".errorprofile", f_ip = f_bwa + ".indelprofile";
+    const std::string f_ep = f_bwa + ".errorprofile", f_ip = f_bwa + ".indelprofile", f_un = P + ".unaligned.fastq";
     OutFiles files(".route-tmp");          // every output of the steps this call will run; ProfileOut writes <prefix>.errorprofile and .indelprofile
     const std::string profile_tmp = f_bwa + ".profile.route-tmp";
     if (first_pass) add_bam(files, f_bwa, true);
     if (first_pass && refine) { files.add(f_ep, profile_tmp + ".errorprofile"); files.add(f_ip, profile_tmp + ".indelprofile"); }
     if (refine) add_bam(files, f_para, true);
     if (with_t) { add_bam(files, f_tr, false); add_bam(files, f_comb, true); }
-    files.refuse_inputs({o->reads_fq, o->ref_fa, o->transcripts_fa, o->error_profile, o->indel_profile}, "ps_map_route: ");
-    { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error("ps_map_route: no HIP device available: parasuite-hip has no CPU path"); }
+    if (keep_un) files.add(f_un);
+    files.refuse_inputs({o.reads_fq, o.ref_fa, refine ? o.ref_refine : nullptr, o.transcripts_fa, o.error_profile, o.indel_profile}, who);
+    { int n = 0; if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(who + "no HIP device available: parasuite-hip has no CPU path"); }
 
     const auto t_begin = clk::now();
     ps_route_stats st; std::memset(&st, 0, sizeof st);
-    Route r(*o, threads, gm, files);
+    Route r(o, ref_genome, ref_refine, threads, gm, files);
     std::string step = "first pass";
     try {
         const bool weak_after_first = with_t && !refine;
-        std::string ep = given ? o->error_profile : "", ip = has(o->indel_profile) ? o->indel_profile : "";
+        std::string ep = given ? o.error_profile : "", ip = has(o.indel_profile) ? o.indel_profile : "";
         if (first_pass) {
             const auto t0 = clk::now();
-            MapJob job; r.lend(job, false);
-            if (refine) job.outs.emplace_back(new ProfileOut(gm, max_len, profile_tmp, threads, job.s_profile));
+            MapJob job; r.lend(job, Route::kGenome);
+            if (refine && !ref_refine) job.outs.emplace_back(new ProfileOut(gm, max_len, profile_tmp, threads, job.s_profile));
             if (weak_after_first) job.outs.emplace_back(new PieceFn([&r](Batch &b) { r.weak_of(b); }));
             else if (refine) job.outs.emplace_back(new PieceFn([&r](Batch &b) { r.keep(b); }));
-            r.pass(job, bwa_mm, nullptr, nullptr, o->ref_fa, f_bwa, gm, false, weak_after_first ? &r.G : nullptr, st.first);
+            r.pass(job, bwa_mm, nullptr, nullptr, ref_genome, f_bwa, gm, false, weak_after_first ? &r.G : nullptr, st.first);
             st.n_reads = (uint64_t)job.n_reads; st.s_parse = job.s_parse; st.s_index_genome = job.s_index; st.n_fastq_parses = 1;
             st.s_first = secs_since(t0);
             if (refine) {
                 step = "profile";
                 const auto t1 = clk::now();
+                if (ref_refine) {          // the profile of the written file against the other reference, contigs by name: ps_error_profile's path
+                    const int dev = r.set_of(Route::kGenome).xs[0]->device;
+                    if (!index_files_exist(ref_refine)) {
+                        require_device(dev);
+                        StreamGuard sg; Index tmp; index_build(ref_refine, tmp, sg.s); index_save(tmp, ref_refine);
+                    }
+                    ProfileCounts pc;
+                    error_profile_count(f_bwa.c_str(), ref_refine, max_len, dev, threads, pc, 0, nullptr);
+                    error_profile_write(pc, profile_tmp);
+                }
                 files.publish(f_ep); files.publish(f_ip);
                 ep = f_ep; ip = f_ip;
                 st.s_profile = secs_since(t1);
@@ -677,37 +727,50 @@ void map_route(const ps_route_opts *o, ps_route_stats *stats_out)
         if (refine) {
             step = "refine pass";
             const auto t0 = clk::now();
-            MapJob job; r.lend(job, false);
+            MapJob job; r.lend(job, Route::kRefine);
             if (first_pass && r.kept_all) job.reads = &r.kept; else ++st.n_fastq_parses;
             if (with_t) job.outs.emplace_back(new PieceFn([&r](Batch &b) { r.weak_of(b); }));
-            r.pass(job, para_mm, ep.c_str(), ip.empty() ? nullptr : ip.c_str(), o->ref_fa, f_para, gm, false, with_t ? &r.G : nullptr, st.refine);
+            const bool extract_sorted = keep_un && !with_t;      // Main.java:354-357, :382-388
+            r.pass(job, para_mm, ep.c_str(), ip.empty() ? nullptr : ip.c_str(), ref_last, f_para, extract_sorted ? 0 : gm, false, with_t ? &r.G : nullptr, st.refine, !extract_sorted);
             if (!first_pass) { st.n_reads = (uint64_t)job.n_reads; st.s_parse = job.s_parse; st.s_index_genome = job.s_index; }
+            if (extract_sorted) {          // the sorted, unfiltered file under its temporary name -> the records it keeps + U, then the index of the file as it ends up
+                const std::string t = files.tmp(f_para), t_kept = t + ".kept";
+                ExtractStats es;
+                extract_weak_reads(t.c_str(), t_kept.c_str(), files.tmp(f_un).c_str(), gm, threads, &es);
+                if (std::rename(t_kept.c_str(), t.c_str()) != 0) { ::unlink(t_kept.c_str()); throw Error("cannot rename " + t_kept + " to " + t); }
+                bam_index(t.c_str(), threads);
+                files.publish(f_para); files.publish(f_para + ".bai"); files.publish(f_un);
+                st.refine.n_out = es.n_kept; st.refine.bam_bytes = es.bam_bytes;
+                st.extract.n_records = es.n_records; st.extract.n_weak = es.n_weak; st.extract.n_kept = es.n_kept;
+            }
             st.s_refine = secs_since(t0);
         }
         r.kept.clear();
+        if (keep_un && with_t) { write_text_file(files.tmp(f_un), r.weak_fq); files.publish(f_un); r.weak_fq = std::string(); }    // the first extraction's, kept (:405-407)
+        if (keep_un && !with_t && !refine) { write_text_file(files.tmp(f_un), ""); files.publish(f_un); }     // the first pass has dropped MAPQ < Q already: empty, as in the Java
         if (with_t) {
             step = "transcript pass";
             const auto t0 = clk::now();
             st.extract.n_records = st.n_reads; st.extract.n_weak = r.n_weak; st.extract.n_kept = st.n_reads - r.n_weak;
-            MapJob job; r.lend(job, true); job.reads = &r.weak;
-            r.pass(job, refine ? para_mm : bwa_mm, refine ? ep.c_str() : nullptr, refine && !ip.empty() ? ip.c_str() : nullptr, o->transcripts_fa, f_tr, tm, true, &r.T, st.transcript);
+            MapJob job; r.lend(job, Route::kTranscripts); job.reads = &r.weak;
+            r.pass(job, refine ? para_mm : bwa_mm, refine ? ep.c_str() : nullptr, refine && !ip.empty() ? ip.c_str() : nullptr, o.transcripts_fa, f_tr, tm, true, &r.T, st.transcript);
             st.s_index_transcripts = job.s_index; st.s_transcript = secs_since(t0);
             step = "combine";
             const auto t1 = clk::now();
-            const int dev = r.genome_set().xs[0]->device;                    // the first device of the passes
+            const int dev = r.set_of(refine && ref_refine ? Route::kRefine : Route::kGenome).xs[0]->device;      // the first device of the passes
             combine_records(r.G, r.T, f_tr.c_str(), files.tmp(f_comb).c_str(), true, true, threads, dev, &st.combine);
             files.publish(f_comb); files.publish(f_comb + ".bai");
             st.s_combine = secs_since(t1);
         }
         step = "closing";
-        st.n_index_loads_genome = (uint32_t)(r.genome_set().n_index_loads - r.g_loads0); st.n_index_loads_transcripts = (uint32_t)(r.transcript_set().n_index_loads - r.t_loads0);
+        st.n_index_loads_genome = (uint32_t)(r.loads_of(Route::kGenome) + r.loads_of(Route::kRefine)); st.n_index_loads_transcripts = (uint32_t)r.loads_of(Route::kTranscripts);
         r.close();
         r.use.done();
         files.keep();
     } catch (const std::exception &e) {
         const std::string m = e.what();
         r.close();
-        throw Error("ps_map_route: " + step + ": " + m);      // what the call wrote goes with `files`
+        throw Error(who + step + ": " + m);      // what the call wrote goes with `files`
     }
     st.s_total = secs_since(t_begin);
     if (stats_out) *stats_out = st;
@@ -717,5 +780,24 @@ void map_route(const ps_route_opts *o, ps_route_stats *stats_out)
                      (unsigned long long)st.n_reads, st.s_total, st.s_parse, st.n_fastq_parses, st.s_index_genome, st.n_index_loads_genome, st.s_first, st.s_profile, st.s_refine,
                      (unsigned long long)st.extract.n_weak, st.s_index_transcripts, st.n_index_loads_transcripts, st.s_transcript, st.s_combine);
 }
+}
+
+void map_route(const ps_route_opts *in, ps_route_stats *stats_out)
+{
+    if (!in) throw Error("ps_map_route: no options");
+    ps_route_opts2 o; std::memset(&o, 0, sizeof o);          // ref_refine NULL, keep_unaligned 0, search NULL
+    o.struct_size = (uint32_t)sizeof o;
+    o.reads_fq = in->reads_fq; o.ref_fa = in->ref_fa; o.out_prefix = in->out_prefix; o.transcripts_fa = in->transcripts_fa;
+    o.bwa_mm = in->bwa_mm; o.parasuite_mm = in->parasuite_mm; o.error_profile = in->error_profile; o.indel_profile = in->indel_profile;
+    o.threads = in->threads; o.refine = in->refine; o.max_read_len = in->max_read_len; o.mapq_genomic = in->mapq_genomic; o.mapq_transcript = in->mapq_transcript;
+    route_run(o, "ps_map_route: ", stats_out);
+}
+void map_route_opts(const ps_route_opts2 *in, ps_route_stats *stats_out)
+{
+    ps_route_opts2 o;
+    route_opts_read(in, o);
+    route_run(o, "ps_map_route_opts: ", stats_out);
+}
 
 }  // namespace ps
+

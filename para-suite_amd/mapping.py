@@ -199,6 +199,18 @@ class ExtractWeakMappingReads:
             raise ExternalCallErrorException("ExtractWeakMappingReads %s: %s" % (mappingFileName, e))
 
 
+class ExtractNotMappedReads:
+    """mirror of utils.postprocessing.ExtractNotMappedReads (ExtractNotMappedReads.java:33-88), the `extractAligned` mode:
+    `new ExtractNotMappedReads().extractReads(mappingFileName, alignedReadFileName)` writes "@" + read name for every record of
+    the mapping, in file order (`ps_extract_read_names`, host code).  Returns the stats dict."""
+
+    def extractReads(self, mappingFileName, alignedReadFileName):
+        try:
+            return capi.ps_extract_read_names(mappingFileName, alignedReadFileName)
+        except capi.PsError as e:
+            raise ExternalCallErrorException("ExtractNotMappedReads %s: %s" % (mappingFileName, e))
+
+
 class CombineGenomeTranscript:
     """mirror of utils.postprocessing.CombineGenomeTranscript (CombineGenomeTranscript.java:36-666), step 5 of `map -t` and the
     `comb` mode (Main.java:400-404, 438-488): `new CombineGenomeTranscript().combine(genomeMappingFileName,
@@ -244,13 +256,19 @@ class Main:
 
     def map(self, readFileName, referenceFileName, outputPrefix, transcriptFileName=None, threads=1, maxReadLength=101,
             mappingQualityFilterGenomic=10, mappingQualityFilterTranscript=1, refine=False, bwaMismatches="2",
-            parasuiteMismatches="-1", profileFileName=None, indelFileName=None):
+            parasuiteMismatches="-1", profileFileName=None, indelFileName=None, keepUnaligned=False, referenceRefineFileName=None,
+            search=None):
+        """keepUnaligned (--unaligned), referenceRefineFileName (--ref-refine) and search (a capi.SearchOpts or a dict of its
+        fields, for every pass) go through `ps_map_route_opts`; without them the call is `ps_map_route`"""
+        kw = dict(transcripts_fa=transcriptFileName, threads=threads, refine=refine, max_read_len=maxReadLength,
+                  mapq_genomic=mappingQualityFilterGenomic, mapq_transcript=mappingQualityFilterTranscript,
+                  bwa_mm=bwaMismatches, parasuite_mm=parasuiteMismatches, error_profile=profileFileName, indel_profile=indelFileName)
         try:
-            self.stats = capi.ps_map_route(readFileName, referenceFileName, outputPrefix, transcripts_fa=transcriptFileName,
-                                           threads=threads, refine=refine, max_read_len=maxReadLength,
-                                           mapq_genomic=mappingQualityFilterGenomic, mapq_transcript=mappingQualityFilterTranscript,
-                                           bwa_mm=bwaMismatches, parasuite_mm=parasuiteMismatches, error_profile=profileFileName,
-                                           indel_profile=indelFileName)
+            if keepUnaligned or referenceRefineFileName or search is not None:
+                self.stats = capi.ps_map_route_opts(readFileName, referenceFileName, outputPrefix, keep_unaligned=keepUnaligned,
+                                                    ref_refine=referenceRefineFileName, search=search, **kw)
+            else:
+                self.stats = capi.ps_map_route(readFileName, referenceFileName, outputPrefix, **kw)
         except capi.PsError as e:
             raise ExternalCallErrorException("map -q %s -r %s -o %s: %s" % (readFileName, referenceFileName, outputPrefix, e))
         return self.mappingFileName(outputPrefix, transcriptFileName, refine)

@@ -2,6 +2,9 @@
 
 The library is the product; this module only marshals arguments.  If the
 shared object is missing the import fails loudly -- there is no fallback.
+
+The ABI is declared once: the mirrors of the header's structs (STRUCTS, in the header's order) and the signature of every
+function (SIGNATURES), which lib() applies when it loads the library.  tests/test_capi_cpu.py holds both against the header.
 """
 import ctypes as C
 import os
@@ -12,33 +15,18 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 SO_PATH = os.environ.get("PARASUITE_LIB") or os.path.join(_HERE, "libparasuite_hip.so")   # PARASUITE_LIB: a diagnostic build of the same library
 
 
-class IndexInfo(C.Structure):
-    _fields_ = [("seq_len", C.c_uint64), ("l_pac", C.c_uint64), ("primary", C.c_uint64), ("L2", C.c_uint64 * 5),
-                ("n_blocks", C.c_uint64), ("n_sa", C.c_uint64), ("device_bytes", C.c_uint64),
-                ("n_contigs", C.c_int32), ("n_holes", C.c_int32), ("sa_rounds", C.c_int32), ("sa_intv", C.c_int32),
-                ("build_ms", C.c_double), ("jump_levels", C.c_int32), ("pad_", C.c_int32)]
+def _fields(ctype, *names):
+    return [(k, ctype) for k in names]
 
 
-class Timing(C.Structure):
-    _fields_ = [("ms_width", C.c_double), ("ms_backtrack", C.c_double), ("ms_compact", C.c_double),
-                ("ms_select", C.c_double), ("ms_sa2pos", C.c_double), ("ms_refine", C.c_double),
-                ("ms_host_post", C.c_double), ("ms_total", C.c_double), ("n_width_launches", C.c_int32),
-                ("n_backtrack_launches", C.c_int32), ("n_overflow_tier1", C.c_int64), ("n_overflow_tier2", C.c_int64),
-                ("ms_classify", C.c_double), ("ms_rows", C.c_double), ("ms_sel_hard", C.c_double), ("ms_sel_easy", C.c_double),
-                ("bt_begin_ms", C.c_double), ("bt_end_ms", C.c_double)]
-
-
-class KStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("occ_pairs", "occ_same_blk", "nodes", "pushes", "pops", "lf_steps", "iters",
-                                          "exact_steps")]
-
+# ---- the structs of the header, in its order ----
 
 class SearchOpts(C.Structure):
     """ps_search_opts: the search options of `bwa aln` / `bwa samse` beyond -n / -X, upstream's defaults unless named:
     SearchOpts(max_gap_opens=2, seed_len=20).  Ranges: include/parasuite_hip.h; check() asks the library (host only)."""
-    _fields_ = [("struct_size", C.c_uint32)] + [(k, C.c_int32) for k in (
-        "max_gap_opens", "max_gap_extensions", "indel_end_skip", "max_del_occ", "seed_len", "max_seed_diff", "max_entries",
-        "s_mm", "s_gapo", "s_gape", "max_top2", "max_alt_hits")]
+    _fields_ = [("struct_size", C.c_uint32)] + _fields(
+        C.c_int32, "max_gap_opens", "max_gap_extensions", "indel_end_skip", "max_del_occ", "seed_len", "max_seed_diff", "max_entries",
+        "s_mm", "s_gapo", "s_gape", "max_top2", "max_alt_hits")
 
     def __init__(self, **kw):
         super().__init__()
@@ -52,11 +40,11 @@ class SearchOpts(C.Structure):
         _chk(lib().ps_search_opts_check(C.byref(self), 1 if profile_mode else 0))
 
 
-def _search_ptr(search):
-    """a SearchOpts, a dict of its fields, or None (the defaults)"""
-    if search is None:
-        return None
-    return C.byref(search if isinstance(search, SearchOpts) else SearchOpts(**search))
+class IndexInfo(C.Structure):
+    _fields_ = [("seq_len", C.c_uint64), ("l_pac", C.c_uint64), ("primary", C.c_uint64), ("L2", C.c_uint64 * 5),
+                ("n_blocks", C.c_uint64), ("n_sa", C.c_uint64), ("device_bytes", C.c_uint64),
+                ("n_contigs", C.c_int32), ("n_holes", C.c_int32), ("sa_rounds", C.c_int32), ("sa_intv", C.c_int32),
+                ("build_ms", C.c_double), ("jump_levels", C.c_int32), ("pad_", C.c_int32)]
 
 
 ALN_DTYPE = np.dtype([("k", "<u8"), ("l", "<u8"), ("score", "<u2"), ("units", "<u2"), ("n_mm", "u1"), ("n_gapo", "u1"),
@@ -65,14 +53,189 @@ HIT_DTYPE = np.dtype([("pos", "<i8"), ("sa", "<u8"), ("type", "<i4"), ("strand",
                       ("n_gapo", "<i4"), ("n_gape", "<i4"), ("ref_shift", "<i4"), ("score", "<i4"), ("c1", "<i4"),
                       ("c2", "<i4"), ("n_cigar", "<i4"), ("n_multi", "<i4"), ("cigar", "<u4", 16)], align=True)
 
-EXPORTS = ["ps_version", "ps_last_error", "ps_index", "ps_map", "ps_ctx_open", "ps_ctx_build", "ps_ctx_close",
-           "ps_search_opts_default", "ps_search_opts_check", "ps_ctx_set_search", "ps_map_opts",
-           "ps_ctx_set_stock", "ps_ctx_set_profile", "ps_ctx_set_profile_matrix", "ps_ctx_set_tiers", "ps_ctx_set_stats", "ps_ctx_set_lanes", "ps_ctx_info",
-           "ps_ctx_blob", "ps_ctx_meta", "ps_ctx_from_blobs", "ps_ctx_clone", "ps_ctx_fetch", "ps_ctx_export_blob", "ps_ctx_sa_lookup", "ps_ctx_order_sort", "ps_ctx_index_check", "ps_sam_to_bam", "ps_map_to_bam", "ps_bam_view", "ps_bam_sort", "ps_bam_index", "ps_batch_from_fastq",
-           "ps_batch_from_codes", "ps_batch_free", "ps_batch_n", "ps_batch_search", "ps_batch_select_hard",
-           "ps_batch_select_easy", "ps_batch_locate", "ps_batch_run", "ps_batch_write_sam", "ps_batch_n_aln",
-           "ps_batch_alns", "ps_batch_hits", "ps_batch_timing", "ps_batch_kstats", "ps_ctx_read_iters", "ps_parse_check", "ps_error_profile", "ps_error_profile_full", "ps_pileup_clusters", "ps_extract_weak_reads", "ps_combine_genome_transcript", "ps_map_profiled", "ps_release_host_cache", "ps_map_route", "ps_map_route_opts", "ps_extract_read_names", "ps_benchmark_reads", "ps_simulate_reads", "ps_fetch_sequences",
-           "ps_resident_begin", "ps_resident_end", "ps_resident_info"]
+
+class Timing(C.Structure):
+    _fields_ = _fields(C.c_double, "ms_width", "ms_backtrack", "ms_compact", "ms_select", "ms_sa2pos", "ms_refine", "ms_host_post",
+                       "ms_total") + \
+               _fields(C.c_int32, "n_width_launches", "n_backtrack_launches") + _fields(C.c_int64, "n_overflow_tier1", "n_overflow_tier2") + \
+               _fields(C.c_double, "ms_classify", "ms_rows", "ms_sel_hard", "ms_sel_easy", "bt_begin_ms", "bt_end_ms")
+
+
+class KStats(C.Structure):
+    _fields_ = _fields(C.c_uint64, "occ_pairs", "occ_same_blk", "nodes", "pushes", "pops", "lf_steps", "iters", "exact_steps")
+
+
+class BamStats(C.Structure):
+    _fields_ = _fields(C.c_uint64, "n_in", "n_out", "bam_bytes")
+
+
+class ProfileStats(C.Structure):
+    _fields_ = _fields(C.c_uint64, "n_records", "n_counted", "n_unmapped", "n_duplicate", "n_start_zero", "n_indel_reads", "n_skipped",
+                       "n_without_qual", "n_qual_beyond_read")
+
+
+class ClusterStats(C.Structure):
+    _fields_ = _fields(C.c_uint64, "n_records", "n_unmapped", "n_skipped_indel", "n_kept", "n_clusters", "n_clusters_written",
+                       "n_crosslinked", "n_ccr", "n_double_stranded", "n_snp_hits", "n_snv_sites", "n_t2c_beyond_51", "n_ccr_clipped",
+                       "n_ccr_past_end", "n_order_unmodelled")
+
+
+class ExtractStats(C.Structure):
+    _fields_ = _fields(C.c_uint64, "n_records", "n_weak", "n_kept", "bam_bytes")
+
+
+class NamesStats(C.Structure):
+    _fields_ = _fields(C.c_uint64, "n_records", "out_bytes")
+
+
+class CombineStats(C.Structure):
+    _fields_ = _fields(C.c_uint64, "n_genome", "n_transcript", "n_unplaced", "n_unlocated", "n_missed_indel_splice", "n_groups",
+                       "n_groups_ambiguous", "n_no_contig", "n_mt_unplaced", "n_lifted", "n_spliced", "n_strand_flipped", "bam_bytes")
+
+
+_ROUTE_PATHS = ("reads_fq", "ref_fa", "out_prefix", "transcripts_fa", "bwa_mm", "parasuite_mm", "error_profile", "indel_profile")
+_ROUTE_INTS = ("threads", "refine", "max_read_len", "mapq_genomic", "mapq_transcript")
+
+
+class RouteOpts(C.Structure):
+    _fields_ = _fields(C.c_char_p, *_ROUTE_PATHS) + _fields(C.c_int32, *_ROUTE_INTS)
+
+
+class RouteStats(C.Structure):
+    _fields_ = [("n_reads", C.c_uint64), ("first", BamStats), ("refine", BamStats), ("transcript", BamStats),
+                ("extract", ExtractStats), ("combine", CombineStats)] + \
+               _fields(C.c_double, "s_total", "s_parse", "s_index_genome", "s_index_transcripts", "s_first", "s_profile", "s_refine",
+                       "s_transcript", "s_combine") + \
+               _fields(C.c_uint32, "n_index_loads_genome", "n_index_loads_transcripts", "n_fastq_parses", "pad_")
+
+
+class RouteOpts2(C.Structure):
+    """ps_route_opts2: ps_route_opts' fields behind a struct_size, then ref_refine, search and keep_unaligned"""
+    _fields_ = [("struct_size", C.c_uint32)] + _fields(C.c_int32, *_ROUTE_INTS) + _fields(C.c_char_p, *_ROUTE_PATHS, "ref_refine") + \
+               [("search", C.POINTER(SearchOpts)), ("keep_unaligned", C.c_int32), ("pad_", C.c_int32)]
+
+
+ROUTE_OPTS_OLD_SIZE = RouteOpts2.ref_refine.offset          # a struct_size up to here holds what ps_route_opts holds
+
+
+class ResidentOpts(C.Structure):
+    _fields_ = _fields(C.c_uint32, "struct_size", "max_references")
+
+
+class ResidentStats(C.Structure):
+    _fields_ = _fields(C.c_uint32, "active", "n_references") + \
+               _fields(C.c_uint64, "n_calls", "n_index_loads", "n_index_reuses", "n_stale_reloads", "n_evictions", "n_dropped_after_error",
+                       "bytes_index_resident")
+
+
+class BenchmarkStats(C.Structure):
+    _fields_ = _fields(C.c_uint64, "n_lines", "n_reads", "n_positives", "n_negatives", "n_records", "n_processed", "n_tp", "n_tn",
+                       "n_unplaced", "n_other_contig", "n_outside", "n_other_bound", "bad_number_record") + \
+               _fields(C.c_float, "precision", "recall", "accuracy")
+
+
+class SimulateOpts(C.Structure):
+    _fields_ = _fields(C.c_char_p, "transcripts_fa", "out_prefix", "error_profile", "t2c_profile", "t2c_positions", "quality_dist",
+                       "indel_profile") + \
+               [("bound_prob", C.c_double), ("seed", C.c_uint64), ("select_read", C.c_double), ("snp_rate", C.c_double),
+                ("snp_report", C.c_double), ("allow_indels", C.c_int32), ("pad_", C.c_int32)]
+
+
+class SimulateStats(C.Structure):
+    _fields_ = _fields(C.c_uint64, "n_reads", "n_bases_simulated", "sum_read_length", "n_clusters", "n_t2c", "n_errors", "most_t2c",
+                       "most_errors", "n_indels", "n_snps", "n_transcripts", "n_selected", "n_clusters_skipped", "n_reads_skipped",
+                       "n_snps_reported", "n_non_acgt", "n_snps_preselected", "n_snp_positions") + \
+               _fields(C.c_double, "avg_read_length", "avg_reads_per_cluster", "s_total", "s_read", "s_plan", "s_snp", "s_snp_kernels",
+                       "s_reads", "s_write")
+
+
+class FetchStats(C.Structure):
+    _fields_ = _fields(C.c_uint64, "n_lines", "n_sites", "n_reverse", "n_bases", "n_hole_bases", "n_inverted", "n_no_contig",
+                       "n_past_end", "n_before_start", "n_pieces") + \
+               _fields(C.c_double, "s_total", "s_read", "s_index", "s_kernels", "s_write")
+
+
+# every struct typedef of the header -> its mirror (ps_aln and ps_hit are read as numpy records)
+STRUCTS = {"ps_search_opts": SearchOpts, "ps_index_info": IndexInfo, "ps_aln": ALN_DTYPE, "ps_hit": HIT_DTYPE, "ps_timing": Timing,
+           "ps_kstats": KStats, "ps_bam_stats": BamStats, "ps_profile_stats": ProfileStats, "ps_cluster_stats": ClusterStats,
+           "ps_extract_stats": ExtractStats, "ps_names_stats": NamesStats, "ps_combine_stats": CombineStats,
+           "ps_route_opts": RouteOpts, "ps_route_stats": RouteStats, "ps_route_opts2": RouteOpts2, "ps_resident_opts": ResidentOpts,
+           "ps_resident_stats": ResidentStats, "ps_benchmark_stats": BenchmarkStats, "ps_simulate_opts": SimulateOpts,
+           "ps_simulate_stats": SimulateStats, "ps_fetch_stats": FetchStats}
+
+# ---- the functions of the header, in its order: name -> (restype, argtypes) ----
+# int, int64_t, uint64_t, double, const char *; _PTR: ps_ctx *, ps_batch * and every buffer handed over as an address
+_I, _I64, _U64, _D, _S, _PTR, _P = C.c_int, C.c_int64, C.c_uint64, C.c_double, C.c_char_p, C.c_void_p, C.POINTER
+_MAP = [_I] + [_S] * 6          # threads, mm, error_profile, indel_profile, ref_fa, fastq, out
+
+SIGNATURES = {
+    "ps_version": (_S, []),
+    "ps_last_error": (_S, []),
+    "ps_index": (_I, [_S]),
+    "ps_map": (_I, _MAP),
+    "ps_search_opts_default": (None, [_P(SearchOpts)]),
+    "ps_search_opts_check": (_I, [_P(SearchOpts), _I]),
+    "ps_map_opts": (_I, _MAP + [_P(SearchOpts)]),
+    "ps_ctx_open": (_PTR, [_S, _I]),
+    "ps_ctx_clone": (_PTR, [_PTR, _I]),
+    "ps_ctx_build": (_PTR, [_S, _I, _I]),
+    "ps_ctx_close": (None, [_PTR]),
+    "ps_ctx_set_stock": (_I, [_PTR, _S]),
+    "ps_ctx_set_profile": (_I, [_PTR, _S, _S, _S]),
+    "ps_ctx_set_profile_matrix": (_I, [_PTR, _P(_D), _D, _D, _I]),
+    "ps_ctx_set_search": (_I, [_PTR, _P(SearchOpts)]),
+    "ps_ctx_set_tiers": (_I, [_PTR, _P(C.c_uint32), _P(C.c_int32), _I]),
+    "ps_ctx_set_stats": (_I, [_PTR, _I]),
+    "ps_ctx_set_lanes": (_I, [_PTR, _I]),
+    "ps_ctx_info": (_I, [_PTR, _P(IndexInfo)]),
+    "ps_ctx_blob": (_I, [_PTR, _I, _P(_PTR), _P(_U64)]),
+    "ps_ctx_meta": (_I64, [_PTR, _S, _I64]),
+    "ps_ctx_from_blobs": (_PTR, [_S, _I64, _I, _P(_PTR)]),
+    "ps_ctx_fetch": (_I, [_PTR, _I, _PTR, _U64]),
+    "ps_ctx_export_blob": (_I, [_PTR, _I, _PTR, _U64]),
+    "ps_ctx_index_check": (_I, [_PTR, _PTR]),
+    "ps_ctx_sa_lookup": (_I, [_PTR, _PTR, _I64, _PTR]),
+    "ps_ctx_order_sort": (_I, [_PTR, _PTR, _I64, _PTR]),
+    "ps_batch_from_fastq": (_PTR, [_PTR, _S]),
+    "ps_batch_from_codes": (_PTR, [_PTR, _I64, _I, _PTR]),
+    "ps_batch_free": (None, [_PTR]),
+    "ps_batch_n": (_I64, [_PTR]),
+    "ps_batch_search": (_I, [_PTR]),
+    "ps_batch_select_hard": (_I, [_PTR, _U64, _P(_U64)]),
+    "ps_batch_select_easy": (_I, [_PTR, _I]),
+    "ps_batch_locate": (_I, [_PTR]),
+    "ps_batch_run": (_I, [_PTR, _I]),
+    "ps_batch_write_sam": (_I, [_PTR, _S, _I, _I]),
+    "ps_batch_n_aln": (_I, [_PTR, _PTR, _I64]),
+    "ps_batch_alns": (_I64, [_PTR, _I64, _PTR, _I64]),
+    "ps_batch_hits": (_I, [_PTR, _PTR, _I64]),
+    "ps_batch_timing": (_I, [_PTR, _P(Timing)]),
+    "ps_ctx_read_iters": (_I64, [_PTR, _PTR, _I64]),
+    "ps_batch_kstats": (_I, [_PTR, _I, _P(KStats)]),
+    "ps_release_host_cache": (None, []),
+    "ps_parse_check": (_I, [_S, _I, _U64, _P(_U64)]),
+    "ps_sam_to_bam": (_I, [_S, _S, _I, _I, _I, _I, _P(BamStats)]),
+    "ps_map_to_bam": (_I, _MAP + [_I, _I, _I, _P(BamStats)]),
+    "ps_bam_view": (_I, [_S, _S, _I, _I, _P(BamStats)]),
+    "ps_bam_sort": (_I, [_S, _S, _I, _I, _P(BamStats)]),
+    "ps_bam_index": (_I, [_S, _I]),
+    "ps_error_profile": (_I, [_S, _S, _I, _S]),
+    "ps_error_profile_full": (_I, [_S, _S, _I, _S, _I, _P(ProfileStats)]),
+    "ps_pileup_clusters": (_I, [_S, _S, _S, _S, _I, _S, _P(ClusterStats)]),
+    "ps_extract_weak_reads": (_I, [_S, _S, _S, _I, _I, _P(ExtractStats)]),
+    "ps_extract_read_names": (_I, [_S, _S, _P(NamesStats)]),
+    "ps_combine_genome_transcript": (_I, [_S, _S, _S, _I, _I, _I, _P(CombineStats)]),
+    "ps_map_profiled": (_I, _MAP + [_I, _I, _S]),
+    "ps_map_route": (_I, [_P(RouteOpts), _P(RouteStats)]),
+    "ps_map_route_opts": (_I, [_P(RouteOpts2), _P(RouteStats)]),
+    "ps_resident_begin": (_I, [_P(ResidentOpts)]),
+    "ps_resident_end": (_I, []),
+    "ps_resident_info": (_I, [_P(ResidentStats)]),
+    "ps_benchmark_reads": (_I, [_S, _S, _S, _P(BenchmarkStats)]),
+    "ps_simulate_reads": (_I, [_P(SimulateOpts), _P(SimulateStats)]),
+    "ps_fetch_sequences": (_I, [_S, _S, _S, _I, _P(FetchStats)]),
+}
+EXPORTS = list(SIGNATURES)
 
 _LIB = None
 
@@ -84,59 +247,9 @@ def lib():
     if not os.path.exists(SO_PATH):
         raise ImportError("libparasuite_hip.so is not built (run __graft_entry__.build()); there is no CPU fallback")
     L = C.CDLL(SO_PATH)
-    P = C.POINTER
-    L.ps_version.restype = C.c_char_p
-    L.ps_last_error.restype = C.c_char_p
-    L.ps_index.argtypes = [C.c_char_p]
-    L.ps_map.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p]
-    L.ps_map_opts.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, P(SearchOpts)]
-    L.ps_search_opts_default.argtypes = [P(SearchOpts)]
-    L.ps_search_opts_default.restype = None
-    L.ps_search_opts_check.argtypes = [P(SearchOpts), C.c_int]
-    L.ps_ctx_set_search.argtypes = [C.c_void_p, P(SearchOpts)]
-    L.ps_ctx_open.argtypes = [C.c_char_p, C.c_int]
-    L.ps_ctx_open.restype = C.c_void_p
-    L.ps_ctx_build.argtypes = [C.c_char_p, C.c_int, C.c_int]
-    L.ps_ctx_build.restype = C.c_void_p
-    L.ps_ctx_close.argtypes = [C.c_void_p]
-    L.ps_ctx_set_stock.argtypes = [C.c_void_p, C.c_char_p]
-    L.ps_ctx_set_profile.argtypes = [C.c_void_p, C.c_char_p, C.c_char_p, C.c_char_p]
-    L.ps_ctx_set_profile_matrix.argtypes = [C.c_void_p, P(C.c_double), C.c_double, C.c_double, C.c_int]
-    L.ps_ctx_set_tiers.argtypes = [C.c_void_p, P(C.c_uint32), P(C.c_int32), C.c_int]
-    L.ps_ctx_set_stats.argtypes = [C.c_void_p, C.c_int]
-    L.ps_ctx_set_lanes.argtypes = [C.c_void_p, C.c_int]
-    L.ps_ctx_info.argtypes = [C.c_void_p, P(IndexInfo)]
-    L.ps_ctx_blob.argtypes = [C.c_void_p, C.c_int, P(C.c_void_p), P(C.c_uint64)]
-    L.ps_ctx_meta.argtypes = [C.c_void_p, C.c_char_p, C.c_int64]
-    L.ps_ctx_meta.restype = C.c_int64
-    L.ps_ctx_from_blobs.argtypes = [C.c_char_p, C.c_int64, C.c_int, P(C.c_void_p)]
-    L.ps_ctx_from_blobs.restype = C.c_void_p
-    L.ps_ctx_fetch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
-    L.ps_ctx_export_blob.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
-    L.ps_ctx_sa_lookup.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.ps_ctx_order_sort.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.ps_ctx_index_check.argtypes = [C.c_void_p, C.c_void_p]
-    L.ps_batch_from_fastq.argtypes = [C.c_void_p, C.c_char_p]
-    L.ps_batch_from_fastq.restype = C.c_void_p
-    L.ps_batch_from_codes.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_void_p]
-    L.ps_batch_from_codes.restype = C.c_void_p
-    L.ps_batch_free.argtypes = [C.c_void_p]
-    L.ps_batch_n.argtypes = [C.c_void_p]
-    L.ps_batch_n.restype = C.c_int64
-    L.ps_batch_search.argtypes = [C.c_void_p]
-    L.ps_batch_select_hard.argtypes = [C.c_void_p, C.c_uint64, P(C.c_uint64)]
-    L.ps_batch_select_easy.argtypes = [C.c_void_p, C.c_int]
-    L.ps_batch_locate.argtypes = [C.c_void_p]
-    L.ps_batch_run.argtypes = [C.c_void_p, C.c_int]
-    L.ps_batch_write_sam.argtypes = [C.c_void_p, C.c_char_p, C.c_int, C.c_int]
-    L.ps_batch_n_aln.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.ps_batch_alns.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64]
-    L.ps_batch_alns.restype = C.c_int64
-    L.ps_batch_hits.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.ps_batch_timing.argtypes = [C.c_void_p, P(Timing)]
-    L.ps_ctx_read_iters.argtypes = [C.c_void_p, C.c_void_p, C.c_int64]
-    L.ps_ctx_read_iters.restype = C.c_int64
-    L.ps_batch_kstats.argtypes = [C.c_void_p, C.c_int, P(KStats)]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _LIB = L
     return L
 
@@ -148,6 +261,30 @@ class PsError(RuntimeError):
 def _chk(rc):
     if rc:
         raise PsError(lib().ps_last_error().decode())
+
+
+def _opt(v):
+    """a parameter the header documents as optional: None or "" -> NULL, anything else its text.  Required strings are encoded
+    where they are passed, so that None for one of them raises here instead of reaching the library"""
+    return None if v is None or v == "" else str(v).encode()
+
+
+def _search_ptr(search):
+    """a SearchOpts, a dict of its fields, or None (the defaults)"""
+    if search is None:
+        return None
+    return C.pointer(search if isinstance(search, SearchOpts) else SearchOpts(**search))
+
+
+def _struct_dict(st):
+    return {f: (_struct_dict(getattr(st, f)) if isinstance(getattr(st, f), C.Structure) else getattr(st, f)) for f, _ in st._fields_}
+
+
+def _stats(fn, cls, *args):
+    """fn(*args, &stats) for a call whose last parameter is its stats struct; returns the struct as a dict (nested for nested structs)"""
+    st = cls()
+    _chk(fn(*args, C.byref(st)))
+    return _struct_dict(st)
 
 
 class Ctx:
@@ -176,8 +313,6 @@ class Ctx:
 
     def clone(self, device=0):
         """a second context holding a device-to-device copy of this one's index (ps_map's route to every device after the first)"""
-        lib().ps_ctx_clone.restype = C.c_void_p
-        lib().ps_ctx_clone.argtypes = [C.c_void_p, C.c_int]
         return Ctx(lib().ps_ctx_clone(self.h, int(device)))
 
     def close(self):
@@ -199,7 +334,7 @@ class Ctx:
         _chk(lib().ps_ctx_set_search(self.h, _search_ptr(kw if search is None and kw else search)))
 
     def set_profile_files(self, ep, ip, x="-1"):
-        _chk(lib().ps_ctx_set_profile(self.h, ep.encode(), ip.encode() if ip else None, str(x).encode()))
+        _chk(lib().ps_ctx_set_profile(self.h, ep.encode(), _opt(ip), str(x).encode()))
 
     def set_profile(self, P, ins_rate=0.0, del_rate=0.0, x=-1):
         arr = (C.c_double * 16)(*[float(v) for v in np.asarray(P, dtype=np.float64).reshape(16)])
@@ -368,119 +503,58 @@ class Batch:
         return out
 
     def timing(self):
-        t = Timing()
-        _chk(lib().ps_batch_timing(self.h, C.byref(t)))
-        return {k: getattr(t, k) for k, _ in Timing._fields_}
+        return _stats(lib().ps_batch_timing, Timing, self.h)
 
     def kstats(self, which):
-        k = KStats()
-        _chk(lib().ps_batch_kstats(self.h, which, C.byref(k)))
-        return {f: getattr(k, f) for f, _ in KStats._fields_}
+        return _stats(lib().ps_batch_kstats, KStats, self.h, which)
 
 
 def ps_parse_check(path, threads=1, chunk_bytes=0):
     """host-only: (reads, bases, hash, pieces) of the read parser -- whole file, or streamed in windows as ps_map does"""
-    L = lib(); L.ps_parse_check.argtypes = [C.c_char_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
     out = (C.c_uint64 * 4)()
-    _chk(L.ps_parse_check(path.encode(), int(threads), int(chunk_bytes), out))
+    _chk(lib().ps_parse_check(path.encode(), int(threads), int(chunk_bytes), out))
     return tuple(int(v) for v in out)
 
 
 def ps_error_profile(mapping, ref_fa, max_read_len=101, out_prefix=None):
     """<out_prefix>.errorprofile / .indelprofile from the records of a SAM or BAM file (counted on the GPU)"""
-    L = lib(); L.ps_error_profile.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p]
-    _chk(L.ps_error_profile(mapping.encode(), ref_fa.encode(), int(max_read_len), out_prefix.encode() if out_prefix else None))
-
-
-class ProfileStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("n_records", "n_counted", "n_unmapped", "n_duplicate", "n_start_zero", "n_indel_reads",
-                                          "n_skipped", "n_without_qual", "n_qual_beyond_read")]
+    _chk(lib().ps_error_profile(mapping.encode(), ref_fa.encode(), int(max_read_len), _opt(out_prefix)))
 
 
 def ps_error_profile_full(mapping, ref_fa, max_read_len=101, out_prefix=None, infer_qualities=False):
     """all six files of ErrorProfiling.inferErrorProfile(infer_qualities, false): <out_prefix>.errorprofile, .indelprofile,
     .errorprofile.vcf, .qualityPerMismatch, .indels, .qualities (empty without infer_qualities); returns the record counters"""
-    L = lib(); L.ps_error_profile_full.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_char_p, C.c_int, C.POINTER(ProfileStats)]
-    st = ProfileStats()
-    _chk(L.ps_error_profile_full(mapping.encode(), ref_fa.encode(), int(max_read_len), out_prefix.encode() if out_prefix else None,
-                                 int(bool(infer_qualities)), C.byref(st)))
-    return {f: int(getattr(st, f)) for f, _ in ProfileStats._fields_}
-
-
-class ClusterStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("n_records", "n_unmapped", "n_skipped_indel", "n_kept", "n_clusters", "n_clusters_written",
-                                          "n_crosslinked", "n_ccr", "n_double_stranded", "n_snp_hits", "n_snv_sites",
-                                          "n_t2c_beyond_51", "n_ccr_clipped", "n_ccr_past_end", "n_order_unmodelled")]
+    return _stats(lib().ps_error_profile_full, ProfileStats, mapping.encode(), ref_fa.encode(), int(max_read_len), _opt(out_prefix),
+                  int(bool(infer_qualities)))
 
 
 def ps_pileup_clusters(mapping, ref_fa, out_file, snp_vcf=None, min_read_coverage=1, site_prefix=None):
     """the six files of PileupClusters.calculateReadPileups: <out_file>, .ccr.fasta, .ccr.tsv, .report and
-    <site_prefix or mapping>.sitefrequency.tsv, .sitepositions.tsv (counted on the GPU); returns the counters"""
-    enc = lambda v: v.encode() if v else None
-    L = lib(); L.ps_pileup_clusters.argtypes = [C.c_char_p] * 4 + [C.c_int, C.c_char_p, C.POINTER(ClusterStats)]
-    st = ClusterStats()
-    _chk(L.ps_pileup_clusters(enc(mapping), enc(ref_fa), enc(out_file), enc(snp_vcf), int(min_read_coverage), enc(site_prefix), C.byref(st)))
-    return {f: int(getattr(st, f)) for f, _ in ClusterStats._fields_}
-
-
-class ExtractStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("n_records", "n_weak", "n_kept", "bam_bytes")]
+    <site_prefix or mapping>.sitefrequency.tsv, .sitepositions.tsv (counted on the GPU); returns the counters.
+    The library itself refuses a missing mapping, ref_fa or out_file"""
+    return _stats(lib().ps_pileup_clusters, ClusterStats, _opt(mapping), _opt(ref_fa), _opt(out_file), _opt(snp_vcf), int(min_read_coverage),
+                  _opt(site_prefix))
 
 
 def ps_extract_weak_reads(mapping, out_bam, out_fastq, mapq_threshold=10, threads=8):
     """ExtractWeakMappingReads.extractReads: records with MAPQ < mapq_threshold -> out_fastq (read orientation restored), the
     others -> out_bam under the input's header (host code, needs no GPU); returns the counters"""
-    L = lib(); L.ps_extract_weak_reads.argtypes = [C.c_char_p] * 3 + [C.c_int, C.c_int, C.POINTER(ExtractStats)]
-    st = ExtractStats()
-    _chk(L.ps_extract_weak_reads(mapping.encode(), out_bam.encode(), out_fastq.encode(), int(mapq_threshold), int(threads), C.byref(st)))
-    return {f: int(getattr(st, f)) for f, _ in ExtractStats._fields_}
-
-
-class CombineStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("n_genome", "n_transcript", "n_unplaced", "n_unlocated", "n_missed_indel_splice", "n_groups",
-                                          "n_groups_ambiguous", "n_no_contig", "n_mt_unplaced", "n_lifted", "n_spliced",
-                                          "n_strand_flipped", "bam_bytes")]
+    return _stats(lib().ps_extract_weak_reads, ExtractStats, mapping.encode(), out_bam.encode(), out_fastq.encode(), int(mapq_threshold),
+                  int(threads))
 
 
 def ps_combine_genome_transcript(genome_bam, transcript_bam, out_bam, sort_by_coordinate=False, write_index=False, threads=8):
     """CombineGenomeTranscript.combine: the genomic records, then the transcript hits lifted to genome coordinates (on the GPU),
     optionally coordinate-sorted with <out_bam>.bai; returns the counters"""
-    L = lib(); L.ps_combine_genome_transcript.argtypes = [C.c_char_p] * 3 + [C.c_int] * 3 + [C.POINTER(CombineStats)]
-    st = CombineStats()
-    _chk(L.ps_combine_genome_transcript(genome_bam.encode(), transcript_bam.encode(), out_bam.encode(), int(bool(sort_by_coordinate)),
-                                        int(bool(write_index)), int(threads), C.byref(st)))
-    return {f: int(getattr(st, f)) for f, _ in CombineStats._fields_}
-
-
-class BenchmarkStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("n_lines", "n_reads", "n_positives", "n_negatives", "n_records", "n_processed", "n_tp", "n_tn",
-                                          "n_unplaced", "n_other_contig", "n_outside", "n_other_bound", "bad_number_record")] + \
-               [(k, C.c_float) for k in ("precision", "recall", "accuracy")]
+    return _stats(lib().ps_combine_genome_transcript, CombineStats, genome_bam.encode(), transcript_bam.encode(), out_bam.encode(),
+                  int(bool(sort_by_coordinate)), int(bool(write_index)), int(threads))
 
 
 def ps_benchmark_reads(mapping, out_statistics, reads_fq):
     """ValidateBenchmarkStatisticsPARCLIP.calculateBenchmarkStatistics: a mapping of simulated reads (SAM or BAM) scored against
     the truth in the read names, the reads file counted for the totals (both on the GPU); writes out_statistics and returns
     the counters"""
-    L = lib(); L.ps_benchmark_reads.argtypes = [C.c_char_p] * 3 + [C.POINTER(BenchmarkStats)]
-    st = BenchmarkStats()
-    _chk(L.ps_benchmark_reads(mapping.encode(), out_statistics.encode(), reads_fq.encode(), C.byref(st)))
-    return {f: getattr(st, f) for f, _ in BenchmarkStats._fields_}
-
-
-class SimulateOpts(C.Structure):
-    _fields_ = [(k, C.c_char_p) for k in ("transcripts_fa", "out_prefix", "error_profile", "t2c_profile", "t2c_positions", "quality_dist",
-                                          "indel_profile")] + \
-               [("bound_prob", C.c_double), ("seed", C.c_uint64), ("select_read", C.c_double), ("snp_rate", C.c_double),
-                ("snp_report", C.c_double), ("allow_indels", C.c_int32), ("pad_", C.c_int32)]
-
-
-class SimulateStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("n_reads", "n_bases_simulated", "sum_read_length", "n_clusters", "n_t2c", "n_errors", "most_t2c",
-                                          "most_errors", "n_indels", "n_snps", "n_transcripts", "n_selected", "n_clusters_skipped",
-                                          "n_reads_skipped", "n_snps_reported", "n_non_acgt", "n_snps_preselected", "n_snp_positions")] + \
-               [(k, C.c_double) for k in ("avg_read_length", "avg_reads_per_cluster", "s_total", "s_read", "s_plan", "s_snp", "s_snp_kernels",
-                                          "s_reads", "s_write")]
+    return _stats(lib().ps_benchmark_reads, BenchmarkStats, mapping.encode(), out_statistics.encode(), reads_fq.encode())
 
 
 def ps_simulate_reads(transcripts_fa, out_prefix, error_profile, t2c_profile, t2c_positions, quality_dist, indel_profile, bound_prob, seed=0,
@@ -488,37 +562,29 @@ def ps_simulate_reads(transcripts_fa, out_prefix, error_profile, t2c_profile, t2
     """bin/createSimulatedPARCLIPDataset.pl, the `simulate` mode: PAR-CLIP reads drawn from transcripts on the GPU; writes
     <out_prefix>.fastq, .clusters, _snps.vsf, .log and .err and returns the counters.  None for one of the last four selects the
     Perl's constant (0.216, 0.01, 0.8, indels allowed)"""
-    L = lib(); L.ps_simulate_reads.argtypes = [C.POINTER(SimulateOpts), C.POINTER(SimulateStats)]
     o = SimulateOpts(*[str(v).encode() for v in (transcripts_fa, out_prefix, error_profile, t2c_profile, t2c_positions, quality_dist, indel_profile)],
                      float(bound_prob), int(seed), -1.0 if select_read is None else float(select_read), -1.0 if snp_rate is None else float(snp_rate),
                      -1.0 if snp_report is None else float(snp_report), -1 if allow_indels is None else int(bool(allow_indels)), 0)
-    st = SimulateStats()
-    _chk(L.ps_simulate_reads(C.byref(o), C.byref(st)))
-    return {f: getattr(st, f) for f, _ in SimulateStats._fields_}
-
-
-class FetchStats(C.Structure):
-    _fields_ = [(k, C.c_uint64) for k in ("n_lines", "n_sites", "n_reverse", "n_bases", "n_hole_bases", "n_inverted", "n_no_contig",
-                                          "n_past_end", "n_before_start", "n_pieces")] + \
-               [(k, C.c_double) for k in ("s_total", "s_read", "s_index", "s_kernels", "s_write")]
+    return _stats(lib().ps_simulate_reads, SimulateStats, C.byref(o))
 
 
 def ps_fetch_sequences(ref_fa, sites, out_file, bed=False):
     """FetchSequencesForBindingSites / FetchSequencesForBEDFile.fetchSequences, the `fetch` (bed false) and `fetchBed` modes:
     the reference sequence of every site of a table, gathered on the GPU from the index of ref_fa (.ann and .pac; the FASTA is
     not opened); writes out_file and returns the counters"""
-    L = lib(); L.ps_fetch_sequences.argtypes = [C.c_char_p] * 3 + [C.c_int, C.POINTER(FetchStats)]
-    st = FetchStats()
-    _chk(L.ps_fetch_sequences(ref_fa.encode(), sites.encode(), out_file.encode(), int(bool(bed)), C.byref(st)))
-    return {f: getattr(st, f) for f, _ in FetchStats._fields_}
+    return _stats(lib().ps_fetch_sequences, FetchStats, ref_fa.encode(), sites.encode(), out_file.encode(), int(bool(bed)))
 
 
-def ps_map_profiled(threads, mm,error_profile, indel_profile, ref_fa, reads, out_sam, min_mapq, max_read_len, profile_prefix):
-    """ps_map + <profile_prefix>.errorprofile / .indelprofile of its alignments with MAPQ >= min_mapq, counted from memory"""
-    enc = lambda v: v.encode() if v else None
-    L = lib(); L.ps_map_profiled.argtypes = [C.c_int] + [C.c_char_p] * 6 + [C.c_int, C.c_int, C.c_char_p]
-    _chk(L.ps_map_profiled(int(threads), enc(str(mm)), enc(error_profile), enc(indel_profile), enc(ref_fa), enc(reads), enc(out_sam),
-                           int(min_mapq), int(max_read_len), enc(profile_prefix)))
+def _map_args(threads, mm, error_profile, indel_profile, ref_fa, fastq, out):
+    """what ps_map, ps_map_opts, ps_map_to_bam and ps_map_profiled have in common: the two profile files are optional"""
+    return int(threads), str(mm).encode(), _opt(error_profile), _opt(indel_profile), ref_fa.encode(), fastq.encode(), out.encode()
+
+
+def ps_map_profiled(threads, mm, error_profile, indel_profile, ref_fa, reads, out_sam, min_mapq, max_read_len, profile_prefix):
+    """ps_map + <profile_prefix>.errorprofile / .indelprofile of its alignments with MAPQ >= min_mapq, counted from memory
+    (the library refuses a missing profile_prefix)"""
+    _chk(lib().ps_map_profiled(*_map_args(threads, mm, error_profile, indel_profile, ref_fa, reads, out_sam), int(min_mapq), int(max_read_len),
+                               _opt(profile_prefix)))
 
 
 def ps_index(ref_fa):
@@ -527,76 +593,41 @@ def ps_index(ref_fa):
 
 def ps_map(threads, mm, error_profile, indel_profile, ref_fa, fastq, out_sam, search=None):
     """search: a SearchOpts or a dict of its fields (`ps_map_opts`); None: `ps_map`"""
-    args = (int(threads), str(mm).encode(), error_profile.encode() if error_profile else None,
-            indel_profile.encode() if indel_profile else None, ref_fa.encode(), fastq.encode(), out_sam.encode())
+    args = _map_args(threads, mm, error_profile, indel_profile, ref_fa, fastq, out_sam)
     if search is None:
         _chk(lib().ps_map(*args))
     else:
         _chk(lib().ps_map_opts(*args, _search_ptr(search)))
 
 
-class BamStats(C.Structure):
-    _fields_ = [("n_in", C.c_uint64), ("n_out", C.c_uint64), ("bam_bytes", C.c_uint64)]
-
-
 def ps_sam_to_bam(sam, bam, min_mapq=0, sort_by_coordinate=False, write_index=False, threads=8):
     """SAM text -> BAM; MAPQ filter, coordinate sort and <bam>.bai in the same pass (host code, needs no GPU)."""
-    L = lib()
-    L.ps_sam_to_bam.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(BamStats)]
-    st = BamStats()
-    _chk(L.ps_sam_to_bam(sam.encode(), bam.encode(), int(min_mapq), int(bool(sort_by_coordinate)), int(bool(write_index)),
-                         int(threads), C.byref(st)))
-    return dict(n_in=st.n_in, n_out=st.n_out, bam_bytes=st.bam_bytes)
+    return _stats(lib().ps_sam_to_bam, BamStats, sam.encode(), bam.encode(), int(min_mapq), int(bool(sort_by_coordinate)), int(bool(write_index)),
+                  int(threads))
 
 
 def ps_map_to_bam(threads, mm, error_profile, indel_profile, ref_fa, fastq, out_bam, min_mapq=0, sort_by_coordinate=False, write_index=False):
     """ps_map with the records going straight into a (MAPQ-filtered, optionally sorted + indexed) BAM: no SAM text in between"""
-    L = lib()
-    L.ps_map_to_bam.argtypes = [C.c_int, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.POINTER(BamStats)]
-    st = BamStats()
-    _chk(L.ps_map_to_bam(int(threads), str(mm).encode(), error_profile.encode() if error_profile else None,
-                         indel_profile.encode() if indel_profile else None, ref_fa.encode(), fastq.encode(), out_bam.encode(),
-                         int(min_mapq), int(bool(sort_by_coordinate)), int(bool(write_index)), C.byref(st)))
-    return dict(n_in=st.n_in, n_out=st.n_out, bam_bytes=st.bam_bytes)
-
-
-def _bam_call(fn, *args):
-    st = BamStats()
-    _chk(fn(*args, C.byref(st)))
-    return dict(n_in=st.n_in, n_out=st.n_out, bam_bytes=st.bam_bytes)
+    return _stats(lib().ps_map_to_bam, BamStats, *_map_args(threads, mm, error_profile, indel_profile, ref_fa, fastq, out_bam),
+                  int(min_mapq), int(bool(sort_by_coordinate)), int(bool(write_index)))
 
 
 def ps_bam_view(in_bam, out_bam, min_mapq=0, threads=8):
-    L = lib(); L.ps_bam_view.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(BamStats)]
-    return _bam_call(L.ps_bam_view, in_bam.encode(), out_bam.encode(), int(min_mapq), int(threads))
+    return _stats(lib().ps_bam_view, BamStats, in_bam.encode(), out_bam.encode(), int(min_mapq), int(threads))
 
 
 def ps_bam_sort(in_bam, out_bam, by_name=False, threads=8):
-    L = lib(); L.ps_bam_sort.argtypes = [C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.POINTER(BamStats)]
-    return _bam_call(L.ps_bam_sort, in_bam.encode(), out_bam.encode(), int(bool(by_name)), int(threads))
+    return _stats(lib().ps_bam_sort, BamStats, in_bam.encode(), out_bam.encode(), int(bool(by_name)), int(threads))
 
 
 def ps_bam_index(bam, threads=8):
-    L = lib(); L.ps_bam_index.argtypes = [C.c_char_p, C.c_int]
-    _chk(L.ps_bam_index(bam.encode(), int(threads)))
+    _chk(lib().ps_bam_index(bam.encode(), int(threads)))
 
 
-class RouteOpts(C.Structure):
-    _fields_ = [(k, C.c_char_p) for k in ("reads_fq", "ref_fa", "out_prefix", "transcripts_fa", "bwa_mm", "parasuite_mm",
-                                          "error_profile", "indel_profile")] + \
-               [(k, C.c_int32) for k in ("threads", "refine", "max_read_len", "mapq_genomic", "mapq_transcript")]
-
-
-class RouteStats(C.Structure):
-    _fields_ = [("n_reads", C.c_uint64), ("first", BamStats), ("refine", BamStats), ("transcript", BamStats),
-                ("extract", ExtractStats), ("combine", CombineStats)] + \
-               [(k, C.c_double) for k in ("s_total", "s_parse", "s_index_genome", "s_index_transcripts", "s_first", "s_profile",
-                                          "s_refine", "s_transcript", "s_combine")] + \
-               [(k, C.c_uint32) for k in ("n_index_loads_genome", "n_index_loads_transcripts", "n_fastq_parses", "pad_")]
-
-
-def _struct_dict(st):
-    return {f: (_struct_dict(getattr(st, f)) if isinstance(getattr(st, f), C.Structure) else getattr(st, f)) for f, _ in st._fields_}
+def _route_args(paths, threads, refine, max_read_len, mapq_genomic, mapq_transcript):
+    """the fields ps_route_opts and ps_route_opts2 share: (the eight strings, the five integers).  Every string goes through
+    _opt: the library itself refuses a missing reads_fq, ref_fa or out_prefix before it touches anything"""
+    return [_opt(p) for p in paths], [int(threads), int(bool(refine)), int(max_read_len), int(mapq_genomic), int(mapq_transcript)]
 
 
 def ps_map_route(reads_fq, ref_fa, out_prefix, transcripts_fa=None, threads=8, refine=False, max_read_len=101, mapq_genomic=10,
@@ -604,25 +635,10 @@ def ps_map_route(reads_fq, ref_fa, out_prefix, transcripts_fa=None, threads=8, r
     """the toolkit's whole `map` mode (Main.java:249-420) in one call: the passes, the error profile, the weak-read extraction, the
     lift and the sorts with the reads parsed once, each index loaded once and everything between the passes handed over in memory;
     leaves the files Main.java names under out_prefix and returns ps_route_stats as nested dicts"""
-    enc = lambda v: str(v).encode() if v not in (None, "") else None
-    L = lib(); L.ps_map_route.argtypes = [C.POINTER(RouteOpts), C.POINTER(RouteStats)]
-    o = RouteOpts(enc(reads_fq), enc(ref_fa), enc(out_prefix), enc(transcripts_fa), enc(bwa_mm), enc(parasuite_mm), enc(error_profile),
-                  enc(indel_profile), int(threads), int(bool(refine)), int(max_read_len), int(mapq_genomic), int(mapq_transcript))
-    st = RouteStats()
-    _chk(L.ps_map_route(C.byref(o), C.byref(st)))
-    return _struct_dict(st)
-
-
-class RouteOpts2(C.Structure):
-    """ps_route_opts2: ps_route_opts' fields behind a struct_size, then ref_refine, search and keep_unaligned"""
-    _fields_ = [("struct_size", C.c_uint32)] + \
-               [(k, C.c_int32) for k in ("threads", "refine", "max_read_len", "mapq_genomic", "mapq_transcript")] + \
-               [(k, C.c_char_p) for k in ("reads_fq", "ref_fa", "out_prefix", "transcripts_fa", "bwa_mm", "parasuite_mm",
-                                          "error_profile", "indel_profile", "ref_refine")] + \
-               [("search", C.POINTER(SearchOpts)), ("keep_unaligned", C.c_int32), ("pad_", C.c_int32)]
-
-
-ROUTE_OPTS_OLD_SIZE = RouteOpts2.ref_refine.offset          # a struct_size up to here holds what ps_route_opts holds
+    paths, ints = _route_args((reads_fq, ref_fa, out_prefix, transcripts_fa, bwa_mm, parasuite_mm, error_profile, indel_profile),
+                              threads, refine, max_read_len, mapq_genomic, mapq_transcript)
+    o = RouteOpts(*paths, *ints)
+    return _stats(lib().ps_map_route, RouteStats, C.byref(o))
 
 
 def ps_map_route_opts(reads_fq, ref_fa, out_prefix, transcripts_fa=None, threads=8, refine=False, max_read_len=101, mapq_genomic=10,
@@ -630,45 +646,22 @@ def ps_map_route_opts(reads_fq, ref_fa, out_prefix, transcripts_fa=None, threads
                       keep_unaligned=False, search=None, struct_size=None):
     """ps_map_route with Main.java's --ref-refine and --unaligned and the search options of every pass (a SearchOpts, a dict of
     its fields or None); struct_size: the size the struct claims (None: all of it)"""
-    enc = lambda v: str(v).encode() if v not in (None, "") else None
-    L = lib(); L.ps_map_route_opts.argtypes = [C.POINTER(RouteOpts2), C.POINTER(RouteStats)]
-    so = None if search is None else (search if isinstance(search, SearchOpts) else SearchOpts(**search))
-    o = RouteOpts2(C.sizeof(RouteOpts2) if struct_size is None else int(struct_size), int(threads), int(bool(refine)), int(max_read_len),
-                   int(mapq_genomic), int(mapq_transcript), enc(reads_fq), enc(ref_fa), enc(out_prefix), enc(transcripts_fa), enc(bwa_mm),
-                   enc(parasuite_mm), enc(error_profile), enc(indel_profile), enc(ref_refine),
-                   C.pointer(so) if so is not None else None, int(bool(keep_unaligned)), 0)
-    st = RouteStats()
-    _chk(L.ps_map_route_opts(C.byref(o), C.byref(st)))
-    return _struct_dict(st)
-
-
-class NamesStats(C.Structure):
-    _fields_ = [("n_records", C.c_uint64), ("out_bytes", C.c_uint64)]
+    paths, ints = _route_args((reads_fq, ref_fa, out_prefix, transcripts_fa, bwa_mm, parasuite_mm, error_profile, indel_profile),
+                              threads, refine, max_read_len, mapq_genomic, mapq_transcript)
+    o = RouteOpts2(C.sizeof(RouteOpts2) if struct_size is None else int(struct_size), *ints, *paths, _opt(ref_refine),
+                   _search_ptr(search), int(bool(keep_unaligned)), 0)
+    return _stats(lib().ps_map_route_opts, RouteStats, C.byref(o))
 
 
 def ps_extract_read_names(mapping, out_file):
     """ExtractNotMappedReads.extractReads, the `extractAligned` mode: "@" + QNAME per record of a SAM or BAM file, in file order
     (host code, needs no GPU)"""
-    L = lib(); L.ps_extract_read_names.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(NamesStats)]
-    st = NamesStats()
-    _chk(L.ps_extract_read_names(mapping.encode(), out_file.encode(), C.byref(st)))
-    return {f: int(getattr(st, f)) for f, _ in NamesStats._fields_}
-
-
-class ResidentOpts(C.Structure):
-    _fields_ = [("struct_size", C.c_uint32), ("max_references", C.c_uint32)]
-
-
-class ResidentStats(C.Structure):
-    _fields_ = [("active", C.c_uint32), ("n_references", C.c_uint32)] + \
-               [(k, C.c_uint64) for k in ("n_calls", "n_index_loads", "n_index_reuses", "n_stale_reloads", "n_evictions",
-                                          "n_dropped_after_error", "bytes_index_resident")]
+    return _stats(lib().ps_extract_read_names, NamesStats, mapping.encode(), out_file.encode())
 
 
 def ps_resident_begin(max_references=2):
-    L = lib(); L.ps_resident_begin.argtypes = [C.POINTER(ResidentOpts)]
     o = ResidentOpts(C.sizeof(ResidentOpts), int(max_references))
-    _chk(L.ps_resident_begin(C.byref(o)))
+    _chk(lib().ps_resident_begin(C.byref(o)))
 
 
 def ps_resident_end():
@@ -677,10 +670,7 @@ def ps_resident_end():
 
 def ps_resident_info():
     """ps_resident_stats as a dict; any time: outside a scope active is 0 and the counters are the last scope's"""
-    L = lib(); L.ps_resident_info.argtypes = [C.POINTER(ResidentStats)]
-    st = ResidentStats()
-    _chk(L.ps_resident_info(C.byref(st)))
-    return {f: int(getattr(st, f)) for f, _ in ResidentStats._fields_}
+    return _stats(lib().ps_resident_info, ResidentStats)
 
 
 class resident:

@@ -28,6 +28,20 @@ class ExternalCallErrorException(Exception):
         return self.command
 
 
+def _call(what, fn, *args, **kw):
+    """Mapping.executeCommand's contract (Mapping.java:151-198): non-zero status => abort with the command; else the call's result"""
+    try:
+        return fn(*args, **kw)
+    except capi.PsError as e:
+        raise ExternalCallErrorException("%s: %s" % (what, e))
+
+
+def _index_unless_present(reference):
+    """`bwa index` for a reference whose .bwt is missing (BWAMapping.java:35-45, PARAsuiteMapping.java:45-55)"""
+    if not os.path.exists(reference + ".bwt"):
+        _call("bwa index " + reference, capi.ps_index, reference)
+
+
 class Mapping:
     """abstract mirror of mapping.Mapping (Mapping.java:26-206)"""
 
@@ -49,12 +63,7 @@ class Mapping:
     def calculatePassedTime(self):
         return int(time.time() - self._t0)          # whole seconds, as Mapping.java:203-206
 
-    def _call(self, what, fn, *args):
-        """Mapping.executeCommand's contract (Mapping.java:151-198): non-zero status => abort with the command"""
-        try:
-            fn(*args)
-        except capi.PsError as e:
-            raise ExternalCallErrorException("%s: %s" % (what, e))
+    _call = staticmethod(_call)
 
     def samToFilteredBam(self, outputPrefix, mappingQualityFilter, sortByCoordinateAndIndex=False, threads=8):
         """<prefix>.sam -> <prefix>.bam holding the reads with MAPQ >= filter (PARAsuiteMapping.java:102-152), optionally
@@ -67,8 +76,7 @@ class Mapping:
     def _map_to_bam(self, what, threads, mm, ep, ip, reference, input, outputPrefix, mappingQualityFilter, sortByCoordinateAndIndex):
         """the mapping call and samToFilteredBam fused (`ps_map_to_bam`): <prefix>.bam straight from the alignment records, the 2 GB of
         <prefix>.sam per 10 M reads are never written; BGZF blocks are compressed while later pieces of the input are searched"""
-        if not os.path.exists(reference + ".bwt"):
-            self._call("bwa index " + reference, capi.ps_index, reference)
+        _index_unless_present(reference)
         self.setTimeStart()
         self._call(what + " | samtools view -bS | view -q %d%s" % (mappingQualityFilter, " | sort | index" if sortByCoordinateAndIndex else ""),
                    capi.ps_map_to_bam, threads, mm, ep, ip, reference, input, outputPrefix + ".bam", mappingQualityFilter,
@@ -88,8 +96,7 @@ class BWAMapping(Mapping):
     """first pass with stock penalties: `bwa aln -t T -n <mm>` + `bwa samse` (BWAMapping.java:51-75)"""
 
     def executeMapping(self, threads, reference, input, outputPrefix, mappingQualityFilter, additionalOptions):
-        if not os.path.exists(reference + ".bwt"):                      # BWAMapping.java:35-45
-            self._call("bwa index " + reference, capi.ps_index, reference)
+        _index_unless_present(reference)
         self.setTimeStart()
         self._call("bwa aln -t %d -n %s %s %s | bwa samse" % (threads, additionalOptions, reference, input),
                    capi.ps_map, threads, additionalOptions, None, None, reference, input, outputPrefix + ".sam", self.searchOptions)
@@ -104,8 +111,7 @@ class BWAMapping(Mapping):
         """the first pass of a --refine run and the ErrorProfiling step behind it (Main.java:288-334) as ONE call: the profile of
         the alignments with MAPQ >= mappingQualityFilter is counted from memory while the SAM is written (`ps_map_profiled`);
         returns the two file names Main hands to PARAsuiteMapping (<outputPrefix>.bam.errorprofile / .indelprofile)"""
-        if not os.path.exists(reference + ".bwt"):
-            self._call("bwa index " + reference, capi.ps_index, reference)
+        _index_unless_present(reference)
         self.setTimeStart()
         prefix = outputPrefix + ".bam"                                    # Main.java:335-338: genomicMappingFileName + ".errorprofile"
         self._call("bwa aln -t %d -n %s %s %s | bwa samse | ErrorProfiling" % (threads, additionalOptions, reference, input),
@@ -131,8 +137,7 @@ class PARAsuiteMapping(Mapping):
         self.indelProfileFilename = indelProfileFilename
 
     def executeMapping(self, threads, reference, input, outputPrefix, mappingQualityFilter, additionalOptions):
-        if not os.path.exists(reference + ".bwt"):                      # PARAsuiteMapping.java:45-55
-            self._call("bwa index " + reference, capi.ps_index, reference)
+        _index_unless_present(reference)
         self.setTimeStart()
         if not self.errorProfileFilename:
             raise ExternalCallErrorException("bwa parasuite: no error profile set (-p)")
@@ -166,10 +171,8 @@ class ErrorProfiling:
         self.maxReadLength = maxReadLength
 
     def inferErrorProfile(self, isInferQualities=False, isShowErrorPlot=False):
-        try:
-            capi.ps_error_profile_full(self.mappingFileName, self.referenceFileName, self.maxReadLength, None, bool(isInferQualities))
-        except capi.PsError as e:
-            raise ExternalCallErrorException("ErrorProfiling %s: %s" % (self.mappingFileName, e))
+        _call("ErrorProfiling %s" % self.mappingFileName, capi.ps_error_profile_full, self.mappingFileName, self.referenceFileName,
+              self.maxReadLength, None, bool(isInferQualities))
         return self.mappingFileName + ".errorprofile", self.mappingFileName + ".indelprofile"
 
 
@@ -180,10 +183,8 @@ class PileupClusters:
     the GPU (`ps_pileup_clusters`).  snpVcfFile None or "": no known SNPs; the VCF needs no .tbi.  Returns the stats dict."""
 
     def calculateReadPileups(self, alignmentFile, referenceFile, outputFile, snpVcfFile, minReadCoverage):
-        try:
-            return capi.ps_pileup_clusters(alignmentFile, referenceFile, outputFile, snpVcfFile, int(minReadCoverage))
-        except capi.PsError as e:
-            raise ExternalCallErrorException("PileupClusters %s: %s" % (alignmentFile, e))
+        return _call("PileupClusters %s" % alignmentFile, capi.ps_pileup_clusters, alignmentFile, referenceFile, outputFile, snpVcfFile,
+                     int(minReadCoverage))
 
 
 class ExtractWeakMappingReads:
@@ -193,10 +194,8 @@ class ExtractWeakMappingReads:
     (`ps_extract_weak_reads`, host code).  The caller renames mappingFileNameNew, as Main does.  Returns the stats dict."""
 
     def extractReads(self, mappingFileName, mappingFileNameNew, unalignedReadFileName, mapqThreshold):
-        try:
-            return capi.ps_extract_weak_reads(mappingFileName, mappingFileNameNew, unalignedReadFileName, int(mapqThreshold))
-        except capi.PsError as e:
-            raise ExternalCallErrorException("ExtractWeakMappingReads %s: %s" % (mappingFileName, e))
+        return _call("ExtractWeakMappingReads %s" % mappingFileName, capi.ps_extract_weak_reads, mappingFileName, mappingFileNameNew,
+                     unalignedReadFileName, int(mapqThreshold))
 
 
 class ExtractNotMappedReads:
@@ -205,10 +204,7 @@ class ExtractNotMappedReads:
     the mapping, in file order (`ps_extract_read_names`, host code).  Returns the stats dict."""
 
     def extractReads(self, mappingFileName, alignedReadFileName):
-        try:
-            return capi.ps_extract_read_names(mappingFileName, alignedReadFileName)
-        except capi.PsError as e:
-            raise ExternalCallErrorException("ExtractNotMappedReads %s: %s" % (mappingFileName, e))
+        return _call("ExtractNotMappedReads %s" % mappingFileName, capi.ps_extract_read_names, mappingFileName, alignedReadFileName)
 
 
 class CombineGenomeTranscript:
@@ -219,10 +215,8 @@ class CombineGenomeTranscript:
     index is left to Mapping.sortByCoordinateAndIndex's mirror (`capi.ps_bam_index`).  Returns the stats dict."""
 
     def combine(self, genomeMappingFileName, transcriptMappingFileName, combinedFileName):
-        try:
-            return capi.ps_combine_genome_transcript(genomeMappingFileName, transcriptMappingFileName, combinedFileName, True, False)
-        except capi.PsError as e:
-            raise ExternalCallErrorException("CombineGenomeTranscript %s %s: %s" % (genomeMappingFileName, transcriptMappingFileName, e))
+        return _call("CombineGenomeTranscript %s %s" % (genomeMappingFileName, transcriptMappingFileName), capi.ps_combine_genome_transcript,
+                     genomeMappingFileName, transcriptMappingFileName, combinedFileName, True, False)
 
 
 class ValidateBenchmarkStatisticsPARCLIP:
@@ -233,10 +227,8 @@ class ValidateBenchmarkStatisticsPARCLIP:
     ignored, as the Java ignores it (:120-125).  Returns the stats dict."""
 
     def calculateBenchmarkStatistics(self, mappingFileName, outStatistics, readsFile, onlyBoundClusters=False):
-        try:
-            return capi.ps_benchmark_reads(mappingFileName, outStatistics, readsFile)
-        except capi.PsError as e:
-            raise ExternalCallErrorException("ValidateBenchmarkStatisticsPARCLIP %s %s: %s" % (mappingFileName, readsFile, e))
+        return _call("ValidateBenchmarkStatisticsPARCLIP %s %s" % (mappingFileName, readsFile), capi.ps_benchmark_reads, mappingFileName,
+                     outStatistics, readsFile)
 
 
 class Main:
@@ -263,12 +255,10 @@ class Main:
         kw = dict(transcripts_fa=transcriptFileName, threads=threads, refine=refine, max_read_len=maxReadLength,
                   mapq_genomic=mappingQualityFilterGenomic, mapq_transcript=mappingQualityFilterTranscript,
                   bwa_mm=bwaMismatches, parasuite_mm=parasuiteMismatches, error_profile=profileFileName, indel_profile=indelFileName)
-        try:
-            if keepUnaligned or referenceRefineFileName or search is not None:
-                self.stats = capi.ps_map_route_opts(readFileName, referenceFileName, outputPrefix, keep_unaligned=keepUnaligned,
-                                                    ref_refine=referenceRefineFileName, search=search, **kw)
-            else:
-                self.stats = capi.ps_map_route(readFileName, referenceFileName, outputPrefix, **kw)
-        except capi.PsError as e:
-            raise ExternalCallErrorException("map -q %s -r %s -o %s: %s" % (readFileName, referenceFileName, outputPrefix, e))
+        route = capi.ps_map_route
+        if keepUnaligned or referenceRefineFileName or search is not None:
+            route = capi.ps_map_route_opts
+            kw.update(keep_unaligned=keepUnaligned, ref_refine=referenceRefineFileName, search=search)
+        self.stats = _call("map -q %s -r %s -o %s" % (readFileName, referenceFileName, outputPrefix), route, readFileName, referenceFileName,
+                           outputPrefix, **kw)
         return self.mappingFileName(outputPrefix, transcriptFileName, refine)

@@ -3,13 +3,12 @@ mapper, pinned to its own answers; the struct's size rule, the refusals made bef
 import ctypes as C
 import os
 import shutil
-import subprocess
 
 import pytest
 
 import map_route as M
 import map_route_flags as F
-from test_capi_cpu import ROOT, _no_gpu
+from test_capi_cpu import _no_gpu
 
 
 class CopyingOrc(M.OrcMapper):
@@ -117,19 +116,6 @@ def test_ref_refine_same_genome_other_file(data, tmp_path):
 
 
 # ---- the struct and the refusals ----------------------------------------------------------------------------------------------
-def test_struct_matches_the_header(tmp_path):
-    import capi
-    src = tmp_path / "sizes.c"
-    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "parasuite_hip.h"\nint main(void) { printf("%zu %zu %zu %zu %zu\\n", sizeof(ps_route_opts2), '
-                   'offsetof(ps_route_opts2, reads_fq), offsetof(ps_route_opts2, ref_refine), offsetof(ps_route_opts2, search), offsetof(ps_route_opts2, keep_unaligned)); return 0; }\n')
-    exe = str(tmp_path / "sizes")
-    subprocess.check_call([os.environ.get("CC", "cc"), "-I", os.path.join(ROOT, "include"), str(src), "-o", exe])
-    size, reads, rr, search, keep = (int(x) for x in subprocess.check_output([exe]).split())
-    R = capi.RouteOpts2
-    assert (C.sizeof(R), R.reads_fq.offset, R.ref_refine.offset, R.search.offset, R.keep_unaligned.offset) == (size, reads, rr, search, keep)
-    assert (size, reads, rr) == (112, 24, 88) and capi.ROUTE_OPTS_OLD_SIZE == 88 and R.struct_size.offset == 0
-
-
 def _inputs(d):
     fq, fa, ep = (os.path.join(d, x) for x in ("r.fq", "g.fa", "x.errorprofile"))
     open(fq, "w").write("@r\nACGT\n+\nIIII\n")

@@ -104,15 +104,12 @@ def test_begin_and_end_error_cases(closed_scope):
     for ok in (1, 8):
         capi.ps_resident_begin(ok)
         capi.ps_resident_end()
-    L.ps_resident_info.argtypes = [C.POINTER(capi.ResidentStats)]
     assert L.ps_resident_info(None) == 1 and L.ps_last_error()
 
 
 def test_struct_size(closed_scope):
     capi = closed_scope
     L = capi.lib()
-    assert C.sizeof(capi.ResidentOpts) == 8 and C.sizeof(capi.ResidentStats) == 8 + 7 * 8
-    L.ps_resident_begin.argtypes = [C.POINTER(capi.ResidentOpts)]
     o = capi.ResidentOpts(4, 99)                                       # a caller whose struct ends before max_references: the default, 99 is not read
     assert L.ps_resident_begin(C.byref(o)) == 0 and L.ps_resident_end() == 0
     for bad in (0, 2, 6, 12, 64):                                      # no multiple of 4, or longer than this library knows

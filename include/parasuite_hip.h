@@ -133,6 +133,14 @@ int     ps_ctx_set_stats(ps_ctx *, int on);
 /* lanes of work (stream + workspace) the batches created afterwards take in turn: 1 (default) or 2 -- two batches on two lanes may
  * be driven from two threads at once, one's selection / SA walk / DP stages then run under the other's search kernel */
 int     ps_ctx_set_lanes(ps_ctx *, int n);
+/* collapsed search: the identical reads of a batch (same bases, same N positions, same length; a read and its reverse complement
+ * are different reads) are searched once and the result is copied to the others -- what a pipeline runs a collapsing tool in front
+ * of the mapper for.  Every output (hit lists, hits, SAM) stays byte for byte what it is without: names, qualities and the
+ * tie-break stream come after the search, in input order.  mode -1 (default): as the environment says when the batch is searched
+ * (PS_COLLAPSE=1: on; unset: off), 0 off, 1 on.  Off, no kernel and no buffer of the feature is used.  Declined (searched as if
+ * off) under PS_READ_ITERS, whose per-read profile is in launch order.  With ps_ctx_set_stats on, the counters count what ran:
+ * the searches of the representatives, not of every read. */
+int     ps_ctx_set_collapse(ps_ctx *, int mode);
 
 typedef struct {                       /* index geometry + build facts */
     uint64_t seq_len, l_pac, primary, L2[5], n_blocks, n_sa, device_bytes;
@@ -182,6 +190,22 @@ int     ps_batch_hits(ps_batch *, ps_hit *out, int64_t cap);
 int     ps_batch_timing(ps_batch *, ps_timing *out);
 int64_t ps_ctx_read_iters(ps_ctx *, uint32_t *out, int64_t cap);   /* profiling aid (env PS_READ_ITERS=1): per read of the last search launch 20 words -- iterations | stack slots used | lower bounds as fetched (read, seed << 8) and the effort estimate's two scans (<< 16, << 24) | best score, final budget << 8, hits << 16 | 16 words of D bounds -- in the order the launch held the reads (leading-base order of the bin, not input order); returns the word count */
 int     ps_batch_kstats(ps_batch *, int which /*0 width 1 backtrack 2 sa2pos*/, ps_kstats *out);
+/* what the collapsed search (ps_ctx_set_collapse) found and saved, after ps_batch_search.  The groups are EXACT: two reads share a
+ * group only after all their packed words and their length have compared equal, never on a hash alone.  They may be INCOMPLETE in
+ * one rare case: identical reads are found as neighbours in an order sorted by a 64-bit key, and where reads of equal key and
+ * different sequence interleave there, identical reads end up in two groups -- that costs a search, never a wrong result.
+ * Searched with collapse off: n_searched == n_reads and the rest 0. */
+typedef struct {
+    int64_t n_reads, n_searched;            /* first tier, all bins: reads, and reads that were actually searched */
+    int64_t n_groups, n_multi, largest;     /* groups, groups with more than one read, reads in the largest group */
+    int64_t n_overflow_reads, n_overflow_searched;   /* larger tiers, summed: reads that needed one, reads searched there */
+    int32_t n_bins, n_bins_collapsed;       /* bins of the batch, bins where a duplicate was found */
+    double  ms_collapse;                    /* key, sort, heads, gather and expand kernels, all bins */
+} ps_collapse_info;
+int     ps_batch_collapse_info(ps_batch *, ps_collapse_info *out);
+/* the groups, in input order: out[g] = input index of the representative of g's group (a representative names itself), for the
+ * first min(cap, n) reads; an error if the batch was not searched or was searched with collapse off */
+int     ps_batch_duplicate_of(ps_batch *, int64_t *out, int64_t cap);
 /* host-only check of the read parser: whole file on `threads` threads (chunk_bytes 0) or streamed in windows of chunk_bytes as
  * ps_map does; out = {reads, bases, order-sensitive hash of names / sequences / qualities, pieces}.  reads_path: plain, gzip or
  * BGZF as for ps_map, with the same two deviations (a truncated member and trailing bytes are errors); for a compressed input

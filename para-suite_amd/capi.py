@@ -65,6 +65,11 @@ class KStats(C.Structure):
     _fields_ = _fields(C.c_uint64, "occ_pairs", "occ_same_blk", "nodes", "pushes", "pops", "lf_steps", "iters", "exact_steps")
 
 
+class CollapseInfo(C.Structure):
+    _fields_ = _fields(C.c_int64, "n_reads", "n_searched", "n_groups", "n_multi", "largest", "n_overflow_reads", "n_overflow_searched") + \
+               _fields(C.c_int32, "n_bins", "n_bins_collapsed") + [("ms_collapse", C.c_double)]
+
+
 class BamStats(C.Structure):
     _fields_ = _fields(C.c_uint64, "n_in", "n_out", "bam_bytes")
 
@@ -157,7 +162,7 @@ class FetchStats(C.Structure):
 
 # every struct typedef of the header -> its mirror (ps_aln and ps_hit are read as numpy records)
 STRUCTS = {"ps_search_opts": SearchOpts, "ps_index_info": IndexInfo, "ps_aln": ALN_DTYPE, "ps_hit": HIT_DTYPE, "ps_timing": Timing,
-           "ps_kstats": KStats, "ps_bam_stats": BamStats, "ps_profile_stats": ProfileStats, "ps_cluster_stats": ClusterStats,
+           "ps_kstats": KStats, "ps_collapse_info": CollapseInfo, "ps_bam_stats": BamStats, "ps_profile_stats": ProfileStats, "ps_cluster_stats": ClusterStats,
            "ps_extract_stats": ExtractStats, "ps_names_stats": NamesStats, "ps_combine_stats": CombineStats,
            "ps_route_opts": RouteOpts, "ps_route_stats": RouteStats, "ps_route_opts2": RouteOpts2, "ps_resident_opts": ResidentOpts,
            "ps_resident_stats": ResidentStats, "ps_benchmark_stats": BenchmarkStats, "ps_simulate_opts": SimulateOpts,
@@ -187,6 +192,7 @@ SIGNATURES = {
     "ps_ctx_set_tiers": (_I, [_PTR, _P(C.c_uint32), _P(C.c_int32), _I]),
     "ps_ctx_set_stats": (_I, [_PTR, _I]),
     "ps_ctx_set_lanes": (_I, [_PTR, _I]),
+    "ps_ctx_set_collapse": (_I, [_PTR, _I]),
     "ps_ctx_info": (_I, [_PTR, _P(IndexInfo)]),
     "ps_ctx_blob": (_I, [_PTR, _I, _P(_PTR), _P(_U64)]),
     "ps_ctx_meta": (_I64, [_PTR, _S, _I64]),
@@ -212,6 +218,8 @@ SIGNATURES = {
     "ps_batch_timing": (_I, [_PTR, _P(Timing)]),
     "ps_ctx_read_iters": (_I64, [_PTR, _PTR, _I64]),
     "ps_batch_kstats": (_I, [_PTR, _I, _P(KStats)]),
+    "ps_batch_collapse_info": (_I, [_PTR, _P(CollapseInfo)]),
+    "ps_batch_duplicate_of": (_I, [_PTR, _PTR, _I64]),
     "ps_release_host_cache": (None, []),
     "ps_parse_check": (_I, [_S, _I, _U64, _P(_U64)]),
     "ps_sam_to_bam": (_I, [_S, _S, _I, _I, _I, _I, _P(BamStats)]),
@@ -352,6 +360,11 @@ class Ctx:
     def set_lanes(self, n):
         """batches created afterwards take n (1 or 2) lanes of work in turn; two batches on two lanes may run from two threads"""
         _chk(lib().ps_ctx_set_lanes(self.h, int(n)))
+
+    def set_collapse(self, mode=1):
+        """identical reads of a batch are searched once and the result copied to the others; every output stays what it is
+        without.  1 on, 0 off, -1 (the default of a context): as PS_COLLAPSE says when the batch is searched"""
+        _chk(lib().ps_ctx_set_collapse(self.h, int(mode)))
 
     def info(self):
         i = IndexInfo()
@@ -507,6 +520,18 @@ class Batch:
 
     def kstats(self, which):
         return _stats(lib().ps_batch_kstats, KStats, self.h, which)
+
+    def collapse_info(self):
+        """ps_collapse_info of the last search as a dict: reads, reads searched, groups ... (collapse off: n_searched == n_reads)"""
+        return _stats(lib().ps_batch_collapse_info, CollapseInfo, self.h)
+
+    def duplicate_of(self):
+        """input order: the input index of the representative of every read's group (a representative names itself).  The groups
+        are exact -- compared in full, never by hash -- and in one rare case incomplete: identical reads may stand in two groups
+        (include/parasuite_hip.h).  An error if the batch was searched with collapse off"""
+        out = np.zeros(self.n, dtype=np.int64)
+        _chk(lib().ps_batch_duplicate_of(self.h, out.ctypes.data, out.size))
+        return out
 
 
 def ps_parse_check(path, threads=1, chunk_bytes=0):

@@ -356,6 +356,33 @@ int ps_batch_kstats(ps_batch *b, int which, ps_kstats *o)
         o->lf_steps = k.lf_steps; o->iters = k.iters; o->exact_steps = k.exact_steps; return 0;
     PS_CATCH_INT
 }
+int ps_ctx_set_collapse(ps_ctx *x, int mode)
+{
+    PS_TRY
+        if (mode < -1 || mode > 1) throw Error("collapse: -1 (as PS_COLLAPSE says), 0 (off) or 1 (on)");
+        x->c.collapse_mode = mode; return 0;
+    PS_CATCH_INT
+}
+int ps_batch_collapse_info(ps_batch *b, ps_collapse_info *o)
+{
+    PS_TRY
+        if (!b->b->collapse_known) throw Error("collapse info: the batch has not been searched");
+        *o = b->b->collapse; return 0;
+    PS_CATCH_INT
+}
+int ps_batch_duplicate_of(ps_batch *b, int64_t *out, int64_t cap)
+{
+    PS_TRY
+        const Batch &B = *b->b;
+        if (!B.collapse_known) throw Error("duplicate_of: the batch has not been searched");
+        if (!B.collapse_on) throw Error("duplicate_of: the batch was searched with collapse off");
+        for (int64_t g = 0; g < B.rs.n && g < cap; ++g) {
+            const Bin &bin = B.bins[(size_t)B.read_bin[g]];
+            out[g] = bin.h_rep_of.empty() ? g : (int64_t)bin.ids[(size_t)bin.h_rep_of[(size_t)B.read_local[g]]];
+        }
+        return 0;
+    PS_CATCH_INT
+}
 
 // The whole `map` step behind one call: the streaming pass and the route are ps_map.hip's.
 int ps_map(int threads, const char *mm, const char *error_profile, const char *indel_profile,

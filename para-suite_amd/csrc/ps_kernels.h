@@ -82,4 +82,23 @@ size_t order_sort_tmp_words(int n);
 void launch_order_sort(const uint8_t *key, int n, uint32_t *tmp, int32_t *order, hipStream_t s);
 void launch_class_ranks(const uint8_t *cls, long long n, const uint32_t *grp, uint32_t *e_before, uint32_t *h_before, hipStream_t s);
 
+// ps_collapse.hip: the groups of identical reads of a bin (ps_collapse.h has the rule).  In: the bin's packed reads.  Scratch, all on the
+// device: key, perm[2], order, rep_of, slot, reps: n elements each; digit: n bytes; sort_tmp: order_sort_tmp_words(n) words; part:
+// 2 * PS_SORT_MAX_WG words; m: one word.  Out: rep_of[read] = its group's representative (a representative names itself), reps[q] = the
+// q-th representative in bin order, slot[representative] = q, *m = their number
+struct CollapseArgs {
+    int n, n_bw, n_mw, len, hash_bits;
+    const int32_t *lens;     // per-read lengths (nullptr: all len)
+    const uint32_t *bases; const uint32_t *nmask;
+    uint64_t *key; int32_t *perm[2]; uint8_t *digit; int32_t *order; uint32_t *sort_tmp; uint32_t *part;
+    int32_t *rep_of, *slot, *reps; uint32_t *m;
+};
+int collapse_sort_passes(int hash_bits);                      // LSD passes over the key's bytes
+void launch_collapse_groups(const CollapseArgs &a, hipStream_t s);
+// the representatives' words and lengths, word-major with stride m (out_lens: only read when a.lens is set)
+void launch_collapse_gather(const CollapseArgs &a, int m, uint32_t *out_bases, uint32_t *out_nmask, int32_t *out_lens, hipStream_t s);
+// every read's hit list, count and state from its representative's (t_*: the search's output over the m representatives, stride aln_cap)
+void launch_collapse_expand(const CollapseArgs &a, int m, const AlnRec *t_alns, const int32_t *t_n_aln, const uint8_t *t_status, int aln_cap,
+                            AlnRec *alns, int32_t *n_aln, uint8_t *status, hipStream_t s);
+
 }  // namespace ps

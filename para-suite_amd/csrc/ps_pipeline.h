@@ -85,6 +85,7 @@ struct Ctx : OptionParts {          // opt, search: the options in their two par
     int n_big = 4096;              // 1 MB stack slots a launch may hand to reads that outgrow their private slice
     int fetch_min = 8, hit_min = 1;    // batching hits costs more in idle lanes than it saves (measured)
     int host_threads = 8;
+    int collapse_mode = -1;        // identical reads of a bin searched once (ps_collapse.h): -1 as PS_COLLAPSE says at search time, 0 off, 1 on
     static const int N_WORK = 4;
     std::unique_ptr<Work> work[N_WORK];
     int n_work = 1, next_work = 0; // lanes in use (1: every batch shares one workspace and stream); batches take them in turn
@@ -119,6 +120,7 @@ struct Bin {
     std::vector<int32_t> h_n_aln; std::vector<uint32_t> h_off; std::vector<AlnRec> h_alns;
     std::map<int32_t, std::vector<AlnRec>> overflow;                                          // reads that needed a larger tier
     int n_bw = 0, n_mw = 0;
+    std::vector<int32_t> h_rep_of;            // collapsed search: bin-local read -> its group's representative; empty: every read stands for itself
 };
 
 struct Batch {
@@ -141,6 +143,7 @@ struct Batch {
     DevBuf<KStats> d_stats; KStats st_width{}, st_backtrack{}, st_sa2pos{};
     Timing tm;
     int64_t n_overflow[3] = {0, 0, 0};
+    bool collapse_known = false, collapse_on = false; ps_collapse_info collapse{};   // the last search: identical reads searched once, and what that saved
     bool searched = false, selected_hard = false, selected = false, located = false;
     const AlnRec *alns_of(int64_t g, int &n);      // downloads the hit lists on first use
     void ensure_host_alns();

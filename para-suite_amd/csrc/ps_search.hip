@@ -234,16 +234,82 @@ void reserve_search_workspace(Ctx *ctx, int work_index)
     }
 }
 
+// The first tier of a bin with its identical reads searched once (ps_collapse.h, ps_collapse.hip): the groups on the device, one
+// representative per group through run_search() as it stands, the result copied to every read of the group -- from there on
+// the status download, k_classify, the hit-list downloads and the samse stage see what they would have seen.  false: the bin has
+// no duplicate (m == n) and is to be searched in place; nothing was gathered.  All scratch is the lane's (a fresh hipMalloc
+// synchronises the device: reserve_search_workspace).
+static bool search_bin_collapsed(Batch &b, const SearchKnobs &kn, Bin &bin)
+{
+    Ctx *ctx = b.ctx; Work *wk = b.wk; hipStream_t s = wk->stream;
+    const int n = (int)bin.ids.size();
+    ps_collapse_info &ci = b.collapse;
+    ci.n_reads += n; ++ci.n_bins;
+    if (n < 2) { ci.n_searched += n; ci.n_groups += n; ci.largest = std::max<int64_t>(ci.largest, n); return false; }
+    CollapseArgs ca;
+    ca.n = n; ca.n_bw = bin.n_bw; ca.n_mw = bin.n_mw; ca.len = bin.len; ca.hash_bits = kn.collapse_hash_bits;
+    ca.lens = bin.ragged ? bin.d_lens.p : nullptr; ca.bases = bin.bases.p; ca.nmask = bin.nmask.p;
+    ca.key = wk->ws_get<uint64_t>("cl_key", (size_t)n);
+    ca.perm[0] = wk->ws_get<int32_t>("cl_perm0", (size_t)n); ca.perm[1] = wk->ws_get<int32_t>("cl_perm1", (size_t)n);
+    ca.digit = wk->ws_get<uint8_t>("cl_digit", (size_t)n); ca.order = wk->ws_get<int32_t>("cl_order", (size_t)n);
+    ca.sort_tmp = wk->ws_get<uint32_t>("cl_sort_tmp", order_sort_tmp_words(n));
+    ca.part = wk->ws_get<uint32_t>("cl_part", (size_t)2 * PS_SORT_MAX_WG + 1); ca.m = ca.part + 2 * PS_SORT_MAX_WG;
+    ca.rep_of = wk->ws_get<int32_t>("cl_rep_of", (size_t)n); ca.slot = wk->ws_get<int32_t>("cl_slot", (size_t)n); ca.reps = wk->ws_get<int32_t>("cl_reps", (size_t)n);
+    uint32_t *h_m = wk->pin_get<uint32_t>("cl_m", 1);
+    EventPair t_groups(s);
+    launch_collapse_groups(ca, s);
+    PS_HIP(hipGetLastError());
+    t_groups.stop(s);
+    PS_HIP(hipMemcpyAsync(h_m, ca.m, 4, hipMemcpyDeviceToHost, s));
+    PS_HIP(hipStreamSynchronize(s));
+    ci.ms_collapse += t_groups.ms();
+    const int m = (int)*h_m;
+    if (m < 1 || m > n) throw Error("internal: collapsed search counted more groups than reads");
+    ci.n_searched += m; ci.n_groups += m;
+    if (m == n) { ci.largest = std::max<int64_t>(ci.largest, 1); return false; }
+    ++ci.n_bins_collapsed;
+    uint32_t *g_bases = wk->ws_get<uint32_t>("cl_bases", (size_t)bin.n_bw * m), *g_nmask = wk->ws_get<uint32_t>("cl_nmask", (size_t)bin.n_mw * m);
+    int32_t *g_lens = bin.ragged ? wk->ws_get<int32_t>("cl_lens", (size_t)m) : nullptr;
+    AlnRec *t_alns = wk->ws_get<AlnRec>("cl_alns", (size_t)m * bin.aln_cap);
+    int32_t *t_n_aln = wk->ws_get<int32_t>("cl_n_aln", (size_t)m); uint8_t *t_status = wk->ws_get<uint8_t>("cl_status", (size_t)m);
+    EventPair t_gather(s);
+    launch_collapse_gather(ca, m, g_bases, g_nmask, g_lens, s);
+    PS_HIP(hipGetLastError());
+    t_gather.stop(s);
+    bin.h_rep_of.resize((size_t)n);
+    PS_HIP(hipMemcpyAsync(bin.h_rep_of.data(), ca.rep_of, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+    run_search(b, kn, bin.md, m, g_bases, g_nmask, g_lens, ctx->pool_cap[0], bin.aln_cap, t_alns, t_n_aln, t_status, true);
+    EventPair t_expand(s);
+    launch_collapse_expand(ca, m, t_alns, t_n_aln, t_status, bin.aln_cap, bin.d_alns.p, bin.d_n_aln.p, bin.d_status.p, s);
+    PS_HIP(hipGetLastError());
+    t_expand.stop(s);
+    ci.ms_collapse += t_gather.ms() + t_expand.ms();                 // waits for the expansion, and with it for the download of rep_of
+    std::vector<int32_t> size((size_t)n, 0);
+    for (int r = 0; r < n; ++r) {
+        const int32_t rep = bin.h_rep_of[(size_t)r];
+        if (rep < 0 || rep >= n || bin.h_rep_of[(size_t)rep] != rep) throw Error("internal: collapsed search left a read without a representative");
+        ++size[(size_t)rep];
+    }
+    for (int r = 0; r < n; ++r) { ci.n_multi += size[(size_t)r] > 1; ci.largest = std::max<int64_t>(ci.largest, size[(size_t)r]); }
+    return true;
+}
+
 // step 1 of batch_search, per bin: the first tier, then the larger tiers for the reads it could not hold (their hit lists go to bin.overflow)
 static void search_bin(Batch &b, const SearchKnobs &kn, Bin &bin)
 {
     Ctx *ctx = b.ctx; Work *wk = b.wk; hipStream_t s = wk->stream;
     const int n = (int)bin.ids.size();
-    bin.host_alns_valid = false;
+    bin.host_alns_valid = false; bin.h_rep_of.clear();
     const int cap1 = (bin.len <= 40 && ctx->aln_cap_short > ctx->aln_cap[0]) ? ctx->aln_cap_short : ctx->aln_cap[0];
     if (bin.d_alns.n < (size_t)n * cap1 || bin.aln_cap != cap1) { bin.d_alns.alloc((size_t)n * cap1); bin.d_n_aln.alloc(n); bin.d_status.alloc(n); }
     bin.aln_cap = cap1;
-    run_search(b, kn, bin.md, n, bin.bases.p, bin.nmask.p, bin.ragged ? bin.d_lens.p : nullptr, ctx->pool_cap[0], bin.aln_cap, bin.d_alns.p, bin.d_n_aln.p, bin.d_status.p, true);
+    if (!b.collapse_on || !search_bin_collapsed(b, kn, bin))
+        run_search(b, kn, bin.md, n, bin.bases.p, bin.nmask.p, bin.ragged ? bin.d_lens.p : nullptr, ctx->pool_cap[0], bin.aln_cap, bin.d_alns.p, bin.d_n_aln.p, bin.d_status.p, true);
+    // collapsed: the larger tiers search the representatives alone -- a read whose search overflowed is the dearest kind, and all its
+    // duplicates overflow with it -- and a group's members take the representative's list afterwards; size[rep]: reads it stands for
+    const std::vector<int32_t> &rep_of = bin.h_rep_of;
+    std::vector<int32_t> size;
+    if (!rep_of.empty()) { size.assign((size_t)n, 0); for (int r = 0; r < n; ++r) ++size[(size_t)rep_of[(size_t)r]]; }
     uint8_t *h_status = wk->pin_get<uint8_t>("status", n);
     PS_HIP(hipMemcpyAsync(h_status, bin.d_status.p, (size_t)n, hipMemcpyDeviceToHost, s));
     hipLaunchKernelGGL(k_classify, dim3(std::min((n + 255) / 256, 4096)), dim3(256), 0, s, bin.d_alns.p, bin.aln_cap, bin.d_n_aln.p, bin.d_status.p,
@@ -256,13 +322,16 @@ static void search_bin(Batch &b, const SearchKnobs &kn, Bin &bin)
     std::vector<int32_t> todo, deep;
     for (int r = 0; r < n; ++r) {
         if (h_status[r] == RS_BAD_SCORE) throw Error("internal: score outside the bucket range");
-        if (h_status[r] != RS_OK) (h_status[r] == RS_OVERFLOW_DEEP ? deep : todo).push_back(r);
+        if (h_status[r] != RS_OK && (rep_of.empty() || rep_of[(size_t)r] == r)) (h_status[r] == RS_OVERFLOW_DEEP ? deep : todo).push_back(r);
     }
     for (int tier = 1; tier < 3; ++tier) {
         if (tier == 2) { todo.insert(todo.end(), deep.begin(), deep.end()); std::sort(todo.begin(), todo.end()); deep.clear(); }
         if (todo.empty()) continue;
-        b.n_overflow[tier] += (int64_t)todo.size();
         const int m = (int)todo.size();
+        int64_t stood_for = m;                                      // the counter keeps counting reads
+        if (!size.empty()) { stood_for = 0; for (int32_t r : todo) stood_for += size[(size_t)r]; }
+        b.n_overflow[tier] += stood_for;
+        if (b.collapse_on) { b.collapse.n_overflow_reads += stood_for; b.collapse.n_overflow_searched += m; }
         std::vector<uint32_t> hb((size_t)bin.n_bw * m), hm((size_t)bin.n_mw * m);
         for (int q = 0; q < m; ++q) {
             for (int wv = 0; wv < bin.n_bw; ++wv) hb[(size_t)wv * m + q] = bin.h_bases[(size_t)wv * n + todo[q]];
@@ -287,6 +356,9 @@ static void search_bin(Batch &b, const SearchKnobs &kn, Bin &bin)
         todo.swap(still);
     }
     if (!todo.empty()) throw Error("a read exceeded the largest search tier (stack or hit capacity)");
+    if (!rep_of.empty() && !bin.overflow.empty())
+        for (int r = 0; r < n; ++r)
+            if (rep_of[(size_t)r] != r) { auto it = bin.overflow.find(rep_of[(size_t)r]); if (it != bin.overflow.end()) bin.overflow[r] = it->second; }
 }
 
 // step 2: the classes on the host (larger-tier reads: from their host-side hit list), the number of class-1 / class-2 reads in front
@@ -382,6 +454,9 @@ void batch_search(Batch &b)
     auto t0 = HostClock::now();
     b.d_stats.zero(s);
     for (int t = 0; t < 3; ++t) b.n_overflow[t] = 0;
+    // identical reads searched once: the context's word, else the environment's; not with the per-read profile, which is in launch order
+    b.collapse_on = (ctx->collapse_mode < 0 ? kn.collapse : ctx->collapse_mode > 0) && !ctx->want_read_iters;
+    b.collapse = ps_collapse_info();
     if (b.d_class.n < (size_t)b.rs.n) b.d_class.alloc((size_t)b.rs.n);
     for (Bin &bin : b.bins) search_bin(b, kn, bin);
     KStats hs[3];
@@ -392,6 +467,11 @@ void batch_search(Batch &b)
     b.st_width = hs[0]; b.st_backtrack = hs[1];                  // behind the wait in classes_and_counts: the download above is asynchronous
     gather_sub_alns(b);
     b.tm.ms_classify = ms_since(tcl);
+    if (!b.collapse_on) b.collapse.n_reads = b.collapse.n_searched = b.rs.n;
+    b.collapse_known = true;
+    if (b.collapse_on && std::getenv("PS_VERBOSE"))
+        std::fprintf(stderr, "[parasuite-hip]   collapsed search: %lld reads, %lld searched, %lld groups, largest %lld, %.2f ms\n", (long long)b.collapse.n_reads,
+                     (long long)b.collapse.n_searched, (long long)b.collapse.n_groups, (long long)b.collapse.largest, b.collapse.ms_collapse);
     b.searched = true; b.selected_hard = b.selected = b.located = false;
     b.tm.ms_total = ms_since(t0);
 }

@@ -22,6 +22,8 @@ struct SearchKnobs {
     int chase_min2 = PS_CHASE_MIN2;     // lanes of a wave that must want the second chase step of an iteration (65: never)
     bool chase = true;                  // ... and below them a barren step takes its match child's step in the same iteration (ps_narrow.h: nt_chase)
     int fetch_min = 8, hit_min = 1;     // tuning: the context's values unless set at search time
+    bool collapse = false;              // identical reads of a bin are searched once (ps_collapse.h); a context may state its own (ps_ctx_set_collapse)
+    int collapse_hash_bits = 64;        // tests: bits of the grouping key that are kept, so that different reads share a key
 };
 inline SearchKnobs search_knobs_from_env(int ctx_fetch_min, int ctx_hit_min)
 {
@@ -41,6 +43,8 @@ inline SearchKnobs search_knobs_from_env(int ctx_fetch_min, int ctx_hit_min)
     if (env_int("PS_CHASE_MIN2", v)) k.chase_min2 = std::max(1, std::min(65, v));
     if (env_int("PS_FETCH_MIN", v)) k.fetch_min = std::max(1, v);
     if (env_int("PS_HIT_MIN", v)) k.hit_min = std::max(1, v);
+    if (env_int("PS_COLLAPSE", v)) k.collapse = v != 0;
+    if (env_int("PS_COLLAPSE_HASH_BITS", v)) k.collapse_hash_bits = std::max(1, std::min(64, v));
     return k;
 }
 

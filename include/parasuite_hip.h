@@ -668,6 +668,28 @@ typedef struct {
 } ps_fetch_stats;
 int     ps_fetch_sequences(const char *ref_fa, const char *sites, const char *out_file, int bed, ps_fetch_stats *stats /* may be NULL */);
 
+/* ---- BGZF compression on the device -------------------------------------------------------------------------------
+ * Every BAM the library writes is a sequence of BGZF blocks: gzip members of at most 0xff00 input bytes, each its own DEFLATE
+ * stream with its own CRC32.  By default they are compressed with zlib on host threads.  The device switch: -1 (the default)
+ * is host zlib; device >= 0 means that every BAM this process writes from now on -- the sam_to_bam, bam_view, bam_sort,
+ * map_to_bam, extract_weak_reads, combine_genome_transcript and map_route calls, all through one function of the library --
+ * is compressed on that device, one workgroup per block (csrc/ps_deflate.h: LZ77 with one candidate per hash, then stored,
+ * fixed or dynamic Huffman by exact bit count).  The files are ordinary BAMs; block cuts, member headers, the end-of-file
+ * block and the .bai arithmetic are the same, only the deflate payloads and their lengths differ from zlib's.  Returns
+ * non-zero with the last error set when there is no such device.  A later HIP failure fails the writing call: there is no
+ * fallback to zlib.  PS_BGZF_GPU=<device> in the environment is the same as the call; it is read once, when the library is
+ * loaded, so the bwa, samtools and parasuite programs take it too.  PS_BAM_LEVEL means nothing on the device path (there is
+ * one effort level).  PS_BGZF_PIECE: input bytes per launch (default 64 MiB, at least one block).
+ * PS_BGZF_BTYPE=stored|fixed|dynamic restricts the encodings (tests; a block that would grow is stored all the same). */
+int     ps_bgzf_device(int device);
+/* src[0, n) cut at 0xff00 bytes as the file writers cut it -> the BGZF members in dst, without an end-of-file block, compressed
+ * on `device` whatever the switch says; device -1: by the library's host path instead (zlib at PS_BAM_LEVEL, default 1, on 16
+ * threads; n_stored / n_fixed / n_dynamic then count each member's first DEFLATE block, kernel_ms is 0) -- the reference that
+ * tools/bgzf_time.py times the device against.  n == 0 writes nothing.  When the members need more than cap bytes the call fails and
+ * writes nothing.  stats->struct_size must hold sizeof(ps_bgzf_stats); out_bytes is what was written; kernel_ms the kernels alone. */
+typedef struct { uint32_t struct_size, n_blocks, n_stored, n_fixed, n_dynamic, pad_; uint64_t in_bytes, out_bytes; double kernel_ms; } ps_bgzf_stats;
+int     ps_bgzf_compress(const void *src, uint64_t n, int device, void *dst, uint64_t cap, ps_bgzf_stats *stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

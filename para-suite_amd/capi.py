@@ -160,13 +160,18 @@ class FetchStats(C.Structure):
                _fields(C.c_double, "s_total", "s_read", "s_index", "s_kernels", "s_write")
 
 
+class BgzfStats(C.Structure):
+    _fields_ = _fields(C.c_uint32, "struct_size", "n_blocks", "n_stored", "n_fixed", "n_dynamic", "pad_") + \
+               _fields(C.c_uint64, "in_bytes", "out_bytes") + [("kernel_ms", C.c_double)]
+
+
 # every struct typedef of the header -> its mirror (ps_aln and ps_hit are read as numpy records)
 STRUCTS = {"ps_search_opts": SearchOpts, "ps_index_info": IndexInfo, "ps_aln": ALN_DTYPE, "ps_hit": HIT_DTYPE, "ps_timing": Timing,
            "ps_kstats": KStats, "ps_collapse_info": CollapseInfo, "ps_bam_stats": BamStats, "ps_profile_stats": ProfileStats, "ps_cluster_stats": ClusterStats,
            "ps_extract_stats": ExtractStats, "ps_names_stats": NamesStats, "ps_combine_stats": CombineStats,
            "ps_route_opts": RouteOpts, "ps_route_stats": RouteStats, "ps_route_opts2": RouteOpts2, "ps_resident_opts": ResidentOpts,
            "ps_resident_stats": ResidentStats, "ps_benchmark_stats": BenchmarkStats, "ps_simulate_opts": SimulateOpts,
-           "ps_simulate_stats": SimulateStats, "ps_fetch_stats": FetchStats}
+           "ps_simulate_stats": SimulateStats, "ps_fetch_stats": FetchStats, "ps_bgzf_stats": BgzfStats}
 
 # ---- the functions of the header, in its order: name -> (restype, argtypes) ----
 # int, int64_t, uint64_t, double, const char *; _PTR: ps_ctx *, ps_batch * and every buffer handed over as an address
@@ -242,6 +247,8 @@ SIGNATURES = {
     "ps_benchmark_reads": (_I, [_S, _S, _S, _P(BenchmarkStats)]),
     "ps_simulate_reads": (_I, [_P(SimulateOpts), _P(SimulateStats)]),
     "ps_fetch_sequences": (_I, [_S, _S, _S, _I, _P(FetchStats)]),
+    "ps_bgzf_device": (_I, [_I]),
+    "ps_bgzf_compress": (_I, [_PTR, _U64, _I, _PTR, _U64, _P(BgzfStats)]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -598,6 +605,22 @@ def ps_fetch_sequences(ref_fa, sites, out_file, bed=False):
     the reference sequence of every site of a table, gathered on the GPU from the index of ref_fa (.ann and .pac; the FASTA is
     not opened); writes out_file and returns the counters"""
     return _stats(lib().ps_fetch_sequences, FetchStats, ref_fa.encode(), sites.encode(), out_file.encode(), int(bool(bed)))
+
+
+def ps_bgzf_device(device):
+    """the BGZF switch: -1 host zlib (the default), device >= 0: every BAM this process writes from now on is compressed on it"""
+    _chk(lib().ps_bgzf_device(int(device)))
+
+
+def ps_bgzf_compress(data, device=0):
+    """data cut at 0xff00 bytes -> (the BGZF members without an end-of-file block, the stats dict), compressed on the device;
+    device -1: by the library's host path (zlib at PS_BAM_LEVEL, 16 threads)"""
+    data = bytes(data)
+    n_blocks = (len(data) + 0xff00 - 1) // 0xff00
+    dst = C.create_string_buffer(max(1, len(data) + len(data) // 100 + n_blocks * 128))   # the device never exceeds the stored form; zlib may, a little
+    st = BgzfStats(struct_size=C.sizeof(BgzfStats))
+    _chk(lib().ps_bgzf_compress(data, len(data), int(device), dst, len(dst), C.byref(st)))
+    return dst.raw[:st.out_bytes], _struct_dict(st)
 
 
 def _map_args(threads, mm, error_profile, indel_profile, ref_fa, fastq, out):

@@ -4,9 +4,11 @@
 // `samtools view -q <mapq> -b`) and Mapping.java:85-108 (`samtools sort`, `samtools index`) spawn four
 // processes and three rewrites of the data for.  Formats follow the public SAM/BAM specification (SAMv1:
 // BGZF blocks of at most 64 KiB with the BC extra field, BAM records, binning index with 16 kb linear index);
-// integer tags take the smallest type as htslib's SAM parser does.  Host code only (zlib), no device work.
+// integer tags take the smallest type as htslib's SAM parser does.  Host code only (zlib), no device work in this file: the BGZF
+// blocks of every writer go through bgzf_batch(), which hands them to the device compressor when one is registered (ps_bam.h).
 #include <zlib.h>
 #include <algorithm>
+#include <atomic>
 #include <cctype>
 #include <cstdint>
 #include <cstdio>
@@ -166,7 +168,29 @@ template <class F> static void par(int n, int threads, F f)
     for (auto &e : err) if (!e.empty()) throw Error(e);
 }
 
+// The one place where BGZF blocks are made: comp[k] becomes the whole member (header, deflate payload, CRC32, ISIZE) of spans[k],
+// each span at most 0xff00 bytes.  On host threads with zlib, or -- the whole list at once -- by the compressor that the library
+// registered (ps_bgzf.hip: ps_bgzf_device, PS_BGZF_GPU); `level` means nothing to that one.
+std::atomic<BgzfBatchFn> g_bgzf_device{nullptr};
+static void bgzf_batch(const std::vector<BgzfSpan> &spans, int level, int threads, std::vector<std::string> &comp)
+{
+    comp.assign(spans.size(), std::string());
+    if (spans.empty()) return;
+    if (const BgzfBatchFn fn = g_bgzf_device.load()) { fn(spans.data(), spans.size(), comp.data()); return; }
+    const int T = threads;
+    par(T, T, [&](int t) { for (size_t k = (size_t)t; k < spans.size(); k += (size_t)T) bgzf_block(spans[k].p, spans[k].n, level, comp[k]); });
+}
+
 }  // namespace
+
+void bgzf_set_device_compressor(BgzfBatchFn fn) { g_bgzf_device.store(fn); }
+static int clamp_threads(int t);
+void bgzf_host_compress(const BgzfSpan *spans, size_t n_spans, int level, int threads, std::string *comp)
+{
+    const int T = clamp_threads(threads);
+    for (size_t k = 0; k < n_spans; ++k) { if (spans[k].n > 0xff00) throw Error("a BGZF span of more than 0xff00 bytes"); comp[k].clear(); }
+    par(T, T, [&](int t) { for (size_t k = (size_t)t; k < n_spans; k += (size_t)T) bgzf_block(spans[k].p, spans[k].n, level, comp[k]); });
+}
 
 namespace {
 
@@ -414,15 +438,14 @@ static void write_bam(Data &d, const char *bam_path, bool write_index, int threa
     }
     if (!keep_enc) for (auto &e : d.enc) { e.clear(); e.shrink_to_fit(); }
     const size_t n_blocks = head_blocks + body_blocks;
-    std::vector<std::string> comp(n_blocks);
+    std::vector<std::string> comp;
     {
-        const int T = threads;
-        par(T, T, [&](int t) {
-            for (size_t k = (size_t)t; k < n_blocks; k += (size_t)T) {
-                if (k < head_blocks) { const size_t a0 = k * BLK; bgzf_block(head.data() + a0, std::min(BLK, head.size() - a0), level, comp[k]); }
-                else { const size_t a0 = (k - head_blocks) * BLK; bgzf_block(stream.data() + a0, (size_t)std::min<uint64_t>(BLK, body_bytes - a0), level, comp[k]); }
-            }
-        });
+        std::vector<BgzfSpan> spans(n_blocks);
+        for (size_t k = 0; k < n_blocks; ++k) {
+            if (k < head_blocks) { const size_t a0 = k * BLK; spans[k] = BgzfSpan{head.data() + a0, std::min(BLK, head.size() - a0)}; }
+            else { const size_t a0 = (k - head_blocks) * BLK; spans[k] = BgzfSpan{stream.data() + a0, (size_t)std::min<uint64_t>(BLK, body_bytes - a0)}; }
+        }
+        bgzf_batch(spans, level, threads, comp);
     }
     std::vector<uint64_t> coff(n_blocks + 1, 0);
     for (size_t k = 0; k < n_blocks; ++k) coff[k + 1] = coff[k] + comp[k].size();
@@ -528,8 +551,10 @@ BamSink::BamSink(const std::string &header_text, const std::vector<std::pair<std
     head.append("BAM\1", 4); put32(head, (uint32_t)p->d.text.size()); head += p->d.text; put32(head, (uint32_t)p->d.refs.size());
     for (auto &r : p->d.refs) { put32(head, (uint32_t)r.first.size() + 1); head += r.first; head.push_back('\0'); put32(head, r.second); }
     const size_t BLK = 0xff00;
-    for (size_t a0 = 0; a0 < head.size(); a0 += BLK) {
-        std::string blk; bgzf_block(head.data() + a0, std::min(BLK, head.size() - a0), p->level, blk);
+    std::vector<BgzfSpan> spans; std::vector<std::string> comp;
+    for (size_t a0 = 0; a0 < head.size(); a0 += BLK) spans.push_back(BgzfSpan{head.data() + a0, std::min(BLK, head.size() - a0)});
+    try { bgzf_batch(spans, p->level, 1, comp); } catch (...) { std::fclose(p->f); delete p; p = nullptr; throw; }
+    for (const std::string &blk : comp) {
         if (std::fwrite(blk.data(), 1, blk.size(), p->f) != blk.size()) p->failed = true;
         p->bytes += blk.size();
     }
@@ -552,9 +577,9 @@ void BamSink::add(std::vector<std::string> &records, std::vector<std::vector<Bam
     const size_t BLK = 0xff00;
     std::vector<std::pair<size_t, size_t>> blk;              // (buffer, offset)
     for (size_t k = 0; k < records.size(); ++k) { p->n_out += recs[k].size(); for (size_t a0 = 0; a0 < records[k].size(); a0 += BLK) blk.emplace_back(k, a0); }
-    std::vector<std::string> comp(blk.size());
-    const int T = p->threads;
-    par(T, T, [&](int t) { for (size_t j = (size_t)t; j < blk.size(); j += (size_t)T) { const std::string &src = records[blk[j].first]; bgzf_block(src.data() + blk[j].second, std::min(BLK, src.size() - blk[j].second), p->level, comp[j]); } });
+    std::vector<BgzfSpan> spans(blk.size()); std::vector<std::string> comp;
+    for (size_t j = 0; j < blk.size(); ++j) { const std::string &src = records[blk[j].first]; spans[j] = BgzfSpan{src.data() + blk[j].second, std::min(BLK, src.size() - blk[j].second)}; }
+    bgzf_batch(spans, p->level, p->threads, comp);
     for (size_t j = 0; j < comp.size(); ++j) { if (std::fwrite(comp[j].data(), 1, comp[j].size(), p->f) != comp[j].size()) p->failed = true; p->bytes += comp[j].size(); }
     records.clear(); recs.clear();
 }

@@ -7,6 +7,14 @@
 #include "ps_outfiles.h"
 namespace ps {
 struct BamStats { uint64_t n_in = 0, n_out = 0, bam_bytes = 0; };
+// Every BGZF block of every writer below is made by one batch function (ps_bam.cpp: bgzf_batch): spans of at most 0xff00 bytes ->
+// comp[k], the whole gzip member of spans[k].  By default zlib on host threads.  A compressor registered here takes the whole
+// list instead (the device compressor of ps_bgzf.hip; this file and ps_bam.cpp stay free of HIP); it throws ps::Error, and the
+// writing call fails with it -- there is no fallback to zlib.  Null: zlib again.
+struct BgzfSpan { const char *p; size_t n; };
+typedef void (*BgzfBatchFn)(const BgzfSpan *spans, size_t n_spans, std::string *comp);
+void bgzf_set_device_compressor(BgzfBatchFn fn);
+void bgzf_host_compress(const BgzfSpan *spans, size_t n_spans, int level, int threads, std::string *comp);   // the host path itself, whatever is registered
 // one encoded BAM record inside a buffer of records: reference id, 0-based position and end, flag, byte range [off, off + len)
 struct BamRec { int32_t ref; int32_t pos; int32_t end; uint32_t flag; size_t off, len; int part; };
 // The record layout (SAMv1 4.2), for every route that makes records -- SAM text (sam_to_bam) and the mapper's hits (ps_map_to_bam).

@@ -11,6 +11,7 @@
 #include "ps_map.h"
 #include "ps_bam.h"
 #include "ps_host.h"
+#include "ps_bgzf.h"
 
 using namespace ps;
 
@@ -552,6 +553,44 @@ int ps_fetch_sequences(const char *ref_fa, const char *sites, const char *out_fi
     PS_CATCH_INT
 }
 
+int ps_bgzf_device(int device)
+{
+    PS_TRY
+        bgzf_set_device(device < 0 ? -1 : device);
+        return 0;
+    PS_CATCH_INT
+}
+int ps_bgzf_compress(const void *src, uint64_t n, int device, void *dst, uint64_t cap, ps_bgzf_stats *stats)
+{
+    PS_TRY
+        if (stats && stats->struct_size < sizeof(ps_bgzf_stats)) throw Error("ps_bgzf_compress: stats->struct_size is not sizeof(ps_bgzf_stats)");
+        if (n && (!src || !dst)) throw Error("ps_bgzf_compress: source and destination are required");
+        const size_t BLK = 0xff00;
+        std::vector<BgzfSpan> spans;
+        for (uint64_t at = 0; at < n; at += BLK) spans.push_back(BgzfSpan{(const char *)src + at, (size_t)std::min<uint64_t>(BLK, n - at)});
+        std::vector<std::string> comp(spans.size());
+        BgzfStats s;
+        if (device >= 0) bgzf_device_compress(spans.data(), spans.size(), device, comp.data(), &s);
+        else {                                      // the library's host path on the same cuts: zlib at PS_BAM_LEVEL (1) on 16 threads
+            int level = 1;
+            if (const char *e = std::getenv("PS_BAM_LEVEL")) level = std::atoi(e);
+            bgzf_host_compress(spans.data(), spans.size(), level < 0 ? 0 : (level > 9 ? 9 : level), 16, comp.data());
+            for (size_t k = 0; k < comp.size(); ++k) {
+                const int btype = ((unsigned char)comp[k][18] >> 1) & 3;        // of the member's first DEFLATE block
+                ++s.n_blocks; s.n_stored += btype == 0; s.n_fixed += btype == 1; s.n_dynamic += btype == 2;
+                s.in_bytes += spans[k].n; s.out_bytes += comp[k].size();
+            }
+        }
+        if (s.out_bytes > cap) throw Error("ps_bgzf_compress: the members take " + std::to_string(s.out_bytes) + " bytes, the destination holds " + std::to_string(cap));
+        char *o = (char *)dst;
+        for (const std::string &c : comp) { std::memcpy(o, c.data(), c.size()); o += c.size(); }
+        if (stats) {
+            stats->n_blocks = s.n_blocks; stats->n_stored = s.n_stored; stats->n_fixed = s.n_fixed; stats->n_dynamic = s.n_dynamic; stats->pad_ = 0;
+            stats->in_bytes = s.in_bytes; stats->out_bytes = s.out_bytes; stats->kernel_ms = s.kernel_ms;
+        }
+        return 0;
+    PS_CATCH_INT
+}
 int ps_sam_to_bam(const char *sam, const char *bam, int min_mapq, int sort_by_coordinate, int write_index, int threads, ps_bam_stats *st)
 {
     PS_TRY

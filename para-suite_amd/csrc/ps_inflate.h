@@ -11,6 +11,8 @@
 //
 // No device work: one DEFLATE stream is a serial chain (every symbol's bit position and the 32 KB window depend on all before
 // it), and BGZF's independent blocks feed a parser that runs on the host.
+// This speaks of inflating.  Compressing has no such chain across BGZF blocks, and the blocks a BAM writer makes can be compressed
+// on the device (ps_deflate.h, ps_bgzf.hip).
 #pragma once
 #include <cstddef>
 #include <cstdint>

@@ -690,6 +690,28 @@ int     ps_bgzf_device(int device);
 typedef struct { uint32_t struct_size, n_blocks, n_stored, n_fixed, n_dynamic, pad_; uint64_t in_bytes, out_bytes; double kernel_ms; } ps_bgzf_stats;
 int     ps_bgzf_compress(const void *src, uint64_t n, int device, void *dst, uint64_t cap, ps_bgzf_stats *stats /* may be NULL */);
 
+/* ---- BAM records built on the device ------------------------------------------------------------------------------
+ * ps_map_to_bam and every pass of ps_map_route / ps_map_route_opts turn a located piece into BAM records.  By default host
+ * threads do that.  With the switch on (on != 0; PS_BAM_RECORDS_GPU=1 in the environment is the same, read once when the
+ * library is loaded) the device that mapped the piece builds the record of every read it finished itself, right after the
+ * locate stage and on the same stream: name, CIGAR, bases, qualities and the tags XT NM XN X0 X1 XM XO XG MD, byte for byte what
+ * the host route writes (csrc/ps_bamrec.h states the record once for both).  Reads finished on the host (several best
+ * intervals, XA lists, larger tiers) keep their records from the host route, spliced into the same stream.  The records, the
+ * sorted files and their .bai are the same with the switch on or off; an unsorted file has one buffer of records per piece
+ * instead of one per host thread, so its BGZF block cuts differ and its inflated bytes do not.  A HIP error fails the writing
+ * call: there is no fallback to the host route.  ps_map, ps_map_profiled and ps_sam_to_bam are not touched by the switch.
+ * ps_bam_records_info: counters summed over the process since the switch was last set (records by who built them, bytes, and
+ * the route's four times in ms: inputs up, kernels, host-built records, stream down). */
+typedef struct { uint64_t n_reads, n_records, n_device, n_host, bytes; double ms_upload, ms_kernels, ms_host_records, ms_download; } ps_bam_records_stats;
+int     ps_bam_records_device(int on);
+int     ps_bam_records_info(ps_bam_records_stats *out);
+/* The staged form, after ps_batch_locate: the batch's records with MAPQ >= min_mapq, in input order, back to back in dst.
+ * on_device 0: the host route on `threads` threads; 1: the device route (`threads` build the host-finished reads' records).
+ * Returns the byte count, -1 on error.  dst NULL: the count alone.  When the records need more than cap bytes the call fails with
+ * both numbers in the error and dst untouched.  origin (may be NULL, as many bytes as there are kept records): 0 where the device
+ * built the record, 1 where the host did. */
+int64_t ps_batch_bam_records(ps_batch *b, int min_mapq, int on_device, int threads, void *dst, uint64_t cap, uint8_t *origin /* may be NULL */, ps_bam_records_stats *stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -165,13 +165,19 @@ class BgzfStats(C.Structure):
                _fields(C.c_uint64, "in_bytes", "out_bytes") + [("kernel_ms", C.c_double)]
 
 
+class BamRecordsStats(C.Structure):
+    _fields_ = _fields(C.c_uint64, "n_reads", "n_records", "n_device", "n_host", "bytes") + \
+               _fields(C.c_double, "ms_upload", "ms_kernels", "ms_host_records", "ms_download")
+
+
 # every struct typedef of the header -> its mirror (ps_aln and ps_hit are read as numpy records)
 STRUCTS = {"ps_search_opts": SearchOpts, "ps_index_info": IndexInfo, "ps_aln": ALN_DTYPE, "ps_hit": HIT_DTYPE, "ps_timing": Timing,
            "ps_kstats": KStats, "ps_collapse_info": CollapseInfo, "ps_bam_stats": BamStats, "ps_profile_stats": ProfileStats, "ps_cluster_stats": ClusterStats,
            "ps_extract_stats": ExtractStats, "ps_names_stats": NamesStats, "ps_combine_stats": CombineStats,
            "ps_route_opts": RouteOpts, "ps_route_stats": RouteStats, "ps_route_opts2": RouteOpts2, "ps_resident_opts": ResidentOpts,
            "ps_resident_stats": ResidentStats, "ps_benchmark_stats": BenchmarkStats, "ps_simulate_opts": SimulateOpts,
-           "ps_simulate_stats": SimulateStats, "ps_fetch_stats": FetchStats, "ps_bgzf_stats": BgzfStats}
+           "ps_simulate_stats": SimulateStats, "ps_fetch_stats": FetchStats, "ps_bgzf_stats": BgzfStats,
+           "ps_bam_records_stats": BamRecordsStats}
 
 # ---- the functions of the header, in its order: name -> (restype, argtypes) ----
 # int, int64_t, uint64_t, double, const char *; _PTR: ps_ctx *, ps_batch * and every buffer handed over as an address
@@ -249,6 +255,9 @@ SIGNATURES = {
     "ps_fetch_sequences": (_I, [_S, _S, _S, _I, _P(FetchStats)]),
     "ps_bgzf_device": (_I, [_I]),
     "ps_bgzf_compress": (_I, [_PTR, _U64, _I, _PTR, _U64, _P(BgzfStats)]),
+    "ps_bam_records_device": (_I, [_I]),
+    "ps_bam_records_info": (_I, [_P(BamRecordsStats)]),
+    "ps_batch_bam_records": (_I64, [_PTR, _I, _I, _I, _PTR, _U64, _PTR, _P(BamRecordsStats)]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -532,6 +541,20 @@ class Batch:
         """ps_collapse_info of the last search as a dict: reads, reads searched, groups ... (collapse off: n_searched == n_reads)"""
         return _stats(lib().ps_batch_collapse_info, CollapseInfo, self.h)
 
+    def bam_records(self, min_mapq=0, on_device=True, threads=8):
+        """after locate(): the batch's BAM records with MAPQ >= min_mapq, in input order -> (the bytes, per record 0 device-built /
+        1 host-built as a uint8 array, ps_bam_records_stats as a dict); on_device False: the host route.  The route runs twice, once for
+        the size and once for the bytes, and with on_device each run adds to the counters of ps_bam_records_info"""
+        st = BamRecordsStats()
+        n = lib().ps_batch_bam_records(self.h, int(min_mapq), int(bool(on_device)), int(threads), None, 0, None, C.byref(st))
+        if n < 0:
+            raise PsError(lib().ps_last_error().decode())
+        dst, origin = np.zeros(max(1, n), dtype=np.uint8), np.zeros(max(1, st.n_records), dtype=np.uint8)
+        n2 = lib().ps_batch_bam_records(self.h, int(min_mapq), int(bool(on_device)), int(threads), dst.ctypes.data, n, origin.ctypes.data, C.byref(st))
+        if n2 < 0:
+            raise PsError(lib().ps_last_error().decode())
+        return dst[:n2].tobytes(), origin[:st.n_records].copy(), _struct_dict(st)
+
     def duplicate_of(self):
         """input order: the input index of the representative of every read's group (a representative names itself).  The groups
         are exact -- compared in full, never by hash -- and in one rare case incomplete: identical reads may stand in two groups
@@ -621,6 +644,17 @@ def ps_bgzf_compress(data, device=0):
     st = BgzfStats(struct_size=C.sizeof(BgzfStats))
     _chk(lib().ps_bgzf_compress(data, len(data), int(device), dst, len(dst), C.byref(st)))
     return dst.raw[:st.out_bytes], _struct_dict(st)
+
+
+def ps_bam_records_device(on):
+    """the switch of the BAM records' device route (off by default): ps_map_to_bam and every pass of ps_map_route build their
+    records on the device that mapped the piece; setting it, either way, resets the counters of ps_bam_records_info"""
+    _chk(lib().ps_bam_records_device(int(bool(on))))
+
+
+def ps_bam_records_info():
+    """ps_bam_records_stats as a dict: what the device route has done since the switch was last set"""
+    return _stats(lib().ps_bam_records_info, BamRecordsStats)
 
 
 def _map_args(threads, mm, error_profile, indel_profile, ref_fa, fastq, out):

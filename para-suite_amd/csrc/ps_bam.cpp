@@ -583,6 +583,25 @@ void BamSink::add(std::vector<std::string> &records, std::vector<std::vector<Bam
     for (size_t j = 0; j < comp.size(); ++j) { if (std::fwrite(comp[j].data(), 1, comp[j].size(), p->f) != comp[j].size()) p->failed = true; p->bytes += comp[j].size(); }
     records.clear(); recs.clear();
 }
+void BamSink::add(const char *records, size_t n_bytes, std::vector<BamRec> &recs, uint64_t n_in)
+{
+    p->d.n_in += n_in;
+    if (p->sort) {
+        const int part = (int)p->d.enc.size();
+        for (BamRec &r : recs) r.part = part;
+        p->d.enc.emplace_back(records, n_bytes);
+        p->d.recs.insert(p->d.recs.end(), recs.begin(), recs.end());
+        recs.clear();
+        return;
+    }
+    const size_t BLK = 0xff00;
+    p->n_out += recs.size();
+    std::vector<BgzfSpan> spans; std::vector<std::string> comp;
+    for (size_t a0 = 0; a0 < n_bytes; a0 += BLK) spans.push_back(BgzfSpan{records + a0, std::min(BLK, n_bytes - a0)});
+    bgzf_batch(spans, p->level, p->threads, comp);
+    for (size_t j = 0; j < comp.size(); ++j) { if (std::fwrite(comp[j].data(), 1, comp[j].size(), p->f) != comp[j].size()) p->failed = true; p->bytes += comp[j].size(); }
+    recs.clear();
+}
 void BamSink::finish(BamStats *stats, BamFile *keep)
 {
     if (keep && !p->sort) throw Error("internal: only a sorted BAM is kept in memory");

@@ -42,6 +42,10 @@ public:
     ~BamSink();
     // buffers of records in input order (one per encoding thread); recs[k][i].off/len index into records[k]; both are consumed
     void add(std::vector<std::string> &records, std::vector<std::vector<BamRec>> &recs, uint64_t n_in);
+    // one buffer of records that stays the caller's (the device route's page-locked download: ps_bamrec.hip); recs[i].off / len index into it.
+    // Unsorted output is cut and compressed straight from the span -- one buffer, so a block never spans two; a sorted sink, which has to
+    // keep the records until finish(), takes its copy.  recs is consumed.
+    void add(const char *records, size_t n_bytes, std::vector<BamRec> &recs, uint64_t n_in);
     void finish(BamStats *stats, BamFile *keep = nullptr);
 private:
     struct Impl; Impl *p;

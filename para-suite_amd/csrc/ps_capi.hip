@@ -1,6 +1,7 @@
 // ps_capi.hip -- extern "C" boundary (include/parasuite_hip.h).  Exceptions stop here: every entry point converts its structs, checks
 // its arguments, makes one call into the library (which throws ps::Error) and turns what is thrown into a status and ps_last_error().
 #include <hip/hip_runtime.h>
+#include <chrono>
 #include <functional>
 #include <cstdio>
 #include <cstdlib>
@@ -590,6 +591,49 @@ int ps_bgzf_compress(const void *src, uint64_t n, int device, void *dst, uint64_
         }
         return 0;
     PS_CATCH_INT
+}
+int ps_bam_records_device(int on) { PS_TRY bam_records_device_set(on != 0); return 0; PS_CATCH_INT }
+int ps_bam_records_info(ps_bam_records_stats *out)
+{
+    PS_TRY
+        if (!out) throw Error("ps_bam_records_info: no place for the result");
+        bam_records_info(*out); return 0;
+    PS_CATCH_INT
+}
+int64_t ps_batch_bam_records(ps_batch *b, int min_mapq, int on_device, int threads, void *dst, uint64_t cap, uint8_t *origin, ps_bam_records_stats *stats)
+{
+    try {
+        Batch &B = *b->b;
+        if (threads < 1) threads = 1;
+        ps_bam_records_stats st; std::memset(&st, 0, sizeof st);
+        st.n_reads = (uint64_t)B.rs.n;
+        auto room = [&](uint64_t need) {
+            if (dst && need > cap) throw Error("ps_batch_bam_records: the records take " + std::to_string(need) + " bytes, the destination holds " + std::to_string(cap));
+        };
+        if (on_device) {
+            require_device(B.ctx->device);
+            DevRecords r;
+            batch_bam_records_device(B, min_mapq, threads, r);
+            room(r.n_bytes);
+            st.n_records = r.recs.size(); st.n_device = r.n_device; st.n_host = r.n_host; st.bytes = r.n_bytes;
+            st.ms_upload = r.ms_upload; st.ms_kernels = r.ms_kernels; st.ms_host_records = r.ms_host_records; st.ms_download = r.ms_download;
+            if (dst && r.n_bytes) std::memcpy(dst, r.bytes, r.n_bytes);
+            if (dst && origin && !r.origin.empty()) std::memcpy(origin, r.origin.data(), r.origin.size());
+        } else {
+            std::vector<std::string> enc; std::vector<std::vector<BamRec>> recs;
+            const auto t0 = std::chrono::steady_clock::now();
+            batch_bam_records(B, min_mapq, threads, enc, recs);
+            st.ms_host_records = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            for (size_t k = 0; k < enc.size(); ++k) { st.bytes += enc[k].size(); st.n_records += recs[k].size(); }
+            st.n_host = st.n_records;
+            room(st.bytes);
+            char *o = (char *)dst;
+            if (dst) for (const std::string &e : enc) { std::memcpy(o, e.data(), e.size()); o += e.size(); }
+            if (dst && origin) std::memset(origin, 1, (size_t)st.n_records);
+        }
+        if (stats) *stats = st;
+        return (int64_t)st.bytes;
+    } catch (const std::exception &e) { fail(e.what()); return -1; } catch (...) { fail("unknown error"); return -1; }
 }
 int ps_sam_to_bam(const char *sam, const char *bam, int min_mapq, int sort_by_coordinate, int write_index, int threads, ps_bam_stats *st)
 {

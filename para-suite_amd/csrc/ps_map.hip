@@ -86,6 +86,12 @@ struct BamRecords : PassOut {
     {
         Charge c{busy};
         BamSink &s = sink_for(*b.ctx);
+        if (b.dev_records && b.dev_records_mapq == o.min_mapq) {      // built on the device by the piece's worker (ps_bamrec.hip)
+            DevRecords &r = *b.dev_records;
+            s.add((const char *)r.bytes, r.n_bytes, r.recs, (uint64_t)b.rs.n);
+            b.dev_records.reset();
+            return;
+        }
         std::vector<std::string> enc; std::vector<std::vector<BamRec>> recs;
         batch_bam_records(b, o.min_mapq, nthr, enc, recs);
         s.add(enc, recs, (uint64_t)b.rs.n);
@@ -130,6 +136,7 @@ struct MapJob {
     MapArgs a;
     std::vector<ReadSet> *reads = nullptr; // the input, already parsed, instead of the file a.reads (consumed)
     bool bam_out = false;                  // the piece plan's: the records are compressed, which wants early pieces
+    bool records_out = false; int records_mapq = 0;   // the pass has a BamRecords output, with this MAPQ filter (the device route of the records builds for it)
     std::vector<std::unique_ptr<PassOut>> outs;
     CtxSet *resident = nullptr;            // ps_map_route, the resident scope: the contexts are taken from there (made and loaded by the first pass that finds none) and left open
     std::vector<CtxSet *> lanes_from;      // the lanes of work (streams, search workspace) of these contexts, which search no more, move to this pass's contexts on the same devices
@@ -320,7 +327,12 @@ void Pass::work(int g, int j, int slot)
             cv.notify_all();
             batch_select_easy(b, nthr);
             batch_locate(b);
-            b.release_device();                                // what is left to do (SAM text) reads host memory only
+            if (job.records_out && bam_records_device_on()) {     // the BAM records while d_sel and d_fin are still in HBM; a HIP error fails the call
+                b.dev_records.reset(new DevRecords());
+                b.dev_records_mapq = job.records_mapq;
+                batch_bam_records_device(b, job.records_mapq, nthr, *b.dev_records);
+            }
+            b.release_device();                               // what is left to do (SAM text) reads host memory only
             if (verbose) {
                 const Timing &t = b.tm;
                 std::fprintf(stderr, "[parasuite-hip]   piece %lld on device %d worker %d: %lld reads; upload %.0f ms, search stage %.0f ms wall (width %.0f backtrack %.0f classify %.0f), select %.0f+%.0f sa2pos %.0f refine %.0f host_post %.0f ms\n",
@@ -541,7 +553,7 @@ void map_to_bam(const MapArgs &a, const char *out_bam, int min_mapq, bool sort_b
 {
     BamOut bo; bo.min_mapq = min_mapq; bo.sort = sort_by_coordinate; bo.index = write_index; bo.stats = stats;
     if (const char *e = std::getenv("PS_BAM_LEVEL")) bo.level = std::atoi(e);
-    MapJob job; job.a = a; job.bam_out = true;
+    MapJob job; job.a = a; job.bam_out = true; job.records_out = true; job.records_mapq = min_mapq;
     job.outs.emplace_back(new BamRecords(bo, out_bam, a.threads > 0 ? a.threads : 1, job.s_write));
     run_single(job);
 }
@@ -617,7 +629,7 @@ struct Route {
     {
         BamStats bs; BamOut bo; bo.min_mapq = min_mapq; bo.sort = !by_name; bo.index = !by_name; bo.by_name = by_name; bo.keep = keep_recs; bo.stats = &bs; bo.level = bam_level;
         const std::string t = files.tmp(out);
-        job.a = MapArgs{threads, mm, ep, ip, ref, o.reads_fq, o.search}; job.bam_out = true;
+        job.a = MapArgs{threads, mm, ep, ip, ref, o.reads_fq, o.search}; job.bam_out = true; job.records_out = true; job.records_mapq = min_mapq;
         job.outs.emplace(job.outs.begin(), new BamRecords(bo, t.c_str(), threads, job.s_write));
         Pass(job).run();
         if (publish) { files.publish(out); if (!by_name) files.publish(out + ".bai"); }

@@ -92,6 +92,7 @@ struct Ctx : OptionParts {          // opt, search: the options in their two par
     Work *take_work();             // creates the lane's stream on first use
     Work *work_at(int i);          // lane i (ps_map: one per worker thread of the device); thread safe
     std::mutex work_mu;
+    std::shared_ptr<void> rec_tables;   // the device route of the BAM records (ps_bamrec.hip): contig and hole tables on the device, uploaded once per context (work_mu)
     // A context in two steps: options and knobs (no device call: ps_map's parser needs nothing else and starts before the runtime is
     // up, which takes 0.2-0.3 s in a fresh process), then the device side (stream, clock).
     explicit Ctx(int device);      // reads the tuning knobs from the environment (PS_FETCH_MIN, PS_N_BIG, ...)
@@ -123,6 +124,15 @@ struct Bin {
     std::vector<int32_t> h_rep_of;            // collapsed search: bin-local read -> its group's representative; empty: every read stands for itself
 };
 
+// The BAM records of a located batch as the device route makes them (ps_bamrec.hip): one page-locked buffer with every kept record in
+// input order, recs[i].off / len into it (part 0), origin[i] 1 where the host built the record (a PS_CLS_HOST read) and 0 where the device did
+struct DevRecords {
+    PinBuf pin; const uint8_t *bytes = nullptr; size_t n_bytes = 0;
+    std::vector<BamRec> recs; std::vector<uint8_t> origin;
+    uint64_t n_reads = 0, n_device = 0, n_host = 0;
+    double ms_upload = 0, ms_kernels = 0, ms_host_records = 0, ms_download = 0;
+};
+
 struct Batch {
     Ctx *ctx = nullptr;
     Work *wk = nullptr;            // the lane of work this batch runs on
@@ -148,6 +158,7 @@ struct Batch {
     const AlnRec *alns_of(int64_t g, int &n);      // downloads the hit lists on first use
     void ensure_host_alns();
     void hit_of(int64_t g, Hit &h) const;
+    std::unique_ptr<DevRecords> dev_records; int dev_records_mapq = 0;   // ps_map with the device route on: the worker's result for the pass's BamRecords output (its MAPQ filter)
     void release_device();         // after batch_locate: everything batch_write_sam / hit_of read is in host memory
 };
 
@@ -161,6 +172,18 @@ void ctx_release_device(Ctx &c);                               // every device a
 void reserve_search_workspace(Ctx *ctx, int work_index);        // the big device allocations of a lane of work, ahead of its first search
 void batch_locate(Batch &b);                                    // SA walk kernel, strand / MAPQ, banded DP of gapped hits
 void batch_bam_records(const Batch &b, int min_mapq, int threads, std::vector<std::string> &enc, std::vector<std::vector<BamRec>> &recs);   // the located batch as BAM records (MAPQ >= min_mapq): one buffer per thread, buffers in input order
+// the records of the host-finished reads alone (Batch::sub, in its order), for the device route to splice in: recs[i] is sub[i]'s record -- part: its
+// buffer, off / len into that buffer, len 0: below the MAPQ filter
+void batch_bam_records_sub(const Batch &b, int min_mapq, int threads, std::vector<std::string> &enc, std::vector<BamRec> &recs);
+// The same records built on the device that mapped the batch (ps_bamrec.hip), after batch_locate and before Batch::release_device, on the
+// batch's own lane: the device builds the record of every read it finished itself, the host those of the PS_CLS_HOST reads (on `threads`
+// threads, while the size kernel runs), and one buffer in input order comes down.  A HIP error throws; there is no fallback to the host route.
+void batch_bam_records_device(Batch &b, int min_mapq, int threads, DevRecords &out);
+// the switch of ps_bam_records_device / PS_BAM_RECORDS_GPU (off by default) and the counters since it was last set
+bool bam_records_device_on();
+void bam_records_device_set(bool on);
+void bam_records_info(ps_bam_records_stats &out);
+void bam_records_count(const ps_bam_records_stats &add);
 std::string sam_header(const RefSeq &ref, const char *pg_line);      // @SQ lines in FASTA order + the @PG line
 // text buffers of the SAM writer, kept from piece to piece by ps_map: fresh ones are first touched page by page, and a page fault waits
 // while another thread gives a finished piece's gigabytes back to the system (0.2 s per piece, measured)

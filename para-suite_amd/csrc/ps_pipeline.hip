@@ -75,6 +75,7 @@ void ctx_release_device(Ctx &c)
     {
         std::lock_guard<std::mutex> l(c.work_mu);
         for (auto &w : c.work) w.reset();
+        c.rec_tables.reset();
     }
     c.ix.blocks.release(); c.ix.sa.release(); c.ix.pac.release(); c.ix.jump.release();     // the view keeps its (now dangling) device pointers: nothing may search with this context again
 }

@@ -309,6 +309,21 @@ void batch_bam_records(const Batch &b, int min_mapq, int threads, std::vector<st
     if (verbose) std::fprintf(stderr, "[parasuite-hip]     BAM records of %lld reads: building on %d threads %.0f ms\n", (long long)N, nt,
                               1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count());
 }
+// the host-finished reads alone, for the device route (ps_bamrec.hip) to splice into its stream: the same bam_record()
+void batch_bam_records_sub(const Batch &b, int min_mapq, int threads, std::vector<std::string> &enc, std::vector<BamRec> &recs)
+{
+    if (!b.located) throw Error("BAM records before locate");
+    const size_t M = b.sub.size();
+    const int nt = par_threads(M, threads);
+    enc.assign((size_t)nt, std::string()); recs.assign(M, BamRec{-1, -1, 0, 4, 0, 0, 0});
+    par_for(M, threads, [&](size_t i0, size_t i1, int t) {
+        std::string &o = enc[t]; o.reserve((i1 - i0) * 256);
+        for (size_t i = i0; i < i1; ++i) {
+            BamRec r; r.part = t; r.len = 0;
+            if (bam_record(b, b.sub[i].g, min_mapq, o, r)) recs[i] = r; else recs[i].part = t;
+        }
+    });
+}
 
 void batch_profile_records(const Batch &b, int min_mapq, int threads, ProfRecords &out)
 {

@@ -1,8 +1,10 @@
 """tools/e2e_time.py's fused route alone, with and without the BGZF switch: FASTQ -> MAPQ-filtered BAM through ps_map_to_bam
 (index load + search + records + BGZF + file written), unsorted and sorted + indexed, zlib level 1 on 16 threads against the
 device compressor.  PS_VERBOSE=1 prints the stage times of each call, where the compress launches queue behind the search.
+SWITCH=records alternates the BAM records' device route (ps_bam_records_device) instead, BGZF on host zlib throughout: the off runs
+of the same command are the reference.
 
-    python tools/e2e_bam_time.py [N_READS=10000000] [GENOME_MBP=1000] [WORKDIR=/tmp]"""
+    python tools/e2e_bam_time.py [N_READS=10000000] [GENOME_MBP=1000] [WORKDIR=/tmp] [SWITCH=bgzf|records]"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, 'para-suite_amd'); sys.path.insert(0, '.')
@@ -11,6 +13,8 @@ import torch, capi, bench
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
 mbp = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
 work = sys.argv[3] if len(sys.argv) > 3 else '/tmp'
+switch = sys.argv[4] if len(sys.argv) > 4 else 'bgzf'
+assert switch in ('bgzf', 'records')
 p = lambda x: os.path.join(work, 'e2e_bam.' + x)
 dev = torch.device('cuda', 0)
 contigs = bench.gen_genome(torch, dev, mbp * 1_000_000, 8, 0x5EED0002)
@@ -32,8 +36,12 @@ os.environ['PS_BAM_LEVEL'] = '1'
 os.environ['PS_VERBOSE'] = os.environ.get('E2E_VERBOSE', '1')
 for kw in (dict(min_mapq=10), dict(min_mapq=10, sort_by_coordinate=True, write_index=True)):
     for device in (-1, 0) * 5:                       # the first pair warms the page cache and the page-locked buffers up; four timed pairs
-        capi.ps_bgzf_device(device)
+        if switch == 'bgzf':
+            capi.ps_bgzf_device(device)
+        else:
+            capi.ps_bam_records_device(device >= 0)
         t = time.time(); st = capi.ps_map_to_bam(16, '-1', p('errorprofile'), p('indelprofile'), p('fa'), p('fq'), p('bam'), **kw); dt = time.time() - t
         print('ps_map_to_bam %s, %s: %.2fs, %d of %d records kept, BAM %.0f MB'
-              % (kw, 'BGZF on device 0' if device >= 0 else 'zlib level 1 on 16 threads', dt, st['n_out'], st['n_in'], st['bam_bytes'] / 1e6), flush=True)
+              % (kw, ('BGZF on device 0' if device >= 0 else 'zlib level 1 on 16 threads') if switch == 'bgzf' else ('records built on the device' if device >= 0 else 'records built on 16 host threads'), dt, st['n_out'], st['n_in'], st['bam_bytes'] / 1e6), flush=True)
 capi.ps_bgzf_device(-1)
+capi.ps_bam_records_device(0)

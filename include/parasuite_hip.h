@@ -712,6 +712,37 @@ int     ps_bam_records_info(ps_bam_records_stats *out);
  * built the record, 1 where the host did. */
 int64_t ps_batch_bam_records(ps_batch *b, int min_mapq, int on_device, int threads, void *dst, uint64_t cap, uint8_t *origin /* may be NULL */, ps_bam_records_stats *stats /* may be NULL */);
 
+/* ---- the coordinate sort of BAM records on the device ----------------------------------------------------------------
+ * Every sorted BAM the library writes (ps_sam_to_bam and ps_map_to_bam with sort_by_coordinate, ps_bam_sort without by_name, the
+ * sorted passes of ps_map_route / ps_map_route_opts, ps_combine_genome_transcript) orders its records with one stable sort on one
+ * host thread and gathers them into the file's stream on host threads.  The device switch: -1 (the default) is that host route;
+ * device >= 0 means that from now on the records' bytes go up to that device, a 64-bit key per record ((uint32_t)ref high,
+ * pos ^ 0x80000000 low: unplaced records last, positions as signed numbers) is sorted there by a stable radix sort, a hand-written
+ * kernel gathers the records into the sorted stream, and the permutation and the stream come down (csrc/ps_bamsort.h states the
+ * key and the gather once for host and device).  Block cuts, compression, the file and the .bai are made as before, from the same
+ * bytes: the files are the same with the switch on or off.  The name sort stays on the host.  The host route is taken, and counted
+ * in n_calls_host, when there are 2^32 records or more or when the call would need more than PS_BAM_SORT_MAX_MB (default 32768)
+ * of device memory.  Returns non-zero with the last error set when there is no such device.  A later HIP failure fails the writing
+ * call: there is no fallback.  PS_BAM_SORT_GPU=<device> in the environment is the same as the call; it is read once, when the
+ * library is loaded, so the bwa, samtools and parasuite programs take it too.
+ * ps_bam_sort_info: summed over the process since the switch was last set; on_device: the switch is on; bytes: record bytes
+ * sorted on the device; the route's four times in ms (records up, keys + sort, offsets + gather, permutation + stream down).
+ * When ps_bgzf_device names the same device and the call keeps no records in memory (every call but the passes of ps_map_route
+ * whose records go on to the next step), the sorted stream does not come down at all: the compressor reads it where it lies, and
+ * only the permutation (for the .bai), the blocks' sizes, CRCs and packed images cross to the host.  n_resident counts these calls.
+ * The file is the one that the BGZF switch alone writes, byte for byte. */
+int     ps_bam_sort_device(int device);
+typedef struct { uint32_t struct_size, on_device; uint64_t n_records, bytes, n_calls_device, n_calls_host, n_resident;
+                 double ms_upload, ms_sort, ms_gather, ms_download; } ps_bam_sort_stats;
+int     ps_bam_sort_info(ps_bam_sort_stats *out);
+/* records: BAM records back to back, block_size first (what ps_batch_bam_records emits) -> the same records in coordinate order
+ * in dst.  device >= 0: the device route whatever the switch says; -1: the library's host route (the stable sort and the gather
+ * on `threads` threads), the reference that tools/bam_sort_time.py measures against.  Returns the byte count, -1 on error.  A
+ * record that runs past n_bytes, or a block_size below 32, fails the call with the record's number.  When the records need more
+ * than cap bytes the call fails and writes nothing; dst is untouched on any error.  n_bytes == 0 writes nothing and returns 0.
+ * stats (struct_size must hold sizeof(ps_bam_sort_stats)): this call alone. */
+int64_t ps_bam_sort_records(const void *records, uint64_t n_bytes, int device, int threads, void *dst, uint64_t cap, ps_bam_sort_stats *stats /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

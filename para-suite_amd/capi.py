@@ -170,6 +170,12 @@ class BamRecordsStats(C.Structure):
                _fields(C.c_double, "ms_upload", "ms_kernels", "ms_host_records", "ms_download")
 
 
+class BamSortStats(C.Structure):
+    _fields_ = _fields(C.c_uint32, "struct_size", "on_device") + \
+               _fields(C.c_uint64, "n_records", "bytes", "n_calls_device", "n_calls_host", "n_resident") + \
+               _fields(C.c_double, "ms_upload", "ms_sort", "ms_gather", "ms_download")
+
+
 # every struct typedef of the header -> its mirror (ps_aln and ps_hit are read as numpy records)
 STRUCTS = {"ps_search_opts": SearchOpts, "ps_index_info": IndexInfo, "ps_aln": ALN_DTYPE, "ps_hit": HIT_DTYPE, "ps_timing": Timing,
            "ps_kstats": KStats, "ps_collapse_info": CollapseInfo, "ps_bam_stats": BamStats, "ps_profile_stats": ProfileStats, "ps_cluster_stats": ClusterStats,
@@ -177,7 +183,7 @@ STRUCTS = {"ps_search_opts": SearchOpts, "ps_index_info": IndexInfo, "ps_aln": A
            "ps_route_opts": RouteOpts, "ps_route_stats": RouteStats, "ps_route_opts2": RouteOpts2, "ps_resident_opts": ResidentOpts,
            "ps_resident_stats": ResidentStats, "ps_benchmark_stats": BenchmarkStats, "ps_simulate_opts": SimulateOpts,
            "ps_simulate_stats": SimulateStats, "ps_fetch_stats": FetchStats, "ps_bgzf_stats": BgzfStats,
-           "ps_bam_records_stats": BamRecordsStats}
+           "ps_bam_records_stats": BamRecordsStats, "ps_bam_sort_stats": BamSortStats}
 
 # ---- the functions of the header, in its order: name -> (restype, argtypes) ----
 # int, int64_t, uint64_t, double, const char *; _PTR: ps_ctx *, ps_batch * and every buffer handed over as an address
@@ -258,6 +264,9 @@ SIGNATURES = {
     "ps_bam_records_device": (_I, [_I]),
     "ps_bam_records_info": (_I, [_P(BamRecordsStats)]),
     "ps_batch_bam_records": (_I64, [_PTR, _I, _I, _I, _PTR, _U64, _PTR, _P(BamRecordsStats)]),
+    "ps_bam_sort_device": (_I, [_I]),
+    "ps_bam_sort_info": (_I, [_P(BamSortStats)]),
+    "ps_bam_sort_records": (_I64, [_PTR, _U64, _I, _I, _PTR, _U64, _P(BamSortStats)]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -655,6 +664,32 @@ def ps_bam_records_device(on):
 def ps_bam_records_info():
     """ps_bam_records_stats as a dict: what the device route has done since the switch was last set"""
     return _stats(lib().ps_bam_records_info, BamRecordsStats)
+
+
+def ps_bam_sort_device(device):
+    """the switch of the coordinate sort's device route: -1 the host (the default), device >= 0: every sorted BAM this process
+    writes from now on is sorted and gathered on it; setting it, either way, resets the counters of ps_bam_sort_info"""
+    _chk(lib().ps_bam_sort_device(int(device)))
+
+
+def ps_bam_sort_info():
+    """ps_bam_sort_stats as a dict: what the coordinate sort has done since the switch was last set"""
+    return _stats(lib().ps_bam_sort_info, BamSortStats)
+
+
+def ps_bam_sort_records(records, device=0, threads=16, cap=None, guard=0):
+    """BAM records back to back -> (the same records in coordinate order, the call's ps_bam_sort_stats as a dict); device -1: the
+    library's host route.  cap: the capacity told to the library (default: what the records take); guard: bytes of 0xee kept
+    behind cap, returned as a third value so that a caller can see them untouched"""
+    records = bytes(records)
+    cap = len(records) if cap is None else int(cap)
+    dst = C.create_string_buffer(b"\xee" * (cap + guard), cap + guard) if cap + guard else C.create_string_buffer(1)
+    st = BamSortStats(struct_size=C.sizeof(BamSortStats))
+    n = lib().ps_bam_sort_records(records, len(records), int(device), int(threads), dst, cap, C.byref(st))
+    if n < 0:
+        raise PsError(lib().ps_last_error().decode())
+    out = dst.raw[:n], _struct_dict(st)
+    return out + (dst.raw[cap:cap + guard],) if guard else out
 
 
 def _map_args(threads, mm, error_profile, indel_profile, ref_fa, fastq, out):

@@ -5,11 +5,14 @@
 // processes and three rewrites of the data for.  Formats follow the public SAM/BAM specification (SAMv1:
 // BGZF blocks of at most 64 KiB with the BC extra field, BAM records, binning index with 16 kb linear index);
 // integer tags take the smallest type as htslib's SAM parser does.  Host code only (zlib), no device work in this file: the BGZF
-// blocks of every writer go through bgzf_batch(), which hands them to the device compressor when one is registered (ps_bam.h).
+// blocks of every writer go through bgzf_batch(), which hands them to the device compressor when one is registered (ps_bam.h), and
+// every coordinate sort through sort_for_write(), which hands sort and gather to the registered hook (ps_bamsort.hip) the same way.
+// PS_VERBOSE: write_bam prints one line with the ms of its stages (sort, offsets + gather, compression, file write, .bai) on stderr.
 #include <zlib.h>
 #include <algorithm>
 #include <atomic>
 #include <cctype>
+#include <chrono>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -418,9 +421,27 @@ static void write_bai(const std::string &bai_path, const Data &d, const Layout &
     write_text_file(bai_path, bai);
 }
 
+using Clock = std::chrono::steady_clock;
+static double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
+
+// what the sort in front of write_bam did: its time and route for the stage line (PS_VERBOSE), and -- from the device route -- the
+// records already gathered in d.recs order, which write_bam takes in place of its own gather (and hands back when the parts are kept).
+// may_stay: the caller keeps no records in memory, so the device route may leave the stream where it is; resident: it did, and
+// write_bam has the body's blocks made from there (BamSortJob in ps_bam.h) -- a Sorted that is dropped before that gives the buffer back.
+struct Sorted {
+    double ms_sort = -1; const char *route = "host"; std::string *stream = nullptr;
+    bool may_stay = false; void (*resident)(std::string *comp) = nullptr;
+    Sorted() {}
+    Sorted(const Sorted &) = delete;
+    ~Sorted() { if (resident) { try { resident(nullptr); } catch (...) {} } }
+};
+
 // ---- Data (records in d.recs order) -> BGZF file (+ .bai)
-static void write_bam(Data &d, const char *bam_path, bool write_index, int threads, BamStats *stats, int level = 6, bool keep_enc = false)
+static void write_bam(Data &d, const char *bam_path, bool write_index, int threads, BamStats *stats, int level = 6, bool keep_enc = false, Sorted *sorted = nullptr)
 {
+    const bool verbose = std::getenv("PS_VERBOSE") != nullptr;
+    double ms_gather = 0, ms_comp = 0, ms_file = 0, ms_bai = 0;
+    Clock::time_point t0 = Clock::now();
     std::string head;
     head.append("BAM\1", 4); put32(head, (uint32_t)d.text.size()); head += d.text; put32(head, (uint32_t)d.refs.size());
     for (auto &r : d.refs) { put32(head, (uint32_t)r.first.size() + 1); head += r.first; head.push_back('\0'); put32(head, r.second); }
@@ -431,22 +452,45 @@ static void write_bam(Data &d, const char *bam_path, bool write_index, int threa
     for (size_t i = 0; i < all.size(); ++i) uoff[i + 1] = uoff[i] + all[i].len;
     const uint64_t body_bytes = uoff[all.size()];
     const size_t body_blocks = (size_t)((body_bytes + BLK - 1) / BLK);
-    std::string stream((size_t)body_bytes, '\0');
-    {
+    std::string stream;
+    const bool resident = sorted && sorted->resident;
+    if (resident) {
+        if (keep_enc) throw Error("internal: a kept file needs its records on the host");
+    } else if (sorted && sorted->stream) {
+        if (sorted->stream->size() != body_bytes) throw Error("internal: the sorted stream has not the records' size");
+        stream.swap(*sorted->stream);
+    } else {
+        stream.assign((size_t)body_bytes, '\0');
         const int T = threads; const size_t per = (all.size() + (size_t)T - 1) / (size_t)T;
         par(T, T, [&](int t) { const size_t a0 = (size_t)t * per, a1 = std::min(all.size(), a0 + per); for (size_t i = a0; i < a1; ++i) std::memcpy(&stream[(size_t)uoff[i]], d.enc[all[i].part].data() + all[i].off, all[i].len); });
     }
     if (!keep_enc) for (auto &e : d.enc) { e.clear(); e.shrink_to_fit(); }
+    ms_gather = ms_since(t0); t0 = Clock::now();
     const size_t n_blocks = head_blocks + body_blocks;
     std::vector<std::string> comp;
     {
-        std::vector<BgzfSpan> spans(n_blocks);
-        for (size_t k = 0; k < n_blocks; ++k) {
+        std::vector<BgzfSpan> spans(resident ? head_blocks : n_blocks);
+        for (size_t k = 0; k < spans.size(); ++k) {
             if (k < head_blocks) { const size_t a0 = k * BLK; spans[k] = BgzfSpan{head.data() + a0, std::min(BLK, head.size() - a0)}; }
             else { const size_t a0 = (k - head_blocks) * BLK; spans[k] = BgzfSpan{stream.data() + a0, (size_t)std::min<uint64_t>(BLK, body_bytes - a0)}; }
         }
-        bgzf_batch(spans, level, threads, comp);
+        if (resident) {                                          // the header's blocks as ever; the body's from the stream on the device
+            bgzf_batch(spans, level, threads, comp);
+            comp.resize(n_blocks);
+            void (*const make)(std::string *) = sorted->resident;
+            sorted->resident = nullptr;                          // it gives the buffer back itself, whatever happens
+            make(comp.data() + head_blocks);
+        } else bgzf_batch(spans, level, threads, comp);
     }
+    ms_comp = ms_since(t0); t0 = Clock::now();
+    // the times of the stages go to stderr and nowhere else
+    auto stage_line = [&]() {
+        if (!verbose) return;
+        char sort_text[64] = "no sort";
+        if (sorted && sorted->ms_sort >= 0) std::snprintf(sort_text, sizeof sort_text, "sort %.1f ms (%s)", sorted->ms_sort, sorted->route);
+        std::fprintf(stderr, "[parasuite-hip] bam: %zu records, %.1f MB in %zu blocks: %s, offsets + gather %.1f ms%s, compression %.1f ms, file write %.1f ms, .bai %.1f ms\n",
+                     all.size(), body_bytes / 1e6, n_blocks, sort_text, ms_gather, resident ? " (the stream stayed on the device)" : sorted && sorted->stream ? " (the stream came with the sort)" : "", ms_comp, ms_file, ms_bai);
+    };
     std::vector<uint64_t> coff(n_blocks + 1, 0);
     for (size_t k = 0; k < n_blocks; ++k) coff[k + 1] = coff[k] + comp[k].size();
     static const unsigned char eof_block[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -458,7 +502,9 @@ static void write_bam(Data &d, const char *bam_path, bool write_index, int threa
     ok = (std::fclose(o) == 0) && ok;
     if (!ok) throw Error(std::string("short write on ") + bam_path);
     if (stats) { stats->n_in = d.n_in; stats->n_out = all.size(); stats->bam_bytes = coff[n_blocks] + 28; }
-    if (!write_index) return;
+    ms_file = ms_since(t0); t0 = Clock::now();
+    if (sorted && sorted->stream && keep_enc) sorted->stream->swap(stream);     // the kept file's one part
+    if (!write_index) { stage_line(); return; }
     auto voff = [&](uint64_t u) -> uint64_t {           // virtual file offset of body byte u
         if (u == body_bytes && u % BLK == 0) return coff[n_blocks] << 16;      // end of the last full block = start of the EOF block
         return (coff[head_blocks + (size_t)(u / BLK)] << 16) | (u % BLK);
@@ -466,6 +512,8 @@ static void write_bam(Data &d, const char *bam_path, bool write_index, int threa
     Layout lay; lay.vbeg.resize(all.size()); lay.vend.resize(all.size());
     for (size_t i = 0; i < all.size(); ++i) { lay.vbeg[i] = voff(uoff[i]); lay.vend[i] = voff(uoff[i + 1]); }
     write_bai(std::string(bam_path) + ".bai", d, lay);
+    ms_bai = ms_since(t0);
+    stage_line();
 }
 
 static void sort_records(Data &d, bool by_name)
@@ -483,7 +531,40 @@ static void sort_records(Data &d, bool by_name)
         });
 }
 
+// The sort in front of write_bam.  By name: the host, whatever is registered.  By coordinate: the registered hook (ps_bam.h) sorts
+// and gathers in one go, the host reorders d.recs by its permutation on threads and write_bam takes the stream as it is; without
+// a hook, or when the hook leaves the call alone, sort_records and write_bam's own gather.  s.stream must name a string.
+std::atomic<BamSortFn> g_sort_device{nullptr};
+static void sort_for_write(Data &d, bool by_name, int threads, Sorted &s)
+{
+    const Clock::time_point t0 = Clock::now();
+    std::string *stream = s.stream;
+    s.stream = nullptr; s.route = "host";
+    const BamSortFn fn = by_name ? nullptr : g_sort_device.load();
+    if (fn) {
+        std::vector<BgzfSpan> parts(d.enc.size());
+        for (size_t k = 0; k < d.enc.size(); ++k) parts[k] = BgzfSpan{d.enc[k].data(), d.enc[k].size()};
+        std::vector<uint32_t> perm;
+        BamSortJob job{parts.data(), parts.size(), d.recs.data(), d.recs.size(), &perm, stream, s.may_stay};
+        if (fn(job)) {
+            s.resident = job.resident;
+            if (perm.size() != d.recs.size()) throw Error("internal: the device sort returned no permutation");
+            std::vector<Rec> in_order(d.recs.size());
+            const int T = threads; const size_t n = d.recs.size();
+            par(T, T, [&](int t) { for (size_t i = n * (size_t)t / (size_t)T; i < n * ((size_t)t + 1) / (size_t)T; ++i) { if (perm[i] >= n) throw Error("internal: the device sort returned no permutation"); in_order[i] = d.recs[perm[i]]; } });
+            d.recs.swap(in_order);
+            s.stream = job.resident ? nullptr : stream; s.route = "device";
+            s.ms_sort = ms_since(t0);
+            return;
+        }
+    }
+    sort_records(d, by_name);
+    s.ms_sort = ms_since(t0);
+}
+
 }  // namespace
+
+void bam_sort_set_device_hook(BamSortFn fn) { g_sort_device.store(fn); }
 
 static int clamp_threads(int t) { return t < 1 ? 1 : (t > 64 ? 64 : t); }
 
@@ -606,8 +687,14 @@ void BamSink::finish(BamStats *stats, BamFile *keep)
 {
     if (keep && !p->sort) throw Error("internal: only a sorted BAM is kept in memory");
     if (p->sort) {
-        sort_records(p->d, p->by_name);
-        write_bam(p->d, p->path.c_str(), p->index, p->threads, stats, p->level, keep != nullptr);
+        std::string stream; Sorted s; s.stream = &stream; s.may_stay = keep == nullptr;
+        sort_for_write(p->d, p->by_name, p->threads, s);
+        write_bam(p->d, p->path.c_str(), p->index, p->threads, stats, p->level, keep != nullptr, &s);
+        if (keep && s.stream) {                                 // the device route's stream is the kept file's one part
+            uint64_t at = 0;
+            for (Rec &r : p->d.recs) { r.part = 0; r.off = (size_t)at; at += r.len; }
+            p->d.enc.assign(1, std::string()); p->d.enc[0].swap(stream);
+        }
         if (keep) {                                             // the file's records, in file order, for the step that would read it back
             *keep = BamFile();
             keep->sort_order = p->by_name ? "queryname" : "coordinate";
@@ -631,8 +718,9 @@ void sam_to_bam(const char *sam_path, const char *bam_path, int min_mapq, bool s
     files.refuse_inputs({sam_path}, "ps_sam_to_bam: ");
     Data d;
     load_sam(sam_path, min_mapq, threads, d);
-    if (sort_by_coordinate) { header_sorted(d.text, "coordinate"); sort_records(d, false); }
-    write_bam(d, t.c_str(), write_index, threads, stats);
+    std::string stream; Sorted s; s.stream = &stream; s.may_stay = true;
+    if (sort_by_coordinate) { header_sorted(d.text, "coordinate"); sort_for_write(d, false, threads, s); } else s.stream = nullptr;
+    write_bam(d, t.c_str(), write_index, threads, stats, 6, false, &s);
     files.publish_all(); files.keep();
 }
 
@@ -662,8 +750,9 @@ void bam_sort(const char *in_bam, const char *out_bam, bool by_name, int threads
     Data d;
     load_bam(in_bam, threads, d, nullptr, nullptr);
     header_sorted(d.text, by_name ? "queryname" : "coordinate");
-    sort_records(d, by_name);
-    write_bam(d, t.c_str(), false, threads, stats);
+    std::string stream; Sorted s; s.stream = &stream; s.may_stay = true;
+    sort_for_write(d, by_name, threads, s);
+    write_bam(d, t.c_str(), false, threads, stats, 6, false, &s);
     files.publish_all(); files.keep();
 }
 
@@ -722,6 +811,37 @@ void load_records(const char *path, int threads, BamFile &out)
     out = BamFile();
     out.sort_order = header_sort_order(d.text);
     out.text.swap(d.text); out.refs.swap(d.refs); out.enc.swap(d.enc); out.recs.swap(d.recs);
+}
+
+void scan_records(const char *records, uint64_t n_bytes, std::vector<BamRec> &recs)
+{
+    recs.clear();
+    const uint8_t *b = (const uint8_t *)records;
+    uint64_t p = 0;
+    while (p < n_bytes) {
+        const uint64_t number = recs.size() + 1;
+        if (n_bytes - p < 4) throw Error("record " + std::to_string(number) + " runs past the end of the buffer");
+        const uint32_t bs = rd32(b + p);
+        if (bs < 32) throw Error("record " + std::to_string(number) + " has a block_size of " + std::to_string(bs) + ", below the 32 fixed bytes");
+        if ((uint64_t)bs + 4 > n_bytes - p) throw Error("record " + std::to_string(number) + " runs past the end of the buffer");
+        Rec r; r.part = 0; r.off = (size_t)p; r.len = 4 + (size_t)bs;
+        r.ref = (int32_t)rd32(b + p + 4); r.pos = (int32_t)rd32(b + p + 8); r.end = r.pos < 0x7fffffff ? r.pos + 1 : r.pos; r.flag = rd32(b + p + 16) >> 16;
+        recs.push_back(r);
+        p += 4 + (uint64_t)bs;
+    }
+}
+
+void sort_records_host(const char *records, std::vector<BamRec> &recs, int threads, char *dst)
+{
+    threads = clamp_threads(threads);
+    std::stable_sort(recs.begin(), recs.end(), [](const Rec &x, const Rec &y) {
+        const uint32_t a = (uint32_t)x.ref, c = (uint32_t)y.ref;
+        return a != c ? a < c : x.pos < y.pos;
+    });
+    std::vector<uint64_t> uoff(recs.size() + 1, 0);
+    for (size_t i = 0; i < recs.size(); ++i) uoff[i + 1] = uoff[i] + recs[i].len;
+    const size_t n = recs.size();
+    par(threads, threads, [&](int t) { for (size_t i = n * (size_t)t / (size_t)threads; i < n * ((size_t)t + 1) / (size_t)threads; ++i) std::memcpy(dst + uoff[i], records + recs[i].off, recs[i].len); });
 }
 
 void flatten_records(const BamFile &f, unsigned columns, const std::vector<int32_t> *rows, int threads, RecTable &out)

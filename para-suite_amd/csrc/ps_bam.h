@@ -15,6 +15,24 @@ struct BgzfSpan { const char *p; size_t n; };
 typedef void (*BgzfBatchFn)(const BgzfSpan *spans, size_t n_spans, std::string *comp);
 void bgzf_set_device_compressor(BgzfBatchFn fn);
 void bgzf_host_compress(const BgzfSpan *spans, size_t n_spans, int level, int threads, std::string *comp);   // the host path itself, whatever is registered
+// The coordinate sort of every writer below (BamSink::finish, sam_to_bam, bam_sort) is one std::stable_sort on one thread plus a gather
+// of the records into the file's stream on host threads.  A hook registered here takes both instead (ps_bamsort.hip: the key, the
+// radix sort and the gather on the device; this file and ps_bam.cpp stay free of HIP): it fills perm, the sorted order, and stream,
+// the records in that order back to back.  It returns false when it leaves the call to the host route (and counts that), throws
+// ps::Error on a device error -- the writing call fails with it, there is no fallback.  Null: the host route.  The name sort never asks.
+struct BamRec;
+struct BamSortJob {
+    const BgzfSpan *parts; size_t n_parts;        // the buffers the records lie in; recs[i].part names one
+    const BamRec *recs; size_t n_recs;
+    std::vector<uint32_t> *perm; std::string *stream;
+    // may_stay (in): the caller can do without the stream on the host.  The hook may then leave the sorted stream on the device (the one
+    // the BGZF switch names), leave `stream` empty and set `resident`: resident(comp) makes the BGZF members of the stream cut at 0xff00
+    // bytes, comp[k] for block k, and gives the device buffer back, also when it throws; resident(nullptr) only gives it back.  The
+    // caller calls it exactly once.
+    bool may_stay = false; void (*resident)(std::string *comp) = nullptr;
+};
+typedef bool (*BamSortFn)(BamSortJob &job);
+void bam_sort_set_device_hook(BamSortFn fn);
 // one encoded BAM record inside a buffer of records: reference id, 0-based position and end, flag, byte range [off, off + len)
 struct BamRec { int32_t ref; int32_t pos; int32_t end; uint32_t flag; size_t off, len; int part; };
 // The record layout (SAMv1 4.2), for every route that makes records -- SAM text (sam_to_bam) and the mapper's hits (ps_map_to_bam).
@@ -68,6 +86,11 @@ struct BamFile {
     const uint8_t *rec(size_t i) const { return (const uint8_t *)enc[(size_t)recs[i].part].data() + recs[i].off; }   // block_size first
 };
 void load_records(const char *sam_or_bam, int threads, BamFile &out);
+// BAM records back to back, block_size first -> one BamRec each (ref, pos, off, len; part 0).  A record that runs past n_bytes or a
+// block_size below 32 throws with the record's number (1-based).
+void scan_records(const char *records, uint64_t n_bytes, std::vector<BamRec> &recs);
+// the host route on its own: recs into coordinate order (std::stable_sort), their bytes gathered into dst on `threads` threads
+void sort_records_host(const char *records, std::vector<BamRec> &recs, int threads, char *dst);
 // The record table: the fields of the records of a BamFile as flat arrays, for the analysis modes' kernels.
 // ref, pos, flag and l_seq always; the other columns by mask.  BAM conventions throughout: pos 0-based (a kernel that wants
 // htsjdk's 1-based start adds one), ref -1 unplaced, CIGAR words len<<4|op with MIDNSHP=X, bases as nibbles =ACMGRSVTWYHKDBN.

@@ -16,5 +16,10 @@ void bgzf_set_device(int device);
 // at most PS_BGZF_PIECE input bytes (default 64 MiB, at least one block); PS_BGZF_BTYPE=stored|fixed|dynamic restricts the
 // encodings (tests).  Calls are serialised: they share one set of staging and device buffers.
 void bgzf_device_compress(const BgzfSpan *spans, size_t n_spans, int device, std::string *comp, BgzfStats *stats);
+// The same for a stream that lies on `device` already (the sorted records of ps_bamsort.hip): d_stream[0, n_bytes) cut at 0xff00
+// bytes -> comp[k], (n_bytes + 0xff00 - 1) / 0xff00 members.  A round's kernel reads the stream in place: no staging copy, no
+// upload; sizes, CRCs and packed images come down as before.  The bytes are the ones bgzf_device_compress makes of the same input.
+void bgzf_device_compress_resident(const uint8_t *d_stream, uint64_t n_bytes, int device, std::string *comp, BgzfStats *stats);
+int bgzf_device_current();                      // the switch: -1 off
 
 }  // namespace ps

@@ -82,22 +82,6 @@ size_t blocks_per_round()
     return std::max<size_t>(1, std::min<size_t>(piece / DF_BLOCK, 16384));
 }
 
-// f(begin, end) over [0, n) on up to `threads` threads
-template <class F> void ranges(size_t n, int threads, F f)
-{
-    const size_t nt = std::min<size_t>((size_t)std::max(1, threads), n);
-    if (nt <= 1) { if (n) f((size_t)0, n); return; }
-    std::vector<std::thread> th;
-    for (size_t t = 0; t < nt; ++t) th.emplace_back([&, t]() { f(n * t / nt, n * (t + 1) / nt); });
-    for (auto &x : th) x.join();
-}
-
-struct DeviceScope {                                // the calling thread's device, put back on the way out
-    int before = -1;
-    explicit DeviceScope(int device) { (void)hipGetDevice(&before); PS_HIP(hipSetDevice(device)); }
-    ~DeviceScope() { if (before >= 0) (void)hipSetDevice(before); }
-};
-
 void device_batch(const BgzfSpan *spans, size_t n_spans, std::string *comp) { bgzf_device_compress(spans, n_spans, g_device, comp, nullptr); }
 
 // PS_BGZF_GPU=<device>: read once, when the library is loaded; a device that is not there fails the first writing call
@@ -124,10 +108,15 @@ void bgzf_set_device(int device)
     bgzf_set_device_compressor(&device_batch);
 }
 
-void bgzf_device_compress(const BgzfSpan *spans, size_t n_spans, int device, std::string *comp, BgzfStats *stats)
+int bgzf_device_current() { return g_device; }
+
+// spans on the host (staged and uploaded round by round), or -- spans null -- d_stream[0, n_bytes) on `device` cut at 0xff00 bytes:
+// a round's kernel then reads the stream where it lies, and neither the staging copy nor the upload happens
+static void compress_rounds(const BgzfSpan *spans, size_t n_spans, const uint8_t *d_stream, uint64_t n_bytes, int device, std::string *comp, BgzfStats *stats)
 {
     BgzfStats st;
-    for (size_t k = 0; k < n_spans; ++k) if (spans[k].n > (size_t)DF_BLOCK) throw Error("ps_bgzf: a span of more than 0xff00 bytes");
+    auto n_of = [&](size_t k) { return spans ? spans[k].n : (size_t)std::min<uint64_t>((uint64_t)DF_BLOCK, n_bytes - (uint64_t)k * DF_BLOCK); };
+    for (size_t k = 0; spans && k < n_spans; ++k) if (spans[k].n > (size_t)DF_BLOCK) throw Error("ps_bgzf: a span of more than 0xff00 bytes");
     if (n_spans) {
         const uint32_t allow = allowed_encodings();
         const size_t per_round = std::min(blocks_per_round(), n_spans);
@@ -142,7 +131,8 @@ void bgzf_device_compress(const BgzfSpan *spans, size_t n_spans, int device, std
         Buffers &b = buffers();
         if (b.device != device) { b.release(); b.device = device; }
         const size_t in_cap = per_round * (size_t)DF_BLOCK, out_cap = per_round * (size_t)DF_OUT_STRIDE;
-        if (b.in.n < in_cap) { b.in.alloc(in_cap); b.tok.alloc(in_cap); }
+        if (spans && b.in.n < in_cap) b.in.alloc(in_cap);
+        if (b.tok.n < in_cap) b.tok.alloc(in_cap);
         if (b.out.n < out_cap) { b.out.alloc(out_cap); b.packed.alloc(out_cap); }
         if (b.offs.n < per_round + 1) { b.offs.alloc(per_round + 1); b.res.alloc(per_round); }
         // page-locked staging: input | offsets | results | images
@@ -155,22 +145,23 @@ void bgzf_device_compress(const BgzfSpan *spans, size_t n_spans, int device, std
         for (size_t r0 = 0; r0 < n_spans; r0 += per_round) {
             const size_t nb = std::min(per_round, n_spans - r0);
             h_offs[0] = 0;
-            for (size_t k = 0; k < nb; ++k) h_offs[k + 1] = h_offs[k] + spans[r0 + k].n;
+            for (size_t k = 0; k < nb; ++k) h_offs[k + 1] = h_offs[k] + n_of(r0 + k);
             const size_t bytes = (size_t)h_offs[nb];
-            ranges(nb, bytes >= ((size_t)4 << 20) ? 8 : 1, [&](size_t k0, size_t k1) { for (size_t k = k0; k < k1; ++k) if (spans[r0 + k].n) std::memcpy(pin + h_offs[k], spans[r0 + k].p, spans[r0 + k].n); });
+            if (spans) ranges(nb, bytes >= ((size_t)4 << 20) ? 8 : 1, [&](size_t k0, size_t k1) { for (size_t k = k0; k < k1; ++k) if (spans[r0 + k].n) std::memcpy(pin + h_offs[k], spans[r0 + k].p, spans[r0 + k].n); });
             const HostClock::time_point t_dev = HostClock::now();
-            if (bytes) b.in.upload(pin, bytes, sg.s);
+            if (spans && bytes) b.in.upload(pin, bytes, sg.s);
+            const uint8_t *d_in = spans ? b.in.p : d_stream + (uint64_t)r0 * DF_BLOCK;      // the round's first byte: the offsets count from it
             b.offs.upload(h_offs, nb + 1, sg.s);
             PS_HIP(hipMemsetAsync(b.res.p, 0, nb * sizeof(DfResult), sg.s));
             ev.start(sg.s);
-            hipLaunchKernelGGL(k_bgzf, dim3((unsigned)nb), dim3(DF_NL), 0, sg.s, b.in.p, b.offs.p, (uint32_t)nb, b.out.p, b.tok.p, b.res.p, allow);
+            hipLaunchKernelGGL(k_bgzf, dim3((unsigned)nb), dim3(DF_NL), 0, sg.s, d_in, b.offs.p, (uint32_t)nb, b.out.p, b.tok.p, b.res.p, allow);
             PS_HIP(hipGetLastError());
             ev.stop(sg.s);
             b.res.download(h_res, nb, sg.s);
             PS_HIP(hipStreamSynchronize(sg.s));
             st.kernel_ms += ev.ms();
             for (size_t k = 0; k < nb; ++k)
-                if (h_res[k].bytes == 0 || h_res[k].bytes > spans[r0 + k].n + 5 || h_res[k].btype > 2) throw Error("ps_bgzf: the device returned no valid block");
+                if (h_res[k].bytes == 0 || h_res[k].bytes > n_of(r0 + k) + 5 || h_res[k].btype > 2) throw Error("ps_bgzf: the device returned no valid block");
             // the sizes are known now: the images are packed on the device (each at a word boundary) and only they come down
             h_offs[0] = 0;
             for (size_t k = 0; k < nb; ++k) h_offs[k + 1] = h_offs[k] + (((uint64_t)h_res[k].bytes + 3) & ~(uint64_t)3);
@@ -187,7 +178,7 @@ void bgzf_device_compress(const BgzfSpan *spans, size_t n_spans, int device, std
             ranges(nb, bytes >= ((size_t)4 << 20) ? 8 : 1, [&](size_t k0, size_t k1) {
                 for (size_t k = k0; k < k1; ++k) {
                     const DfResult &r = h_res[k];
-                    const uint32_t n = (uint32_t)spans[r0 + k].n, total = 18 + r.bytes + 8;
+                    const uint32_t n = (uint32_t)n_of(r0 + k), total = 18 + r.bytes + 8;
                     const unsigned char head[18] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0, (unsigned char)((total - 1) & 0xff), (unsigned char)((total - 1) >> 8)};
                     unsigned char tail[8];
                     for (int j = 0; j < 4; ++j) { tail[j] = (unsigned char)(r.crc >> (8 * j)); tail[4 + j] = (unsigned char)(n >> (8 * j)); }
@@ -199,14 +190,25 @@ void bgzf_device_compress(const BgzfSpan *spans, size_t n_spans, int device, std
             for (size_t k = 0; k < nb; ++k) {
                 const DfResult &r = h_res[k];
                 ++st.n_blocks; st.n_stored += r.btype == 0; st.n_fixed += r.btype == 1; st.n_dynamic += r.btype == 2;
-                st.in_bytes += spans[r0 + k].n; st.out_bytes += 18 + r.bytes + 8;
+                st.in_bytes += n_of(r0 + k); st.out_bytes += 18 + r.bytes + 8;
             }
         }
         if (verbose)
-            std::fprintf(stderr, "[parasuite-hip] bgzf: %u blocks, %.1f MB -> %.1f MB on device %d in %.1f ms: waited %.1f ms for the compressor, device part %.1f ms (kernels %.1f ms), the rest staging and assembly\n",
-                         st.n_blocks, st.in_bytes / 1e6, st.out_bytes / 1e6, device, ms_since(t_begin) + ms_lock, ms_lock, ms_device, st.kernel_ms);
+            std::fprintf(stderr, "[parasuite-hip] bgzf: %u blocks%s, %.1f MB -> %.1f MB on device %d in %.1f ms: waited %.1f ms for the compressor, device part %.1f ms (kernels %.1f ms), the rest staging and assembly\n",
+                         st.n_blocks, spans ? "" : " of a stream that lay on the device", st.in_bytes / 1e6, st.out_bytes / 1e6, device, ms_since(t_begin) + ms_lock, ms_lock, ms_device, st.kernel_ms);
     }
     if (stats) *stats = st;
+}
+
+void bgzf_device_compress(const BgzfSpan *spans, size_t n_spans, int device, std::string *comp, BgzfStats *stats)
+{
+    static const BgzfSpan none{nullptr, 0};
+    compress_rounds(spans ? spans : &none, n_spans, nullptr, 0, device, comp, stats);
+}
+
+void bgzf_device_compress_resident(const uint8_t *d_stream, uint64_t n_bytes, int device, std::string *comp, BgzfStats *stats)
+{
+    compress_rounds(nullptr, (size_t)((n_bytes + DF_BLOCK - 1) / DF_BLOCK), d_stream, n_bytes, device, comp, stats);
 }
 
 }  // namespace ps

@@ -5,6 +5,7 @@
 #include <chrono>
 #include <cstdio>
 #include <map>
+#include <thread>
 #include "ps_host.h"
 #include "ps_bam.h"
 #include "ps_outfiles.h"
@@ -34,6 +35,23 @@ template <class F> void cub_call(hipStream_t s, F f)       // f(temporary storag
     PS_HIP(hipStreamSynchronize(s));
 }
 inline unsigned blocks_for(size_t n, unsigned per = 256) { return (unsigned)std::max<size_t>(1, (n + per - 1) / per); }
+
+struct DeviceScope {                                // the calling thread's device, put back on the way out
+    int before = -1;
+    explicit DeviceScope(int device) { (void)hipGetDevice(&before); PS_HIP(hipSetDevice(device)); }
+    DeviceScope(const DeviceScope &) = delete;
+    ~DeviceScope() { if (before >= 0) (void)hipSetDevice(before); }
+};
+
+// f(begin, end) over [0, n) on up to `threads` threads
+template <class F> void ranges(size_t n, int threads, F f)
+{
+    const size_t nt = std::min<size_t>((size_t)std::max(1, threads), n);
+    if (nt <= 1) { if (n) f((size_t)0, n); return; }
+    std::vector<std::thread> th;
+    for (size_t t = 0; t < nt; ++t) th.emplace_back([&, t]() { f(n * t / nt, n * (t + 1) / nt); });
+    for (auto &x : th) x.join();
+}
 
 using HostClock = std::chrono::steady_clock;
 inline double ms_since(HostClock::time_point t) { return std::chrono::duration<double, std::milli>(HostClock::now() - t).count(); }

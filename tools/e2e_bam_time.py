@@ -2,9 +2,11 @@
 (index load + search + records + BGZF + file written), unsorted and sorted + indexed, zlib level 1 on 16 threads against the
 device compressor.  PS_VERBOSE=1 prints the stage times of each call, where the compress launches queue behind the search.
 SWITCH=records alternates the BAM records' device route (ps_bam_records_device) instead, BGZF on host zlib throughout: the off runs
-of the same command are the reference.
+of the same command are the reference.  SWITCH=sort alternates the coordinate sort's device route (ps_bam_sort_device) the same way, on
+the sorted + indexed call alone (the unsorted file never sorts); the stage lines of both routes come with PS_VERBOSE.  SWITCH=sort+bgzf
+is the same with the device compressor on throughout, so that the on runs leave the sorted stream on the device for it.
 
-    python tools/e2e_bam_time.py [N_READS=10000000] [GENOME_MBP=1000] [WORKDIR=/tmp] [SWITCH=bgzf|records]"""
+    python tools/e2e_bam_time.py [N_READS=10000000] [GENOME_MBP=1000] [WORKDIR=/tmp] [SWITCH=bgzf|records|sort|sort+bgzf]"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, 'para-suite_amd'); sys.path.insert(0, '.')
@@ -14,7 +16,11 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
 mbp = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
 work = sys.argv[3] if len(sys.argv) > 3 else '/tmp'
 switch = sys.argv[4] if len(sys.argv) > 4 else 'bgzf'
-assert switch in ('bgzf', 'records')
+assert switch in ('bgzf', 'records', 'sort', 'sort+bgzf')
+resident = switch == 'sort+bgzf'
+if resident:
+    switch = 'sort'
+    capi.ps_bgzf_device(0)
 p = lambda x: os.path.join(work, 'e2e_bam.' + x)
 dev = torch.device('cuda', 0)
 contigs = bench.gen_genome(torch, dev, mbp * 1_000_000, 8, 0x5EED0002)
@@ -34,14 +40,19 @@ with open(p('errorprofile'), 'w') as f:
 open(p('indelprofile'), 'w').write('2.1E-5\t5.9E-4')
 os.environ['PS_BAM_LEVEL'] = '1'
 os.environ['PS_VERBOSE'] = os.environ.get('E2E_VERBOSE', '1')
-for kw in (dict(min_mapq=10), dict(min_mapq=10, sort_by_coordinate=True, write_index=True)):
+LABEL = dict(bgzf=('zlib level 1 on 16 threads', 'BGZF on device 0'), records=('records built on 16 host threads', 'records built on the device'),
+             sort=('records sorted and gathered on the host' + ', BGZF on device 0' * resident, 'records sorted and gathered on device 0' + ', the stream left there for BGZF on device 0' * resident))
+for kw in (dict(min_mapq=10), dict(min_mapq=10, sort_by_coordinate=True, write_index=True))[1 if switch == 'sort' else 0:]:
     for device in (-1, 0) * 5:                       # the first pair warms the page cache and the page-locked buffers up; four timed pairs
         if switch == 'bgzf':
             capi.ps_bgzf_device(device)
-        else:
+        elif switch == 'records':
             capi.ps_bam_records_device(device >= 0)
+        else:
+            capi.ps_bam_sort_device(device)
         t = time.time(); st = capi.ps_map_to_bam(16, '-1', p('errorprofile'), p('indelprofile'), p('fa'), p('fq'), p('bam'), **kw); dt = time.time() - t
         print('ps_map_to_bam %s, %s: %.2fs, %d of %d records kept, BAM %.0f MB'
-              % (kw, ('BGZF on device 0' if device >= 0 else 'zlib level 1 on 16 threads') if switch == 'bgzf' else ('records built on the device' if device >= 0 else 'records built on 16 host threads'), dt, st['n_out'], st['n_in'], st['bam_bytes'] / 1e6), flush=True)
+              % (kw, LABEL[switch][device >= 0], dt, st['n_out'], st['n_in'], st['bam_bytes'] / 1e6), flush=True)
 capi.ps_bgzf_device(-1)
 capi.ps_bam_records_device(0)
+capi.ps_bam_sort_device(-1)

@@ -720,7 +720,7 @@ int64_t ps_batch_bam_records(ps_batch *b, int min_mapq, int on_device, int threa
  * pos ^ 0x80000000 low: unplaced records last, positions as signed numbers) is sorted there by a stable radix sort, a hand-written
  * kernel gathers the records into the sorted stream, and the permutation and the stream come down (csrc/ps_bamsort.h states the
  * key and the gather once for host and device).  Block cuts, compression, the file and the .bai are made as before, from the same
- * bytes: the files are the same with the switch on or off.  The name sort stays on the host.  The host route is taken, and counted
+ * bytes: the files are the same with the switch on or off.  The name sort has a switch of its own (below).  The host route is taken, and counted
  * in n_calls_host, when there are 2^32 records or more or when the call would need more than PS_BAM_SORT_MAX_MB (default 32768)
  * of device memory.  Returns non-zero with the last error set when there is no such device.  A later HIP failure fails the writing
  * call: there is no fallback.  PS_BAM_SORT_GPU=<device> in the environment is the same as the call; it is read once, when the
@@ -742,6 +742,35 @@ int     ps_bam_sort_info(ps_bam_sort_stats *out);
  * than cap bytes the call fails and writes nothing; dst is untouched on any error.  n_bytes == 0 writes nothing and returns 0.
  * stats (struct_size must hold sizeof(ps_bam_sort_stats)): this call alone. */
 int64_t ps_bam_sort_records(const void *records, uint64_t n_bytes, int device, int threads, void *dst, uint64_t cap, ps_bam_sort_stats *stats /* may be NULL */);
+
+/* ---- the name sort of BAM records on the device ------------------------------------------------------------------------
+ * Every name-sorted BAM the library writes (ps_bam_sort with by_name, `samtools sort -n` through the shim, the name-sorted
+ * transcript pass of ps_map_route / ps_map_route_opts) orders its records with one stable sort on one host thread whose comparator
+ * walks two names byte by byte, digit runs compared as numbers, then first of pair before second.  This switch is that sort's own:
+ * ps_bam_sort_device and PS_BAM_SORT_GPU keep meaning the coordinate sort alone, and neither sort ever asks the other's switch.
+ * device >= 0: the records go up as they do for the coordinate sort; a kernel writes a normalised key per name whose bytes order
+ * exactly as the comparator does (csrc/ps_namesort.h states it once for host and device: a byte that is no digit as itself, a digit
+ * run as 0x30, the length without leading zeros, the digits left; zero padding; the pair bits in the row's last byte), as a row of
+ * key_words 32-bit words, column-major; from the last column to the first, a stable radix sort orders the records by one column --
+ * columns in which all rows agree are skipped, n_passes counts the others; then the coordinate route's gather, download and -- when
+ * ps_bgzf_device names the same device and the call keeps no records -- resident hand-over (n_resident).  The files are the same
+ * with the switch on or off.  The host route is taken, and counted in n_calls_host, when there are 2^32 records or more, when a
+ * record's name does not end inside the record, or when the call would need more than PS_BAM_SORT_MAX_MB of device memory (the
+ * coordinate route's need and 4 * key_words bytes per record).  Returns non-zero with the last error set when there is no such
+ * device.  A later HIP failure fails the writing call: there is no fallback.  -1 turns the route off, gives back its buffers (but
+ * not those the coordinate switch still needs) and, like every setting, resets this switch's counters alone.
+ * PS_BAM_NAME_SORT_GPU=<device> in the environment is the same as the call; it is read once, when the library is loaded.
+ * ps_bam_name_sort_info: summed over the process since the switch was last set, key_words of the last device call; the route's
+ * five times in ms (records up, the look at the names + rows, column sorts, offsets + gather, permutation + stream down). */
+int     ps_bam_name_sort_device(int device);
+typedef struct { uint32_t struct_size, on_device; uint64_t n_records, bytes, n_calls_device, n_calls_host, n_resident;
+                 uint32_t key_words, pad_; uint64_t n_passes;
+                 double ms_upload, ms_keys, ms_sort, ms_gather, ms_download; } ps_bam_name_sort_stats;
+int     ps_bam_name_sort_info(ps_bam_name_sort_stats *out);
+/* ps_bam_sort_records for the name order, with its contract: device >= 0 the device route whatever the switch says, -1 the
+ * library's host route (the stable sort by the comparator and the pair bits, the gather on `threads` threads).  Beyond
+ * ps_bam_sort_records' checks, a record whose name does not end inside it fails the call with the record's number. */
+int64_t ps_bam_name_sort_records(const void *records, uint64_t n_bytes, int device, int threads, void *dst, uint64_t cap, ps_bam_name_sort_stats *stats /* may be NULL */);
 
 #ifdef __cplusplus
 }

@@ -176,6 +176,13 @@ class BamSortStats(C.Structure):
                _fields(C.c_double, "ms_upload", "ms_sort", "ms_gather", "ms_download")
 
 
+class BamNameSortStats(C.Structure):
+    _fields_ = _fields(C.c_uint32, "struct_size", "on_device") + \
+               _fields(C.c_uint64, "n_records", "bytes", "n_calls_device", "n_calls_host", "n_resident") + \
+               _fields(C.c_uint32, "key_words", "pad_") + [("n_passes", C.c_uint64)] + \
+               _fields(C.c_double, "ms_upload", "ms_keys", "ms_sort", "ms_gather", "ms_download")
+
+
 # every struct typedef of the header -> its mirror (ps_aln and ps_hit are read as numpy records)
 STRUCTS = {"ps_search_opts": SearchOpts, "ps_index_info": IndexInfo, "ps_aln": ALN_DTYPE, "ps_hit": HIT_DTYPE, "ps_timing": Timing,
            "ps_kstats": KStats, "ps_collapse_info": CollapseInfo, "ps_bam_stats": BamStats, "ps_profile_stats": ProfileStats, "ps_cluster_stats": ClusterStats,
@@ -183,7 +190,8 @@ STRUCTS = {"ps_search_opts": SearchOpts, "ps_index_info": IndexInfo, "ps_aln": A
            "ps_route_opts": RouteOpts, "ps_route_stats": RouteStats, "ps_route_opts2": RouteOpts2, "ps_resident_opts": ResidentOpts,
            "ps_resident_stats": ResidentStats, "ps_benchmark_stats": BenchmarkStats, "ps_simulate_opts": SimulateOpts,
            "ps_simulate_stats": SimulateStats, "ps_fetch_stats": FetchStats, "ps_bgzf_stats": BgzfStats,
-           "ps_bam_records_stats": BamRecordsStats, "ps_bam_sort_stats": BamSortStats}
+           "ps_bam_records_stats": BamRecordsStats, "ps_bam_sort_stats": BamSortStats,
+           "ps_bam_name_sort_stats": BamNameSortStats}
 
 # ---- the functions of the header, in its order: name -> (restype, argtypes) ----
 # int, int64_t, uint64_t, double, const char *; _PTR: ps_ctx *, ps_batch * and every buffer handed over as an address
@@ -267,6 +275,9 @@ SIGNATURES = {
     "ps_bam_sort_device": (_I, [_I]),
     "ps_bam_sort_info": (_I, [_P(BamSortStats)]),
     "ps_bam_sort_records": (_I64, [_PTR, _U64, _I, _I, _PTR, _U64, _P(BamSortStats)]),
+    "ps_bam_name_sort_device": (_I, [_I]),
+    "ps_bam_name_sort_info": (_I, [_P(BamNameSortStats)]),
+    "ps_bam_name_sort_records": (_I64, [_PTR, _U64, _I, _I, _PTR, _U64, _P(BamNameSortStats)]),
 }
 EXPORTS = list(SIGNATURES)
 
@@ -677,19 +688,42 @@ def ps_bam_sort_info():
     return _stats(lib().ps_bam_sort_info, BamSortStats)
 
 
-def ps_bam_sort_records(records, device=0, threads=16, cap=None, guard=0):
-    """BAM records back to back -> (the same records in coordinate order, the call's ps_bam_sort_stats as a dict); device -1: the
-    library's host route.  cap: the capacity told to the library (default: what the records take); guard: bytes of 0xee kept
-    behind cap, returned as a third value so that a caller can see them untouched"""
+def _sort_records(fn, stats_cls, records, device, threads, cap, guard):
+    """the staged sort of either order: (the sorted records, the call's stats as a dict[, the guard bytes])"""
     records = bytes(records)
     cap = len(records) if cap is None else int(cap)
     dst = C.create_string_buffer(b"\xee" * (cap + guard), cap + guard) if cap + guard else C.create_string_buffer(1)
-    st = BamSortStats(struct_size=C.sizeof(BamSortStats))
-    n = lib().ps_bam_sort_records(records, len(records), int(device), int(threads), dst, cap, C.byref(st))
+    st = stats_cls(struct_size=C.sizeof(stats_cls))
+    n = fn(records, len(records), int(device), int(threads), dst, cap, C.byref(st))
     if n < 0:
         raise PsError(lib().ps_last_error().decode())
     out = dst.raw[:n], _struct_dict(st)
     return out + (dst.raw[cap:cap + guard],) if guard else out
+
+
+def ps_bam_sort_records(records, device=0, threads=16, cap=None, guard=0):
+    """BAM records back to back -> (the same records in coordinate order, the call's ps_bam_sort_stats as a dict); device -1: the
+    library's host route.  cap: the capacity told to the library (default: what the records take); guard: bytes of 0xee kept
+    behind cap, returned as a third value so that a caller can see them untouched"""
+    return _sort_records(lib().ps_bam_sort_records, BamSortStats, records, device, threads, cap, guard)
+
+
+def ps_bam_name_sort_device(device):
+    """the switch of the name sort's device route (`samtools sort -n`'s order): -1 the host (the default), device >= 0: every
+    name-sorted BAM this process writes from now on is sorted and gathered on it; setting it, either way, resets the counters of
+    ps_bam_name_sort_info and leaves the coordinate sort's switch alone"""
+    _chk(lib().ps_bam_name_sort_device(int(device)))
+
+
+def ps_bam_name_sort_info():
+    """ps_bam_name_sort_stats as a dict: what the name sort has done since its switch was last set"""
+    return _stats(lib().ps_bam_name_sort_info, BamNameSortStats)
+
+
+def ps_bam_name_sort_records(records, device=0, threads=16, cap=None, guard=0):
+    """BAM records back to back -> (the same records in name order, the call's ps_bam_name_sort_stats as a dict); device -1: the
+    library's host route.  cap and guard: as ps_bam_sort_records takes them"""
+    return _sort_records(lib().ps_bam_name_sort_records, BamNameSortStats, records, device, threads, cap, guard)
 
 
 def _map_args(threads, mm, error_profile, indel_profile, ref_fa, fastq, out):

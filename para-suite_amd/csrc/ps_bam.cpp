@@ -6,7 +6,7 @@
 // BGZF blocks of at most 64 KiB with the BC extra field, BAM records, binning index with 16 kb linear index);
 // integer tags take the smallest type as htslib's SAM parser does.  Host code only (zlib), no device work in this file: the BGZF
 // blocks of every writer go through bgzf_batch(), which hands them to the device compressor when one is registered (ps_bam.h), and
-// every coordinate sort through sort_for_write(), which hands sort and gather to the registered hook (ps_bamsort.hip) the same way.
+// every sort through sort_for_write(), which hands sort and gather to the hook registered for its order (ps_bamsort.hip) the same way.
 // PS_VERBOSE: write_bam prints one line with the ms of its stages (sort, offsets + gather, compression, file write, .bai) on stderr.
 #include <zlib.h>
 #include <algorithm>
@@ -531,16 +531,16 @@ static void sort_records(Data &d, bool by_name)
         });
 }
 
-// The sort in front of write_bam.  By name: the host, whatever is registered.  By coordinate: the registered hook (ps_bam.h) sorts
-// and gathers in one go, the host reorders d.recs by its permutation on threads and write_bam takes the stream as it is; without
-// a hook, or when the hook leaves the call alone, sort_records and write_bam's own gather.  s.stream must name a string.
-std::atomic<BamSortFn> g_sort_device{nullptr};
+// The sort in front of write_bam.  Each order has a hook of its own (ps_bam.h): the registered one sorts and gathers in one go, the
+// host reorders d.recs by its permutation on threads and write_bam takes the stream as it is; without a hook, or when the hook
+// leaves the call alone, sort_records and write_bam's own gather.  s.stream must name a string.
+std::atomic<BamSortFn> g_sort_device{nullptr}, g_name_sort_device{nullptr};
 static void sort_for_write(Data &d, bool by_name, int threads, Sorted &s)
 {
     const Clock::time_point t0 = Clock::now();
     std::string *stream = s.stream;
     s.stream = nullptr; s.route = "host";
-    const BamSortFn fn = by_name ? nullptr : g_sort_device.load();
+    const BamSortFn fn = by_name ? g_name_sort_device.load() : g_sort_device.load();
     if (fn) {
         std::vector<BgzfSpan> parts(d.enc.size());
         for (size_t k = 0; k < d.enc.size(); ++k) parts[k] = BgzfSpan{d.enc[k].data(), d.enc[k].size()};
@@ -565,6 +565,8 @@ static void sort_for_write(Data &d, bool by_name, int threads, Sorted &s)
 }  // namespace
 
 void bam_sort_set_device_hook(BamSortFn fn) { g_sort_device.store(fn); }
+void bam_name_sort_set_device_hook(BamSortFn fn) { g_name_sort_device.store(fn); }
+int bam_name_cmp(const char *a, const char *b) { return strnum_cmp(a, b); }
 
 static int clamp_threads(int t) { return t < 1 ? 1 : (t > 64 ? 64 : t); }
 
@@ -831,17 +833,33 @@ void scan_records(const char *records, uint64_t n_bytes, std::vector<BamRec> &re
     }
 }
 
-void sort_records_host(const char *records, std::vector<BamRec> &recs, int threads, char *dst)
+// the sorted records' bytes into dst, back to back, on threads
+static void gather_records(const char *records, const std::vector<BamRec> &recs, int threads, char *dst)
 {
     threads = clamp_threads(threads);
-    std::stable_sort(recs.begin(), recs.end(), [](const Rec &x, const Rec &y) {
-        const uint32_t a = (uint32_t)x.ref, c = (uint32_t)y.ref;
-        return a != c ? a < c : x.pos < y.pos;
-    });
     std::vector<uint64_t> uoff(recs.size() + 1, 0);
     for (size_t i = 0; i < recs.size(); ++i) uoff[i + 1] = uoff[i] + recs[i].len;
     const size_t n = recs.size();
     par(threads, threads, [&](int t) { for (size_t i = n * (size_t)t / (size_t)threads; i < n * ((size_t)t + 1) / (size_t)threads; ++i) std::memcpy(dst + uoff[i], records + recs[i].off, recs[i].len); });
+}
+
+void sort_records_host(const char *records, std::vector<BamRec> &recs, int threads, char *dst)
+{
+    std::stable_sort(recs.begin(), recs.end(), [](const Rec &x, const Rec &y) {
+        const uint32_t a = (uint32_t)x.ref, c = (uint32_t)y.ref;
+        return a != c ? a < c : x.pos < y.pos;
+    });
+    gather_records(records, recs, threads, dst);
+}
+
+void sort_records_host_by_name(const char *records, std::vector<BamRec> &recs, int threads, char *dst)
+{
+    std::stable_sort(recs.begin(), recs.end(), [&](const Rec &x, const Rec &y) {
+        const int c = strnum_cmp(records + x.off + 36, records + y.off + 36);
+        if (c) return c < 0;
+        return ((x.flag >> 6) & 3) < ((y.flag >> 6) & 3);                 // first of pair before second
+    });
+    gather_records(records, recs, threads, dst);
 }
 
 void flatten_records(const BamFile &f, unsigned columns, const std::vector<int32_t> *rows, int threads, RecTable &out)

@@ -19,7 +19,9 @@ void bgzf_host_compress(const BgzfSpan *spans, size_t n_spans, int level, int th
 // of the records into the file's stream on host threads.  A hook registered here takes both instead (ps_bamsort.hip: the key, the
 // radix sort and the gather on the device; this file and ps_bam.cpp stay free of HIP): it fills perm, the sorted order, and stream,
 // the records in that order back to back.  It returns false when it leaves the call to the host route (and counts that), throws
-// ps::Error on a device error -- the writing call fails with it, there is no fallback.  Null: the host route.  The name sort never asks.
+// ps::Error on a device error -- the writing call fails with it, there is no fallback.  Null: the host route.  The name sort (`samtools
+// sort -n`'s order, bam_name_cmp, then first of pair before second) has a hook of its own with the same contract: ps_bamsort.hip's
+// name route, whose key ps_namesort.h states.  Each sort asks its own hook and never the other's.
 struct BamRec;
 struct BamSortJob {
     const BgzfSpan *parts; size_t n_parts;        // the buffers the records lie in; recs[i].part names one
@@ -33,6 +35,7 @@ struct BamSortJob {
 };
 typedef bool (*BamSortFn)(BamSortJob &job);
 void bam_sort_set_device_hook(BamSortFn fn);
+void bam_name_sort_set_device_hook(BamSortFn fn);
 // one encoded BAM record inside a buffer of records: reference id, 0-based position and end, flag, byte range [off, off + len)
 struct BamRec { int32_t ref; int32_t pos; int32_t end; uint32_t flag; size_t off, len; int part; };
 // The record layout (SAMv1 4.2), for every route that makes records -- SAM text (sam_to_bam) and the mapper's hits (ps_map_to_bam).
@@ -91,6 +94,10 @@ void load_records(const char *sam_or_bam, int threads, BamFile &out);
 void scan_records(const char *records, uint64_t n_bytes, std::vector<BamRec> &recs);
 // the host route on its own: recs into coordinate order (std::stable_sort), their bytes gathered into dst on `threads` threads
 void sort_records_host(const char *records, std::vector<BamRec> &recs, int threads, char *dst);
+// the name order's comparator (read names as `samtools sort -n` orders them: digit runs compare as numbers; NUL-terminated), and the
+// host route of that order: recs (every name ends inside its record) by bam_name_cmp, then the pair bits of the flag, then gathered
+int bam_name_cmp(const char *a, const char *b);
+void sort_records_host_by_name(const char *records, std::vector<BamRec> &recs, int threads, char *dst);
 // The record table: the fields of the records of a BamFile as flat arrays, for the analysis modes' kernels.
 // ref, pos, flag and l_seq always; the other columns by mask.  BAM conventions throughout: pos 0-based (a kernel that wants
 // htsjdk's 1-based start adds one), ref -1 unplaced, CIGAR words len<<4|op with MIDNSHP=X, bases as nibbles =ACMGRSVTWYHKDBN.

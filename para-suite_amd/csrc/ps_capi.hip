@@ -14,6 +14,7 @@
 #include "ps_host.h"
 #include "ps_bgzf.h"
 #include "ps_bamsort.h"
+#include "ps_namesort.h"
 
 using namespace ps;
 
@@ -672,6 +673,55 @@ int64_t ps_bam_sort_records(const void *records, uint64_t n_bytes, int device, i
         } else {
             const auto t0 = std::chrono::steady_clock::now();
             sort_records_host((const char *)records, recs, threads, (char *)dst);       // nothing in it fails once the records are scanned
+            st.ms_sort = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            st.n_calls_host = 1; st.n_records = recs.size(); st.bytes = n_bytes;
+        }
+        put(stats, st);
+        return (int64_t)n_bytes;
+    } catch (const std::exception &e) { fail(e.what()); return -1; } catch (...) { fail("unknown error"); return -1; }
+}
+static void put(ps_bam_name_sort_stats *o, const BamNameSortStats &s)
+{
+    if (!o) return;
+    o->on_device = s.on_device; o->n_records = s.n_records; o->bytes = s.bytes; o->n_calls_device = s.n_calls_device; o->n_calls_host = s.n_calls_host;
+    o->n_resident = s.n_resident; o->key_words = s.key_words; o->pad_ = 0; o->n_passes = s.n_passes;
+    o->ms_upload = s.ms_upload; o->ms_keys = s.ms_keys; o->ms_sort = s.ms_sort; o->ms_gather = s.ms_gather; o->ms_download = s.ms_download;
+}
+int ps_bam_name_sort_device(int device) { PS_TRY bam_name_sort_set_device(device < 0 ? -1 : device); return 0; PS_CATCH_INT }
+int ps_bam_name_sort_info(ps_bam_name_sort_stats *out)
+{
+    PS_TRY
+        if (!out) throw Error("ps_bam_name_sort_info: no place for the result");
+        BamNameSortStats s; bam_name_sort_info(s);
+        out->struct_size = sizeof(ps_bam_name_sort_stats); put(out, s); return 0;
+    PS_CATCH_INT
+}
+int64_t ps_bam_name_sort_records(const void *records, uint64_t n_bytes, int device, int threads, void *dst, uint64_t cap, ps_bam_name_sort_stats *stats)
+{
+    try {
+        if (stats && stats->struct_size < sizeof(ps_bam_name_sort_stats)) throw Error("ps_bam_name_sort_records: stats->struct_size is not sizeof(ps_bam_name_sort_stats)");
+        BamNameSortStats st;
+        if (n_bytes == 0) { put(stats, st); return 0; }
+        if (!records || !dst) throw Error("ps_bam_name_sort_records: records and destination are required");
+        std::vector<BamRec> recs;
+        try { scan_records((const char *)records, n_bytes, recs); } catch (const Error &e) { throw Error(std::string("ps_bam_name_sort_records: ") + e.what()); }
+        for (size_t i = 0; i < recs.size(); ++i) {              // l_read_name at byte 12 counts the NUL that ends the name at byte 36 + l_read_name - 1
+            const uint8_t *p = (const uint8_t *)records + recs[i].off;
+            if (recs[i].len < 37 || p[12] < 1 || 36 + (size_t)p[12] > recs[i].len || p[36 + p[12] - 1] != 0)
+                throw Error("ps_bam_name_sort_records: record " + std::to_string(i + 1) + " has a name that does not end inside it");
+        }
+        if (n_bytes > cap) throw Error("ps_bam_name_sort_records: the records take " + std::to_string(n_bytes) + " bytes, the destination holds " + std::to_string(cap));
+        if (device >= 0) {
+            require_device(device);
+            const BgzfSpan part{(const char *)records, (size_t)n_bytes};
+            std::vector<uint32_t> perm; std::string stream;
+            BamSortJob job{&part, 1, recs.data(), recs.size(), &perm, &stream};
+            if (!bam_name_sort_device_run(job, device, &st)) throw Error("ps_bam_name_sort_records: the records need more device memory than PS_BAM_SORT_MAX_MB allows, or there are 2^32 of them or more");
+            if (stream.size() != n_bytes) throw Error("ps_bam_name_sort_records: the sorted stream has not the records' size");
+            std::memcpy(dst, stream.data(), stream.size());
+        } else {
+            const auto t0 = std::chrono::steady_clock::now();
+            sort_records_host_by_name((const char *)records, recs, threads, (char *)dst);   // nothing in it fails once the records are scanned
             st.ms_sort = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             st.n_calls_host = 1; st.n_records = recs.size(); st.bytes = n_bytes;
         }

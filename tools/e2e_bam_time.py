@@ -5,8 +5,10 @@ SWITCH=records alternates the BAM records' device route (ps_bam_records_device) 
 of the same command are the reference.  SWITCH=sort alternates the coordinate sort's device route (ps_bam_sort_device) the same way, on
 the sorted + indexed call alone (the unsorted file never sorts); the stage lines of both routes come with PS_VERBOSE.  SWITCH=sort+bgzf
 is the same with the device compressor on throughout, so that the on runs leave the sorted stream on the device for it.
+SWITCH=namesort writes the unsorted MAPQ-filtered BAM once and then times ps_bam_sort by name on it (`samtools sort -n`), the name
+sort's device route (ps_bam_name_sort_device) off and on in turn; SWITCH=namesort+bgzf the same with the device compressor on throughout.
 
-    python tools/e2e_bam_time.py [N_READS=10000000] [GENOME_MBP=1000] [WORKDIR=/tmp] [SWITCH=bgzf|records|sort|sort+bgzf]"""
+    python tools/e2e_bam_time.py [N_READS=10000000] [GENOME_MBP=1000] [WORKDIR=/tmp] [SWITCH=bgzf|records|sort|sort+bgzf|namesort|namesort+bgzf]"""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, 'para-suite_amd'); sys.path.insert(0, '.')
@@ -16,10 +18,10 @@ n = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
 mbp = int(sys.argv[2]) if len(sys.argv) > 2 else 1000
 work = sys.argv[3] if len(sys.argv) > 3 else '/tmp'
 switch = sys.argv[4] if len(sys.argv) > 4 else 'bgzf'
-assert switch in ('bgzf', 'records', 'sort', 'sort+bgzf')
-resident = switch == 'sort+bgzf'
+assert switch in ('bgzf', 'records', 'sort', 'sort+bgzf', 'namesort', 'namesort+bgzf')
+resident = switch.endswith('+bgzf')
 if resident:
-    switch = 'sort'
+    switch = switch[:-len('+bgzf')]
     capi.ps_bgzf_device(0)
 p = lambda x: os.path.join(work, 'e2e_bam.' + x)
 dev = torch.device('cuda', 0)
@@ -42,7 +44,15 @@ os.environ['PS_BAM_LEVEL'] = '1'
 os.environ['PS_VERBOSE'] = os.environ.get('E2E_VERBOSE', '1')
 LABEL = dict(bgzf=('zlib level 1 on 16 threads', 'BGZF on device 0'), records=('records built on 16 host threads', 'records built on the device'),
              sort=('records sorted and gathered on the host' + ', BGZF on device 0' * resident, 'records sorted and gathered on device 0' + ', the stream left there for BGZF on device 0' * resident))
-for kw in (dict(min_mapq=10), dict(min_mapq=10, sort_by_coordinate=True, write_index=True))[1 if switch == 'sort' else 0:]:
+if switch == 'namesort':
+    st = capi.ps_map_to_bam(16, '-1', p('errorprofile'), p('indelprofile'), p('fa'), p('fq'), p('bam'), min_mapq=10)
+    print('ps_map_to_bam: %d of %d records kept, BAM %.0f MB' % (st['n_out'], st['n_in'], st['bam_bytes'] / 1e6), flush=True)
+    for device in (-1, 0) * 5:
+        capi.ps_bam_name_sort_device(device)
+        t = time.time(); st = capi.ps_bam_sort(p('bam'), p('byname.bam'), by_name=True, threads=16); dt = time.time() - t
+        print('ps_bam_sort by name, %s: %.2fs, %d records, BAM %.0f MB' % (LABEL['sort'][device >= 0], dt, st['n_out'], st['bam_bytes'] / 1e6), flush=True)
+    capi.ps_bam_name_sort_device(-1)
+for kw in () if switch == 'namesort' else (dict(min_mapq=10), dict(min_mapq=10, sort_by_coordinate=True, write_index=True))[1 if switch == 'sort' else 0:]:
     for device in (-1, 0) * 5:                       # the first pair warms the page cache and the page-locked buffers up; four timed pairs
         if switch == 'bgzf':
             capi.ps_bgzf_device(device)

@@ -724,7 +724,9 @@ int64_t ps_batch_bam_records(ps_batch *b, int min_mapq, int on_device, int threa
  * in n_calls_host, when there are 2^32 records or more or when the call would need more than PS_BAM_SORT_MAX_MB (default 32768)
  * of device memory.  Returns non-zero with the last error set when there is no such device.  A later HIP failure fails the writing
  * call: there is no fallback.  PS_BAM_SORT_GPU=<device> in the environment is the same as the call; it is read once, when the
- * library is loaded, so the bwa, samtools and parasuite programs take it too.
+ * library is loaded, so the bwa, samtools and parasuite programs take it too.  PS_BAM_SORT_PIECE: bytes of one half of the
+ * page-locked staging that both sorts' records, columns, permutation and stream pass through (for tests: default 64 MiB and never
+ * more, at least 256, rounded down to a multiple of 64; unset, empty, not a number or <= 0: the default); read at every call.
  * ps_bam_sort_info: summed over the process since the switch was last set; on_device: the switch is on; bytes: record bytes
  * sorted on the device; the route's four times in ms (records up, keys + sort, offsets + gather, permutation + stream down).
  * When ps_bgzf_device names the same device and the call keeps no records in memory (every call but the passes of ps_map_route

@@ -25,6 +25,7 @@
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
+#include <stdlib.h>
 #include "ps_types.h"
 
 namespace ps {
@@ -141,6 +142,41 @@ BS_FN void bamsort_gather_group(BsShared &sh, const BsArgs &a, uint64_t g0)
         BS_SYNC();
         s = e;
     }
+}
+
+// ---- the staging of the device route: two page-locked halves of one PIECE each.  Plain host functions, so that the check program
+// runs the very code that run_route runs.
+const size_t BS_PIECE_DEFAULT = (size_t)64 << 20, BS_PIECE_MIN = 256;
+
+// PS_BAM_SORT_PIECE=<bytes> (tests): the size of one half.  Unset, empty, not a number or <= 0: the default; never more than the default
+// (the knob cannot grow the page-locked allocation), never less than 256; rounded down to a multiple of 64, so that the second half and
+// the column sub-arrays keep their alignment.
+static inline size_t bamsort_piece_bytes(const char *value)
+{
+    if (!value || !value[0]) return BS_PIECE_DEFAULT;
+    const long long v = atoll(value);
+    if (v <= 0 || v >= (long long)BS_PIECE_DEFAULT) return BS_PIECE_DEFAULT;
+    return v < (long long)BS_PIECE_MIN ? BS_PIECE_MIN : (size_t)v & ~(size_t)63;
+}
+
+// The four per-record columns go up `per` records at a time, as four sub-arrays of one half: the source offset (8 bytes per record),
+// then the length and the order's two columns (4 bytes each) -- 20 bytes per record in all.
+static inline size_t bamsort_columns_per_piece(size_t piece) { return piece / 20; }
+struct BsColumnsAt { size_t off, len, ref, pos; };      // byte offsets inside the half
+static inline BsColumnsAt bamsort_columns_at(size_t per) { return BsColumnsAt{0, 8 * per, 12 * per, 16 * per}; }
+
+// The upload's cut: the parts go up back to back in pieces that ignore part and record boundaries.  The cursor names the next source
+// byte; one cut is the run of bytes of the cursor's part that still fits into `room` bytes of the half (none for an empty part), and
+// taking it moves the cursor on, to the next part where this one is used up.  The caller stops at room 0 or behind the last part.
+struct BsCursor { size_t part = 0; uint64_t in_part = 0; };
+struct BsCut { size_t part; uint64_t in_part; size_t take; };
+static inline BsCut bamsort_next_cut(BsCursor &c, uint64_t part_bytes, size_t room)
+{
+    const uint64_t left = part_bytes - c.in_part;
+    const BsCut cut{c.part, c.in_part, left < room ? (size_t)left : room};
+    c.in_part += cut.take;
+    if (c.in_part == part_bytes) { ++c.part; c.in_part = 0; }
+    return cut;
 }
 
 // ---- the host side of the device route (ps_bamsort.hip); BamSortJob: ps_bam.h

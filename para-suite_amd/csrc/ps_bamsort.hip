@@ -108,8 +108,6 @@ __global__ __launch_bounds__(256) void k_namesort_column(const uint32_t *column,
 
 namespace {
 
-const size_t PIECE = (size_t)64 << 20;              // one half of the page-locked staging
-
 template <class T> void need(DevBuf<T> &b, size_t n) { if (b.n < n) b.alloc(n); }
 
 struct Buffers {                                    // grow-only, kept between calls (never destroyed: a writer may run during exit)
@@ -139,17 +137,18 @@ void copy_threads(void *dst, const void *src, size_t n)
     ranges(n, n >= ((size_t)4 << 20) ? 8 : 1, [&](size_t a0, size_t a1) { std::memcpy((char *)dst + a0, (const char *)src + a0, a1 - a0); });
 }
 
-// the two halves of the staging: half() waits until the copy that last used the half is over, sent() marks the one just enqueued
+// the two halves of the staging, `piece` bytes each: half() waits until the copy that last used the half is over, sent() marks the one
+// just enqueued
 struct Stager {
-    uint8_t *base; hipStream_t s; hipEvent_t ev[2] = {nullptr, nullptr}; bool used[2] = {false, false}; int cur = 0;
-    Stager(uint8_t *pin, hipStream_t stream) : base(pin), s(stream)
+    uint8_t *base; size_t piece; hipStream_t s; hipEvent_t ev[2] = {nullptr, nullptr}; bool used[2] = {false, false}; int cur = 0;
+    Stager(uint8_t *pin, size_t piece_bytes, hipStream_t stream) : base(pin), piece(piece_bytes), s(stream)
     {
         PS_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
         if (hipEventCreateWithFlags(&ev[1], hipEventDisableTiming) != hipSuccess) { (void)hipEventDestroy(ev[0]); throw Error("hipEventCreate failed"); }
     }
     Stager(const Stager &) = delete;
     ~Stager() { (void)hipStreamSynchronize(s); (void)hipEventDestroy(ev[0]); (void)hipEventDestroy(ev[1]); }
-    uint8_t *half() { if (used[cur]) { PS_HIP(hipEventSynchronize(ev[cur])); used[cur] = false; } return base + (size_t)cur * PIECE; }
+    uint8_t *half() { if (used[cur]) { PS_HIP(hipEventSynchronize(ev[cur])); used[cur] = false; } return base + (size_t)cur * piece; }
     void sent() { PS_HIP(hipEventRecord(ev[cur], s)); used[cur] = true; cur ^= 1; }
     void wait_all() { PS_HIP(hipStreamSynchronize(s)); used[0] = used[1] = false; }
 };
@@ -264,22 +263,22 @@ template <class Order> bool run_route(BamSortJob &job, int device, Order &order)
     need(b.off, n); need(b.len, n); need(b.ref, n); need(b.pos, n);
     need(b.key_a, n); need(b.key_b, n); need(b.idx_a, n); need(b.idx_b, n); need(b.slen, n + 1); need(b.doff, n + 1);
     order.need_buffers(b, n);
+    const size_t PIECE = bamsort_piece_bytes(std::getenv("PS_BAM_SORT_PIECE"));    // one half of the page-locked staging (64 MiB; the knob is for tests)
     uint8_t *pin = (uint8_t *)b.pin.get(2 * PIECE);
     StreamGuard sg;
-    Stager stg(pin, sg.s);
+    Stager stg(pin, PIECE, sg.s);
 
     // ---- upload: the parts back to back, then the four columns (offset, length and the order's two), piece by piece
     HostClock::time_point t0 = HostClock::now();
     {
-        size_t k = 0; uint64_t in_part = 0, at = 0;
+        BsCursor cur; uint64_t at = 0;
         while (at < src_bytes) {
             uint8_t *h = stg.half();
             size_t fill = 0;
-            while (fill < PIECE && k < job.n_parts) {
-                const size_t take = (size_t)std::min<uint64_t>(PIECE - fill, job.parts[k].n - in_part);
-                if (take) copy_threads(h + fill, job.parts[k].p + in_part, take);
-                fill += take; in_part += take;
-                if (in_part == job.parts[k].n) { ++k; in_part = 0; }
+            while (fill < PIECE && cur.part < job.n_parts) {
+                const BsCut c = bamsort_next_cut(cur, job.parts[cur.part].n, PIECE - fill);
+                if (c.take) copy_threads(h + fill, job.parts[c.part].p + c.in_part, c.take);
+                fill += c.take;
             }
             PS_HIP(hipMemcpyAsync(b.src.p + at, h, fill, hipMemcpyHostToDevice, sg.s));
             stg.sent();
@@ -288,11 +287,12 @@ template <class Order> bool run_route(BamSortJob &job, int device, Order &order)
     }
     uint64_t any = 0;
     {
-        const size_t per = PIECE / 20;              // off 8, len 4, ref 4, pos 4 per record
+        const size_t per = bamsort_columns_per_piece(PIECE);           // off 8, len 4, ref 4, pos 4 per record
+        const BsColumnsAt col = bamsort_columns_at(per);
         for (size_t i0 = 0; i0 < n; i0 += per) {
             const size_t m = std::min(per, n - i0);
             uint8_t *h = stg.half();
-            uint64_t *h_off = (uint64_t *)h; uint32_t *h_len = (uint32_t *)(h + 8 * per); int32_t *h_ref = (int32_t *)(h + 12 * per), *h_pos = (int32_t *)(h + 16 * per);
+            uint64_t *h_off = (uint64_t *)(h + col.off); uint32_t *h_len = (uint32_t *)(h + col.len); int32_t *h_ref = (int32_t *)(h + col.ref), *h_pos = (int32_t *)(h + col.pos);
             std::atomic<uint64_t> any_piece{0};
             ranges(m, m >= 65536 ? 8 : 1, [&](size_t a0, size_t a1) {
                 uint64_t o = 0;

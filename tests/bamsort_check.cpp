@@ -7,7 +7,12 @@
 //           size (the source up to a multiple of 4, as the header asks), over two backgrounds: after every group the bytes of its
 //           range are the reference's and every other byte still has the value it had before the group.
 //   swap    negative control: one swapped pair in the permutation must fail the comparison.
+//   piece   PS_BAM_SORT_PIECE's parser at every documented clamp; the four column sub-arrays of a half (no overlap, inside the half,
+//           aligned) for every piece size from 256 to 8192 and the default; a replay of run_route's upload loop over ps_bamsort.h's
+//           cut: the copies tile the parts' bytes once and in order, for part lists with empty parts, parts that end on a piece
+//           boundary and parts of many pieces.
 #include <algorithm>
+#include <utility>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -181,9 +186,137 @@ static int check_swap()
     return 0;
 }
 
+// ------------------------------------------------------------------ the staging: knob, column layout, upload cut
+#define CHECK(x) do { if (!(x)) { std::fprintf(stderr, "%s:%d: CHECK failed: %s\n", __FILE__, __LINE__, #x); return 1; } } while (0)
+
+// the piece size with PS_BAM_SORT_PIECE set to `value` (nullptr: unset), read from the environment as run_route reads it
+static size_t with(const char *value)
+{
+    unsetenv("PS_BAM_SORT_PIECE");
+    if (value) setenv("PS_BAM_SORT_PIECE", value, 1);
+    return bamsort_piece_bytes(std::getenv("PS_BAM_SORT_PIECE"));
+}
+
+static int check_piece_knob()
+{
+    const size_t D = (size_t)64 << 20;
+    CHECK(BS_PIECE_DEFAULT == D && D % 64 == 0);
+    CHECK(with(nullptr) == D); CHECK(with("") == D); CHECK(with("abc") == D); CHECK(with("0") == D); CHECK(with("-5") == D);     // the default
+    CHECK(with("1") == 256); CHECK(with("255") == 256); CHECK(with("256") == 256);                                             // at least 256
+    CHECK(with("257") == 256); CHECK(with("319") == 256); CHECK(with("320") == 320);                                           // down to a multiple of 64
+    CHECK(with("67108864") == D); CHECK(with("67108865") == D); CHECK(with("99999999999") == D);                               // never more than the default
+    CHECK(with("4096") == 4096); CHECK(with("67108863") == D - 64);
+    unsetenv("PS_BAM_SORT_PIECE");
+    std::printf("piece knob ok: 16 values\n");
+    return 0;
+}
+
+static int check_one_layout(size_t piece)
+{
+    const size_t per = bamsort_columns_per_piece(piece);
+    const BsColumnsAt c = bamsort_columns_at(per);
+    CHECK(per >= 1);
+    const size_t beg[4] = {c.off, c.len, c.ref, c.pos}, width[4] = {8, 4, 4, 4};
+    for (int a = 0; a < 4; ++a) {
+        CHECK(beg[a] + width[a] * per <= piece);                                  // ends inside the half
+        CHECK(beg[a] % width[a] == 0);                                            // a half starts at a multiple of 64: the offset's alignment is the array's
+        for (int b = 0; b < a; ++b) CHECK(beg[b] + width[b] * per <= beg[a] || beg[a] + width[a] * per <= beg[b]);
+    }
+    return 0;
+}
+
+static int check_column_layout()
+{
+    size_t n = 0;
+    for (size_t piece = 256; piece <= 8192; piece += 64, ++n) if (check_one_layout(piece)) return 1;
+    if (check_one_layout(BS_PIECE_DEFAULT)) return 1;
+    CHECK(bamsort_columns_per_piece(256) == 12 && bamsort_columns_per_piece(BS_PIECE_DEFAULT) == 3355443);
+    CHECK(BS_PIECE_DEFAULT % 64 == 0);                                            // the second half starts aligned as the first
+    std::printf("column layout ok: %zu piece sizes and the default\n", n);
+    return 0;
+}
+
+// The upload loop of run_route with its copies recorded in place of made: per piece the (device offset, bytes) of the one copy to the
+// device, and per cut the source range it takes.  The cut itself is ps_bamsort.h's.
+struct Replay { std::vector<std::pair<uint64_t, size_t>> copies; bool ok = true; size_t n_cuts = 0; };
+static Replay replay_upload(const std::vector<uint64_t> &parts, size_t piece)
+{
+    Replay r;
+    uint64_t src_bytes = 0;
+    std::vector<uint64_t> base;
+    for (uint64_t n : parts) { base.push_back(src_bytes); src_bytes += n; }
+    BsCursor cur; uint64_t at = 0;
+    while (at < src_bytes) {
+        size_t fill = 0;
+        while (fill < piece && cur.part < parts.size()) {
+            const BsCut c = bamsort_next_cut(cur, parts[cur.part], piece - fill);
+            ++r.n_cuts;
+            // the cut lies inside its part, fits the half, and is the next source byte in the back-to-back order
+            if (c.part >= parts.size() || c.in_part + c.take > parts[c.part] || c.take > piece - fill || base[c.part] + c.in_part != at + fill) r.ok = false;
+            if (c.take == 0 && parts[c.part] != 0) r.ok = false;                  // only an empty part yields nothing
+            fill += c.take;
+        }
+        if (fill == 0) { r.ok = false; break; }
+        r.copies.push_back({at, fill});
+        at += fill;
+    }
+    if (cur.in_part != 0) r.ok = false;
+    for (size_t k = cur.part; k < parts.size(); ++k) if (parts[k] != 0) r.ok = false;      // only empty parts may be left behind the last byte
+    return r;
+}
+
+static int check_upload_cut()
+{
+    const size_t pieces[] = {256, 320, 4096};
+    size_t n_cases = 0;
+    for (size_t P : pieces) {
+        const std::vector<std::vector<uint64_t>> lists = {
+            {},                                                                   // nothing at all
+            {0}, {0, 0, 0},                                                       // only empty parts
+            {1}, {P - 1}, {P}, {P + 1},                                           // around one piece
+            {P, P}, {2 * P}, {P / 2, P / 2, P},                                   // parts that end exactly on a piece boundary
+            {0, 5, 0, 0, P, 0, 7, 0},                                             // empty parts first, between and last
+            {37 * P + 11},                                                        // one part of many pieces
+            {3, 10 * P + 1, 0, P - 4, 1, 1, 1, 5 * P},                            // pieces that span several parts, parts that span several pieces
+        };
+        for (const auto &parts : lists) {
+            uint64_t src_bytes = 0;
+            for (uint64_t n : parts) src_bytes += n;
+            const Replay r = replay_upload(parts, P);
+            CHECK(r.ok);
+            CHECK(r.copies.size() == (src_bytes + P - 1) / P);
+            uint64_t at = 0;
+            for (size_t k = 0; k < r.copies.size(); ++k) {                        // the copies tile [0, src_bytes) once and in order, every piece but the last full
+                CHECK(r.copies[k].first == at && r.copies[k].second >= 1 && r.copies[k].second <= P);
+                CHECK(k + 1 == r.copies.size() || r.copies[k].second == P);
+                at += r.copies[k].second;
+            }
+            CHECK(at == src_bytes);
+            ++n_cases;
+        }
+    }
+    {   // seeded lists, a third of the parts empty
+        for (int t = 0; t < 200; ++t) {
+            const size_t P = 256 + 64 * below(8);
+            std::vector<uint64_t> parts(1 + below(9));
+            uint64_t src_bytes = 0;
+            for (auto &n : parts) { n = below(3) == 0 ? 0 : below(2) ? below(4 * (uint32_t)P) : (uint64_t)P * below(4); src_bytes += n; }
+            const Replay r = replay_upload(parts, P);
+            CHECK(r.ok && r.copies.size() == (src_bytes + P - 1) / P);
+            uint64_t at = 0;
+            for (const auto &c : r.copies) { CHECK(c.first == at && c.second >= 1 && c.second <= P); at += c.second; }
+            CHECK(at == src_bytes);
+            ++n_cases;
+        }
+    }
+    std::printf("upload cut ok: %zu part lists\n", n_cases);
+    return 0;
+}
+
 int main()
 {
     if (check_keys() || check_gather() || check_swap()) return 1;
+    if (check_piece_knob() || check_column_layout() || check_upload_cut()) return 1;
     std::printf("all ok\n");
     return 0;
 }

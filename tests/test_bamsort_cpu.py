@@ -1,7 +1,8 @@
 """The coordinate sort of BAM records as csrc/ps_bamsort.h states it for host and device, without a device.  tests/bamsort_check.cpp
 is the header (with csrc/ps_bam.cpp, which links alone with zlib) under the host compiler, built with AddressSanitizer and UBSan as
 a plain executable: the key's order against the library's comparator, the gather's 64 lanes run one after the other on exact-size
-heap buffers, and a swapped pair as the negative control.  The library's host route behind ps_bam_sort_records (no sanitizer: it is
+heap buffers, a swapped pair as the negative control, and the host functions of the device route's staging (the piece knob, the column
+layout, the upload's cut).  The library's host route behind ps_bam_sort_records (no sanitizer: it is
 loaded into Python) is held to Python's own sorted()."""
 import ctypes as C
 import os
@@ -40,6 +41,22 @@ def test_gather_lane_by_lane(check_output):
 
 def test_a_swapped_pair_fails_the_comparison(check_output):
     assert any(l.startswith("swap ok") for l in check_output) and check_output[-1] == "all ok"
+
+
+def test_the_piece_knob_clamps_as_documented(check_output):
+    """PS_BAM_SORT_PIECE: unset, empty, not a number, <= 0, below 256, not a multiple of 64, the default and above"""
+    assert "piece knob ok: 16 values" in check_output, check_output
+
+
+def test_the_column_sub_arrays_fit_their_half(check_output):
+    """every piece size from 256 to 8192 in steps of 64, and the default: four arrays, disjoint, inside the half, aligned"""
+    assert "column layout ok: %d piece sizes and the default" % len(range(256, 8193, 64)) in check_output, check_output
+
+
+def test_the_upload_cut_tiles_the_parts(check_output):
+    """run_route's upload loop replayed over the header's cut: empty parts, parts that end on a piece boundary, parts of many pieces"""
+    line = [l for l in check_output if l.startswith("upload cut ok")]
+    assert line and int(line[0].split()[3]) >= 3 * 13 + 200, check_output
 
 
 @pytest.mark.parametrize("n", [0, 1, 65, 3000])

@@ -6,7 +6,8 @@
 // BGZF blocks of at most 64 KiB with the BC extra field, BAM records, binning index with 16 kb linear index);
 // integer tags take the smallest type as htslib's SAM parser does.  Host code only (zlib), no device work in this file: the BGZF
 // blocks of every writer go through bgzf_batch(), which hands them to the device compressor when one is registered (ps_bam.h), and
-// every sort through sort_for_write(), which hands sort and gather to the hook registered for its order (ps_bamsort.hip) the same way.
+// every sort through sort_for_write(), which hands sort and gather to the hook registered for its order (ps_bamsort.hip) the same way
+// and returns the body of the file (ps_bam.h: BamBody) that write_bam then writes.
 // PS_VERBOSE: write_bam prints one line with the ms of its stages (sort, offsets + gather, compression, file write, .bai) on stderr.
 #include <zlib.h>
 #include <algorithm>
@@ -138,10 +139,9 @@ static bool encode_line(const char *line, size_t n, const std::map<std::string, 
     return true;
 }
 
-// one BGZF block (gzip member with the BC extra field) of at most 0xff00 input bytes
+// one BGZF block (gzip member with the BC extra field) of at most kBgzfBlock input bytes
 static void bgzf_block(const char *src, size_t n, int level, std::string &out)
 {
-    static const unsigned char head[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0};
     std::vector<unsigned char> buf(n + n / 100 + 64);
     z_stream zs; std::memset(&zs, 0, sizeof zs);
     if (deflateInit2(&zs, level, Z_DEFLATED, -15, 8, Z_DEFAULT_STRATEGY) != Z_OK) throw Error("deflateInit2 failed");
@@ -150,13 +150,8 @@ static void bgzf_block(const char *src, size_t n, int level, std::string &out)
     if (deflate(&zs, Z_FINISH) != Z_STREAM_END) { deflateEnd(&zs); throw Error("deflate failed"); }
     const size_t cn = zs.total_out;
     deflateEnd(&zs);
-    const size_t total = 18 + cn + 8;
-    if (total > 65536) throw Error("BGZF block too large");
-    out.append((const char *)head, 16);
-    put16(out, (uint16_t)(total - 1));
-    out.append((const char *)buf.data(), cn);
-    put32(out, (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef *)src, (uInt)n));
-    put32(out, (uint32_t)n);
+    if (18 + cn + 8 > 65536) throw Error("BGZF block too large");
+    bgzf_member(buf.data(), cn, (uint32_t)crc32(crc32(0L, Z_NULL, 0), (const Bytef *)src, (uInt)n), (uint32_t)n, out);
 }
 
 template <class F> static void par(int n, int threads, F f)
@@ -172,26 +167,35 @@ template <class F> static void par(int n, int threads, F f)
 }
 
 // The one place where BGZF blocks are made: comp[k] becomes the whole member (header, deflate payload, CRC32, ISIZE) of spans[k],
-// each span at most 0xff00 bytes.  On host threads with zlib, or -- the whole list at once -- by the compressor that the library
-// registered (ps_bgzf.hip: ps_bgzf_device, PS_BGZF_GPU); `level` means nothing to that one.
+// each span at most kBgzfBlock bytes.  On host threads with zlib (bgzf_host_compress), or -- the whole list at once -- by the
+// compressor that the library registered (ps_bgzf.hip: ps_bgzf_device, PS_BGZF_GPU); `level` means nothing to that one.
 std::atomic<BgzfBatchFn> g_bgzf_device{nullptr};
 static void bgzf_batch(const std::vector<BgzfSpan> &spans, int level, int threads, std::vector<std::string> &comp)
 {
     comp.assign(spans.size(), std::string());
     if (spans.empty()) return;
-    if (const BgzfBatchFn fn = g_bgzf_device.load()) { fn(spans.data(), spans.size(), comp.data()); return; }
-    const int T = threads;
-    par(T, T, [&](int t) { for (size_t k = (size_t)t; k < spans.size(); k += (size_t)T) bgzf_block(spans[k].p, spans[k].n, level, comp[k]); });
+    if (const BgzfBatchFn fn = g_bgzf_device.load()) fn(spans.data(), spans.size(), comp.data());
+    else bgzf_host_compress(spans.data(), spans.size(), level, threads, comp.data());
 }
+
+static int clamp_threads(int t) { return t < 1 ? 1 : (t > 64 ? 64 : t); }
 
 }  // namespace
 
 void bgzf_set_device_compressor(BgzfBatchFn fn) { g_bgzf_device.store(fn); }
-static int clamp_threads(int t);
+void bgzf_member(const void *payload, size_t n_payload, uint32_t crc, uint32_t isize, std::string &out)
+{
+    static const unsigned char head[16] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0};
+    const size_t total = 18 + n_payload + 8;
+    out.reserve(out.size() + total);
+    out.append((const char *)head, 16); put16(out, (uint16_t)(total - 1));
+    out.append((const char *)payload, n_payload);
+    put32(out, crc); put32(out, isize);
+}
 void bgzf_host_compress(const BgzfSpan *spans, size_t n_spans, int level, int threads, std::string *comp)
 {
     const int T = clamp_threads(threads);
-    for (size_t k = 0; k < n_spans; ++k) { if (spans[k].n > 0xff00) throw Error("a BGZF span of more than 0xff00 bytes"); comp[k].clear(); }
+    for (size_t k = 0; k < n_spans; ++k) { if (spans[k].n > kBgzfBlock) throw Error("a BGZF span of more than 0xff00 bytes"); comp[k].clear(); }
     par(T, T, [&](int t) { for (size_t k = (size_t)t; k < n_spans; k += (size_t)T) bgzf_block(spans[k].p, spans[k].n, level, comp[k]); });
 }
 
@@ -424,76 +428,88 @@ static void write_bai(const std::string &bai_path, const Data &d, const Layout &
 using Clock = std::chrono::steady_clock;
 static double ms_since(Clock::time_point t) { return std::chrono::duration<double, std::milli>(Clock::now() - t).count(); }
 
-// what the sort in front of write_bam did: its time and route for the stage line (PS_VERBOSE), and -- from the device route -- the
-// records already gathered in d.recs order, which write_bam takes in place of its own gather (and hands back when the parts are kept).
-// may_stay: the caller keeps no records in memory, so the device route may leave the stream where it is; resident: it did, and
-// write_bam has the body's blocks made from there (BamSortJob in ps_bam.h) -- a Sorted that is dropped before that gives the buffer back.
-struct Sorted {
-    double ms_sort = -1; const char *route = "host"; std::string *stream = nullptr;
-    bool may_stay = false; void (*resident)(std::string *comp) = nullptr;
-    Sorted() {}
-    Sorted(const Sorted &) = delete;
-    ~Sorted() { if (resident) { try { resident(nullptr); } catch (...) {} } }
-};
+static std::string bam_header(const Data &d)        // magic, l_text, text, n_ref, the references
+{
+    std::string head;
+    head.append("BAM\1", 4); put32(head, (uint32_t)d.text.size()); head += d.text; put32(head, (uint32_t)d.refs.size());
+    for (auto &r : d.refs) { put32(head, (uint32_t)r.first.size() + 1); head += r.first; head.push_back('\0'); put32(head, r.second); }
+    return head;
+}
+static const unsigned char eof_block[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
 
-// ---- Data (records in d.recs order) -> BGZF file (+ .bai)
-static void write_bam(Data &d, const char *bam_path, bool write_index, int threads, BamStats *stats, int level = 6, bool keep_enc = false, Sorted *sorted = nullptr)
+// the two orders, each stated once.  Coordinate: the reference id as unsigned (-1, no reference, sorts last), then the position.
+// Name: strnum_cmp, then the first read of a pair before the second; name(r): where r's NUL-terminated name starts.
+struct CoordinateLess { bool operator()(const Rec &x, const Rec &y) const { const uint32_t a = (uint32_t)x.ref, c = (uint32_t)y.ref; return a != c ? a < c : x.pos < y.pos; } };
+template <class NameOf> static void sort_in_order(std::vector<Rec> &recs, bool by_name, NameOf name)
+{
+    if (by_name)
+        std::stable_sort(recs.begin(), recs.end(), [&](const Rec &x, const Rec &y) {
+            const int c = strnum_cmp(name(x), name(y));
+            return c ? c < 0 : ((x.flag >> 6) & 3) < ((y.flag >> 6) & 3);
+        });
+    else std::stable_sort(recs.begin(), recs.end(), CoordinateLess());
+}
+
+// where every record starts when the records lie back to back in this order (n + 1 offsets), and their bytes put there on threads;
+// part(r): the start of the buffer that r.off counts from
+static std::vector<uint64_t> stream_offsets(const std::vector<Rec> &recs)
+{
+    std::vector<uint64_t> uoff(recs.size() + 1, 0);
+    for (size_t i = 0; i < recs.size(); ++i) uoff[i + 1] = uoff[i] + recs[i].len;
+    return uoff;
+}
+template <class PartOf> static void gather(const std::vector<Rec> &recs, const std::vector<uint64_t> &uoff, int T, char *dst, PartOf part)
+{
+    const size_t n = recs.size();
+    par(T, T, [&](int t) { for (size_t i = n * (size_t)t / (size_t)T; i < n * ((size_t)t + 1) / (size_t)T; ++i) std::memcpy(dst + uoff[i], part(recs[i]) + recs[i].off, recs[i].len); });
+}
+
+// ---- Data (records in d.recs order) -> BGZF file (+ .bai).  body says where the records' bytes are (ps_bam.h); a device stream is
+// used up, a host stream -- the sort's, or the one gathered here -- is left in body for the caller that keeps the file.  The parts are dropped.
+static void write_bam(Data &d, BamBody &body, const char *bam_path, bool write_index, int threads, BamStats *stats, int level = 6)
 {
     const bool verbose = std::getenv("PS_VERBOSE") != nullptr;
     double ms_gather = 0, ms_comp = 0, ms_file = 0, ms_bai = 0;
     Clock::time_point t0 = Clock::now();
-    std::string head;
-    head.append("BAM\1", 4); put32(head, (uint32_t)d.text.size()); head += d.text; put32(head, (uint32_t)d.refs.size());
-    for (auto &r : d.refs) { put32(head, (uint32_t)r.first.size() + 1); head += r.first; head.push_back('\0'); put32(head, r.second); }
-    const size_t BLK = 0xff00;
+    const std::string head = bam_header(d);
+    const size_t BLK = kBgzfBlock;
     const size_t head_blocks = (head.size() + BLK - 1) / BLK;           // own blocks: samtools flushes after the header too
     const std::vector<Rec> &all = d.recs;
-    std::vector<uint64_t> uoff(all.size() + 1, 0);
-    for (size_t i = 0; i < all.size(); ++i) uoff[i + 1] = uoff[i] + all[i].len;
+    const std::vector<uint64_t> uoff = stream_offsets(all);
     const uint64_t body_bytes = uoff[all.size()];
     const size_t body_blocks = (size_t)((body_bytes + BLK - 1) / BLK);
-    std::string stream;
-    const bool resident = sorted && sorted->resident;
-    if (resident) {
-        if (keep_enc) throw Error("internal: a kept file needs its records on the host");
-    } else if (sorted && sorted->stream) {
-        if (sorted->stream->size() != body_bytes) throw Error("internal: the sorted stream has not the records' size");
-        stream.swap(*sorted->stream);
-    } else {
-        stream.assign((size_t)body_bytes, '\0');
-        const int T = threads; const size_t per = (all.size() + (size_t)T - 1) / (size_t)T;
-        par(T, T, [&](int t) { const size_t a0 = (size_t)t * per, a1 = std::min(all.size(), a0 + per); for (size_t i = a0; i < a1; ++i) std::memcpy(&stream[(size_t)uoff[i]], d.enc[all[i].part].data() + all[i].off, all[i].len); });
-    }
-    if (!keep_enc) for (auto &e : d.enc) { e.clear(); e.shrink_to_fit(); }
+    const bool resident = body.device != nullptr, came_with_sort = !body.in_parts && !resident;
+    if (body.in_parts) {
+        body.host.assign((size_t)body_bytes, '\0');
+        gather(all, uoff, threads, &body.host[0], [&](const Rec &r) { return d.enc[(size_t)r.part].data(); });
+        body.in_parts = false;
+    } else if (came_with_sort && body.host.size() != body_bytes) throw Error("internal: the sorted stream has not the records' size");
+    for (auto &e : d.enc) { e.clear(); e.shrink_to_fit(); }
     ms_gather = ms_since(t0); t0 = Clock::now();
     const size_t n_blocks = head_blocks + body_blocks;
     std::vector<std::string> comp;
     {
-        std::vector<BgzfSpan> spans(resident ? head_blocks : n_blocks);
-        for (size_t k = 0; k < spans.size(); ++k) {
-            if (k < head_blocks) { const size_t a0 = k * BLK; spans[k] = BgzfSpan{head.data() + a0, std::min(BLK, head.size() - a0)}; }
-            else { const size_t a0 = (k - head_blocks) * BLK; spans[k] = BgzfSpan{stream.data() + a0, (size_t)std::min<uint64_t>(BLK, body_bytes - a0)}; }
-        }
-        if (resident) {                                          // the header's blocks as ever; the body's from the stream on the device
-            bgzf_batch(spans, level, threads, comp);
+        std::vector<BgzfSpan> spans; spans.reserve(n_blocks);
+        bgzf_cut(head.data(), head.size(), spans);
+        bgzf_cut(body.host.data(), body.host.size(), spans);
+        bgzf_batch(spans, level, threads, comp);
+        if (resident) {                                          // the header's blocks as ever; the body's from the stream on the device, which then goes back
             comp.resize(n_blocks);
-            void (*const make)(std::string *) = sorted->resident;
-            sorted->resident = nullptr;                          // it gives the buffer back itself, whatever happens
-            make(comp.data() + head_blocks);
-        } else bgzf_batch(spans, level, threads, comp);
+            body.device->blocks(comp.data() + head_blocks);
+            body.device.reset();
+        }
     }
     ms_comp = ms_since(t0); t0 = Clock::now();
     // the times of the stages go to stderr and nowhere else
     auto stage_line = [&]() {
         if (!verbose) return;
         char sort_text[64] = "no sort";
-        if (sorted && sorted->ms_sort >= 0) std::snprintf(sort_text, sizeof sort_text, "sort %.1f ms (%s)", sorted->ms_sort, sorted->route);
+        if (body.ms_sort >= 0) std::snprintf(sort_text, sizeof sort_text, "sort %.1f ms (%s)", body.ms_sort, body.route);
         std::fprintf(stderr, "[parasuite-hip] bam: %zu records, %.1f MB in %zu blocks: %s, offsets + gather %.1f ms%s, compression %.1f ms, file write %.1f ms, .bai %.1f ms\n",
-                     all.size(), body_bytes / 1e6, n_blocks, sort_text, ms_gather, resident ? " (the stream stayed on the device)" : sorted && sorted->stream ? " (the stream came with the sort)" : "", ms_comp, ms_file, ms_bai);
+                     all.size(), body_bytes / 1e6, n_blocks, sort_text, ms_gather, resident ? " (the stream stayed on the device)" : came_with_sort ? " (the stream came with the sort)" : "", ms_comp, ms_file, ms_bai);
     };
     std::vector<uint64_t> coff(n_blocks + 1, 0);
     for (size_t k = 0; k < n_blocks; ++k) coff[k + 1] = coff[k] + comp[k].size();
-    static const unsigned char eof_block[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     FILE *o = std::fopen(bam_path, "wb");
     if (!o) throw Error(std::string("cannot write ") + bam_path);
     bool ok = true;
@@ -503,7 +519,6 @@ static void write_bam(Data &d, const char *bam_path, bool write_index, int threa
     if (!ok) throw Error(std::string("short write on ") + bam_path);
     if (stats) { stats->n_in = d.n_in; stats->n_out = all.size(); stats->bam_bytes = coff[n_blocks] + 28; }
     ms_file = ms_since(t0); t0 = Clock::now();
-    if (sorted && sorted->stream && keep_enc) sorted->stream->swap(stream);     // the kept file's one part
     if (!write_index) { stage_line(); return; }
     auto voff = [&](uint64_t u) -> uint64_t {           // virtual file offset of body byte u
         if (u == body_bytes && u % BLK == 0) return coff[n_blocks] << 16;      // end of the last full block = start of the EOF block
@@ -516,50 +531,35 @@ static void write_bam(Data &d, const char *bam_path, bool write_index, int threa
     stage_line();
 }
 
-static void sort_records(Data &d, bool by_name)
-{
-    if (by_name)
-        std::stable_sort(d.recs.begin(), d.recs.end(), [&](const Rec &x, const Rec &y) {
-            const int c = strnum_cmp(rec_name(d, x), rec_name(d, y));
-            if (c) return c < 0;
-            return ((x.flag >> 6) & 3) < ((y.flag >> 6) & 3);             // first of pair before second
-        });
-    else
-        std::stable_sort(d.recs.begin(), d.recs.end(), [](const Rec &x, const Rec &y) {
-            const uint32_t a = (uint32_t)x.ref, c = (uint32_t)y.ref;      // -1 (no reference) sorts last
-            return a != c ? a < c : x.pos < y.pos;
-        });
-}
-
-// The sort in front of write_bam.  Each order has a hook of its own (ps_bam.h): the registered one sorts and gathers in one go, the
-// host reorders d.recs by its permutation on threads and write_bam takes the stream as it is; without a hook, or when the hook
-// leaves the call alone, sort_records and write_bam's own gather.  s.stream must name a string.
+// The sort in front of write_bam, and the body it leaves.  Each order has a hook of its own (ps_bam.h): the registered one sorts and
+// gathers in one go, the host reorders d.recs by its permutation on threads, and the body is the hook's stream -- on the device only
+// when the caller said that it may stay there.  Without a hook, or when the hook leaves the call alone: sort_in_order, and the body
+// is still in the parts.
 std::atomic<BamSortFn> g_sort_device{nullptr}, g_name_sort_device{nullptr};
-static void sort_for_write(Data &d, bool by_name, int threads, Sorted &s)
+static BamBody sort_for_write(Data &d, bool by_name, int threads, bool may_stay)
 {
     const Clock::time_point t0 = Clock::now();
-    std::string *stream = s.stream;
-    s.stream = nullptr; s.route = "host";
+    BamBody body;
     const BamSortFn fn = by_name ? g_name_sort_device.load() : g_sort_device.load();
     if (fn) {
         std::vector<BgzfSpan> parts(d.enc.size());
         for (size_t k = 0; k < d.enc.size(); ++k) parts[k] = BgzfSpan{d.enc[k].data(), d.enc[k].size()};
         std::vector<uint32_t> perm;
-        BamSortJob job{parts.data(), parts.size(), d.recs.data(), d.recs.size(), &perm, stream, s.may_stay};
+        BamSortJob job{parts.data(), parts.size(), d.recs.data(), d.recs.size(), &perm, &body, may_stay};
         if (fn(job)) {
-            s.resident = job.resident;
             if (perm.size() != d.recs.size()) throw Error("internal: the device sort returned no permutation");
             std::vector<Rec> in_order(d.recs.size());
             const int T = threads; const size_t n = d.recs.size();
             par(T, T, [&](int t) { for (size_t i = n * (size_t)t / (size_t)T; i < n * ((size_t)t + 1) / (size_t)T; ++i) { if (perm[i] >= n) throw Error("internal: the device sort returned no permutation"); in_order[i] = d.recs[perm[i]]; } });
             d.recs.swap(in_order);
-            s.stream = job.resident ? nullptr : stream; s.route = "device";
-            s.ms_sort = ms_since(t0);
-            return;
+            body.in_parts = false; body.route = "device";
+            body.ms_sort = ms_since(t0);
+            return body;
         }
     }
-    sort_records(d, by_name);
-    s.ms_sort = ms_since(t0);
+    sort_in_order(d.recs, by_name, [&](const Rec &r) { return rec_name(d, r); });
+    body.ms_sort = ms_since(t0);
+    return body;
 }
 
 }  // namespace
@@ -567,8 +567,6 @@ static void sort_for_write(Data &d, bool by_name, int threads, Sorted &s)
 void bam_sort_set_device_hook(BamSortFn fn) { g_sort_device.store(fn); }
 void bam_name_sort_set_device_hook(BamSortFn fn) { g_name_sort_device.store(fn); }
 int bam_name_cmp(const char *a, const char *b) { return strnum_cmp(a, b); }
-
-static int clamp_threads(int t) { return t < 1 ? 1 : (t > 64 ? 64 : t); }
 
 // these run once per field of every record of ps_map_to_bam: raw stores into storage grown once per call, no append per byte
 static inline void st16(char *d, uint32_t v) { d[0] = (char)(v & 0xff); d[1] = (char)((v >> 8) & 0xff); }
@@ -618,6 +616,20 @@ void bam_rec_end(std::string &o, BamRec &r)
 struct BamSink::Impl {
     Data d; std::string path; bool sort = false, index = false, by_name = false; int threads = 1, level = 6;
     FILE *f = nullptr; uint64_t bytes = 0, n_out = 0; bool failed = false;
+    // a sorted sink keeps the buffer as one more part, which its records then name
+    void keep_part(std::string &&records, std::vector<BamRec> &recs)
+    {
+        for (BamRec &r : recs) r.part = (int)d.enc.size();
+        d.enc.push_back(std::move(records));
+        d.recs.insert(d.recs.end(), recs.begin(), recs.end());
+    }
+    // an unsorted one compresses the spans side by side and appends the blocks to the file
+    void append(const std::vector<BgzfSpan> &spans, int T)
+    {
+        std::vector<std::string> comp;
+        bgzf_batch(spans, level, T, comp);
+        for (const std::string &blk : comp) { if (std::fwrite(blk.data(), 1, blk.size(), f) != blk.size()) failed = true; bytes += blk.size(); }
+    }
 };
 BamSink::BamSink(const std::string &header_text, const std::vector<std::pair<std::string, uint32_t>> &refs, const char *bam_path,
                  bool sort_by_coordinate, bool write_index, int threads, int level, bool sort_by_name) : p(new Impl())
@@ -630,81 +642,52 @@ BamSink::BamSink(const std::string &header_text, const std::vector<std::pair<std
     if (p->sort) { header_sorted(p->d.text, "coordinate"); return; }
     p->f = std::fopen(bam_path, "wb");
     if (!p->f) { const std::string m = std::string("cannot write ") + bam_path; delete p; p = nullptr; throw Error(m); }
-    std::string head;
-    head.append("BAM\1", 4); put32(head, (uint32_t)p->d.text.size()); head += p->d.text; put32(head, (uint32_t)p->d.refs.size());
-    for (auto &r : p->d.refs) { put32(head, (uint32_t)r.first.size() + 1); head += r.first; head.push_back('\0'); put32(head, r.second); }
-    const size_t BLK = 0xff00;
-    std::vector<BgzfSpan> spans; std::vector<std::string> comp;
-    for (size_t a0 = 0; a0 < head.size(); a0 += BLK) spans.push_back(BgzfSpan{head.data() + a0, std::min(BLK, head.size() - a0)});
-    try { bgzf_batch(spans, p->level, 1, comp); } catch (...) { std::fclose(p->f); delete p; p = nullptr; throw; }
-    for (const std::string &blk : comp) {
-        if (std::fwrite(blk.data(), 1, blk.size(), p->f) != blk.size()) p->failed = true;
-        p->bytes += blk.size();
-    }
+    const std::string head = bam_header(p->d);
+    std::vector<BgzfSpan> spans;
+    bgzf_cut(head.data(), head.size(), spans);
+    try { p->append(spans, 1); } catch (...) { std::fclose(p->f); delete p; p = nullptr; throw; }
 }
 BamSink::~BamSink() { if (p) { if (p->f) std::fclose(p->f); delete p; } }
+// Unsorted: every buffer is cut into its own BGZF blocks (a record may span two blocks, a block never spans two buffers); all blocks
+// of the call are compressed side by side.
 void BamSink::add(std::vector<std::string> &records, std::vector<std::vector<BamRec>> &recs, uint64_t n_in)
 {
     p->d.n_in += n_in;
-    if (p->sort) {
-        for (size_t k = 0; k < records.size(); ++k) {
-            const int part = (int)p->d.enc.size();
-            for (BamRec &r : recs[k]) r.part = part;
-            p->d.enc.push_back(std::move(records[k]));
-            p->d.recs.insert(p->d.recs.end(), recs[k].begin(), recs[k].end());
-        }
-        return;
-    }
-    // every buffer is cut into its own BGZF blocks (a record may span two blocks, a block never spans two buffers); all blocks of
-    // the call are compressed side by side
-    const size_t BLK = 0xff00;
-    std::vector<std::pair<size_t, size_t>> blk;              // (buffer, offset)
-    for (size_t k = 0; k < records.size(); ++k) { p->n_out += recs[k].size(); for (size_t a0 = 0; a0 < records[k].size(); a0 += BLK) blk.emplace_back(k, a0); }
-    std::vector<BgzfSpan> spans(blk.size()); std::vector<std::string> comp;
-    for (size_t j = 0; j < blk.size(); ++j) { const std::string &src = records[blk[j].first]; spans[j] = BgzfSpan{src.data() + blk[j].second, std::min(BLK, src.size() - blk[j].second)}; }
-    bgzf_batch(spans, p->level, p->threads, comp);
-    for (size_t j = 0; j < comp.size(); ++j) { if (std::fwrite(comp[j].data(), 1, comp[j].size(), p->f) != comp[j].size()) p->failed = true; p->bytes += comp[j].size(); }
+    if (p->sort) { for (size_t k = 0; k < records.size(); ++k) p->keep_part(std::move(records[k]), recs[k]); return; }
+    std::vector<BgzfSpan> spans;
+    for (size_t k = 0; k < records.size(); ++k) { p->n_out += recs[k].size(); bgzf_cut(records[k].data(), records[k].size(), spans); }
+    p->append(spans, p->threads);
     records.clear(); recs.clear();
 }
 void BamSink::add(const char *records, size_t n_bytes, std::vector<BamRec> &recs, uint64_t n_in)
 {
     p->d.n_in += n_in;
-    if (p->sort) {
-        const int part = (int)p->d.enc.size();
-        for (BamRec &r : recs) r.part = part;
-        p->d.enc.emplace_back(records, n_bytes);
-        p->d.recs.insert(p->d.recs.end(), recs.begin(), recs.end());
-        recs.clear();
-        return;
+    if (p->sort) p->keep_part(std::string(records, n_bytes), recs);
+    else {
+        p->n_out += recs.size();
+        std::vector<BgzfSpan> spans;
+        bgzf_cut(records, n_bytes, spans);
+        p->append(spans, p->threads);
     }
-    const size_t BLK = 0xff00;
-    p->n_out += recs.size();
-    std::vector<BgzfSpan> spans; std::vector<std::string> comp;
-    for (size_t a0 = 0; a0 < n_bytes; a0 += BLK) spans.push_back(BgzfSpan{records + a0, std::min(BLK, n_bytes - a0)});
-    bgzf_batch(spans, p->level, p->threads, comp);
-    for (size_t j = 0; j < comp.size(); ++j) { if (std::fwrite(comp[j].data(), 1, comp[j].size(), p->f) != comp[j].size()) p->failed = true; p->bytes += comp[j].size(); }
     recs.clear();
 }
 void BamSink::finish(BamStats *stats, BamFile *keep)
 {
     if (keep && !p->sort) throw Error("internal: only a sorted BAM is kept in memory");
     if (p->sort) {
-        std::string stream; Sorted s; s.stream = &stream; s.may_stay = keep == nullptr;
-        sort_for_write(p->d, p->by_name, p->threads, s);
-        write_bam(p->d, p->path.c_str(), p->index, p->threads, stats, p->level, keep != nullptr, &s);
-        if (keep && s.stream) {                                 // the device route's stream is the kept file's one part
+        BamBody body = sort_for_write(p->d, p->by_name, p->threads, keep == nullptr);
+        if (keep && body.device) throw Error("internal: a kept file needs its records on the host");
+        write_bam(p->d, body, p->path.c_str(), p->index, p->threads, stats, p->level);
+        if (keep) {                                             // the file's records, in file order, for the step that would read it back: the stream is their one part
             uint64_t at = 0;
             for (Rec &r : p->d.recs) { r.part = 0; r.off = (size_t)at; at += r.len; }
-            p->d.enc.assign(1, std::string()); p->d.enc[0].swap(stream);
-        }
-        if (keep) {                                             // the file's records, in file order, for the step that would read it back
             *keep = BamFile();
             keep->sort_order = p->by_name ? "queryname" : "coordinate";
-            keep->text.swap(p->d.text); keep->refs.swap(p->d.refs); keep->enc.swap(p->d.enc); keep->recs.swap(p->d.recs);
+            keep->text.swap(p->d.text); keep->refs.swap(p->d.refs); keep->recs.swap(p->d.recs);
+            keep->enc.assign(1, std::string()); keep->enc[0].swap(body.host);
         }
         return;
     }
-    static const unsigned char eof_block[28] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 66, 67, 2, 0, 27, 0, 3, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     bool ok = !p->failed && std::fwrite(eof_block, 1, 28, p->f) == 28;
     ok = (std::fclose(p->f) == 0) && ok;
     p->f = nullptr;
@@ -720,9 +703,9 @@ void sam_to_bam(const char *sam_path, const char *bam_path, int min_mapq, bool s
     files.refuse_inputs({sam_path}, "ps_sam_to_bam: ");
     Data d;
     load_sam(sam_path, min_mapq, threads, d);
-    std::string stream; Sorted s; s.stream = &stream; s.may_stay = true;
-    if (sort_by_coordinate) { header_sorted(d.text, "coordinate"); sort_for_write(d, false, threads, s); } else s.stream = nullptr;
-    write_bam(d, t.c_str(), write_index, threads, stats, 6, false, &s);
+    BamBody body;
+    if (sort_by_coordinate) { header_sorted(d.text, "coordinate"); body = sort_for_write(d, false, threads, true); }
+    write_bam(d, body, t.c_str(), write_index, threads, stats);
     files.publish_all(); files.keep();
 }
 
@@ -739,7 +722,8 @@ void bam_view(const char *in_bam, const char *out_bam, int min_mapq, int threads
         for (const Rec &r : d.recs) if (rec_mapq(d, r) >= min_mapq) keep.push_back(r);
         d.recs.swap(keep);
     }
-    write_bam(d, t.c_str(), false, threads, stats);
+    BamBody body;
+    write_bam(d, body, t.c_str(), false, threads, stats);
     files.publish_all(); files.keep();
 }
 
@@ -752,9 +736,8 @@ void bam_sort(const char *in_bam, const char *out_bam, bool by_name, int threads
     Data d;
     load_bam(in_bam, threads, d, nullptr, nullptr);
     header_sorted(d.text, by_name ? "queryname" : "coordinate");
-    std::string stream; Sorted s; s.stream = &stream; s.may_stay = true;
-    sort_for_write(d, by_name, threads, s);
-    write_bam(d, t.c_str(), false, threads, stats, 6, false, &s);
+    BamBody body = sort_for_write(d, by_name, threads, true);
+    write_bam(d, body, t.c_str(), false, threads, stats);
     files.publish_all(); files.keep();
 }
 
@@ -766,10 +749,7 @@ void bam_index(const char *bam, int threads)
     files.refuse_inputs({bam}, "ps_bam_index: ");
     Data d; Blocks bk; std::vector<uint64_t> rec_u;
     load_bam(bam, threads, d, &bk, &rec_u);
-    for (size_t i = 1; i < d.recs.size(); ++i) {
-        const uint32_t a = (uint32_t)d.recs[i - 1].ref, c = (uint32_t)d.recs[i].ref;
-        if (a > c || (a == c && d.recs[i - 1].pos > d.recs[i].pos)) throw Error(std::string("not sorted by coordinate: ") + bam);
-    }
+    for (size_t i = 1; i < d.recs.size(); ++i) if (CoordinateLess()(d.recs[i], d.recs[i - 1])) throw Error(std::string("not sorted by coordinate: ") + bam);
     auto voff = [&](uint64_t u) -> uint64_t {           // uncompressed offset -> (compressed block start << 16) | offset inside
         size_t lo = 0, hi = bk.starts.size();
         while (hi - lo > 1) { const size_t mid = (lo + hi) / 2; if (bk.starts[mid].second <= u) lo = mid; else hi = mid; }
@@ -833,34 +813,13 @@ void scan_records(const char *records, uint64_t n_bytes, std::vector<BamRec> &re
     }
 }
 
-// the sorted records' bytes into dst, back to back, on threads
-static void gather_records(const char *records, const std::vector<BamRec> &recs, int threads, char *dst)
+static void sort_and_gather(const char *records, std::vector<BamRec> &recs, bool by_name, int threads, char *dst)
 {
-    threads = clamp_threads(threads);
-    std::vector<uint64_t> uoff(recs.size() + 1, 0);
-    for (size_t i = 0; i < recs.size(); ++i) uoff[i + 1] = uoff[i] + recs[i].len;
-    const size_t n = recs.size();
-    par(threads, threads, [&](int t) { for (size_t i = n * (size_t)t / (size_t)threads; i < n * ((size_t)t + 1) / (size_t)threads; ++i) std::memcpy(dst + uoff[i], records + recs[i].off, recs[i].len); });
+    sort_in_order(recs, by_name, [&](const Rec &r) { return records + r.off + 36; });
+    gather(recs, stream_offsets(recs), clamp_threads(threads), dst, [&](const Rec &) { return records; });
 }
-
-void sort_records_host(const char *records, std::vector<BamRec> &recs, int threads, char *dst)
-{
-    std::stable_sort(recs.begin(), recs.end(), [](const Rec &x, const Rec &y) {
-        const uint32_t a = (uint32_t)x.ref, c = (uint32_t)y.ref;
-        return a != c ? a < c : x.pos < y.pos;
-    });
-    gather_records(records, recs, threads, dst);
-}
-
-void sort_records_host_by_name(const char *records, std::vector<BamRec> &recs, int threads, char *dst)
-{
-    std::stable_sort(recs.begin(), recs.end(), [&](const Rec &x, const Rec &y) {
-        const int c = strnum_cmp(records + x.off + 36, records + y.off + 36);
-        if (c) return c < 0;
-        return ((x.flag >> 6) & 3) < ((y.flag >> 6) & 3);                 // first of pair before second
-    });
-    gather_records(records, recs, threads, dst);
-}
+void sort_records_host(const char *records, std::vector<BamRec> &recs, int threads, char *dst) { sort_and_gather(records, recs, false, threads, dst); }
+void sort_records_host_by_name(const char *records, std::vector<BamRec> &recs, int threads, char *dst) { sort_and_gather(records, recs, true, threads, dst); }
 
 void flatten_records(const BamFile &f, unsigned columns, const std::vector<int32_t> *rows, int threads, RecTable &out)
 {
@@ -950,8 +909,8 @@ void extract_weak_reads(const char *path, const char *out_bam, const char *out_f
     }
     const uint64_t n_records = d.recs.size();
     d.recs.swap(keep);
-    BamStats bs;
-    write_bam(d, t_bam.c_str(), false, threads, &bs);
+    BamStats bs; BamBody body;
+    write_bam(d, body, t_bam.c_str(), false, threads, &bs);
     write_text_file(t_fq, fq);
     files.publish_all(); files.keep();
     if (stats) { stats->n_records = n_records; stats->n_weak = n_weak; stats->n_kept = bs.n_out; stats->bam_bytes = bs.bam_bytes; }

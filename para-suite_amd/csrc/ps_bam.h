@@ -1,37 +1,50 @@
 // ps_bam.h -- SAM text -> BAM / sorted BAM + .bai, and the same operations on BAM input (host only, zlib).
 #pragma once
 #include <stdint.h>
+#include <algorithm>
+#include <memory>
 #include <string>
 #include <utility>
 #include <vector>
 #include "ps_outfiles.h"
 namespace ps {
 struct BamStats { uint64_t n_in = 0, n_out = 0, bam_bytes = 0; };
-// Every BGZF block of every writer below is made by one batch function (ps_bam.cpp: bgzf_batch): spans of at most 0xff00 bytes ->
+// Every BGZF block of every writer below is made by one batch function (ps_bam.cpp: bgzf_batch): spans of at most kBgzfBlock bytes ->
 // comp[k], the whole gzip member of spans[k].  By default zlib on host threads.  A compressor registered here takes the whole
 // list instead (the device compressor of ps_bgzf.hip; this file and ps_bam.cpp stay free of HIP); it throws ps::Error, and the
 // writing call fails with it -- there is no fallback to zlib.  Null: zlib again.
 struct BgzfSpan { const char *p; size_t n; };
+const size_t kBgzfBlock = 0xff00;                 // the input bytes of one block, and where every writer cuts
+inline void bgzf_cut(const char *p, size_t n, std::vector<BgzfSpan> &spans) { for (size_t a = 0; a < n; a += kBgzfBlock) spans.push_back(BgzfSpan{p + a, std::min(kBgzfBlock, n - a)}); }   // [p, p + n) in blocks, appended
 typedef void (*BgzfBatchFn)(const BgzfSpan *spans, size_t n_spans, std::string *comp);
 void bgzf_set_device_compressor(BgzfBatchFn fn);
 void bgzf_host_compress(const BgzfSpan *spans, size_t n_spans, int level, int threads, std::string *comp);   // the host path itself, whatever is registered
-// The coordinate sort of every writer below (BamSink::finish, sam_to_bam, bam_sort) is one std::stable_sort on one thread plus a gather
-// of the records into the file's stream on host threads.  A hook registered here takes both instead (ps_bamsort.hip: the key, the
-// radix sort and the gather on the device; this file and ps_bam.cpp stay free of HIP): it fills perm, the sorted order, and stream,
-// the records in that order back to back.  It returns false when it leaves the call to the host route (and counts that), throws
-// ps::Error on a device error -- the writing call fails with it, there is no fallback.  Null: the host route.  The name sort (`samtools
-// sort -n`'s order, bam_name_cmp, then first of pair before second) has a hook of its own with the same contract: ps_bamsort.hip's
-// name route, whose key ps_namesort.h states.  Each sort asks its own hook and never the other's.
+// one member: the 16 fixed bytes with the BC field, BSIZE, the DEFLATE payload, CRC32 and ISIZE of the input -- for both compressors
+void bgzf_member(const void *payload, size_t n_payload, uint32_t crc, uint32_t isize, std::string &out);
+// THE BODY of a file: where the records' bytes are, in file order.  Still in the parts the records name (write_bam gathers them),
+// one stream on the host, or one stream on a device.  The value owns what it names: a device stream goes back to where it came from
+// when the body is destroyed, whether its blocks were made or not.
+struct DeviceStream {                             // ps_bamsort.hip implements it; no HIP here
+    virtual ~DeviceStream() {}
+    virtual void blocks(std::string *comp) = 0;   // the BGZF members of the stream cut at kBgzfBlock bytes, comp[k] for block k; at most once
+};
+struct BamBody {
+    std::string host; std::unique_ptr<DeviceStream> device; bool in_parts = true;   // in_parts: neither stream holds anything yet
+    double ms_sort = -1; const char *route = "host";                                // of the sort that made it, for write_bam's stage line (PS_VERBOSE)
+};
+// The sort of every writer below (BamSink::finish, sam_to_bam, bam_sort) is one std::stable_sort on one thread; write_bam then gathers
+// the records into the file's stream on host threads.  A hook registered here takes both instead (ps_bamsort.hip: the key, the
+// radix sort and the gather on the device; this file and ps_bam.cpp stay free of HIP): it fills perm, the sorted order, and body:
+// the records in that order back to back in body->host, or -- only when may_stay says that the caller can do without the stream on
+// the host, and the BGZF switch names the hook's device -- in body->device.  It returns false when it leaves the call to the host
+// route (and counts that; body is as it was), throws ps::Error on a device error -- the writing call fails with it, there is no
+// fallback.  Null: the host route.  The name sort (`samtools sort -n`'s order, bam_name_cmp, then first of pair before second) has a
+// hook of its own with the same contract: ps_bamsort.hip's name route, whose key ps_namesort.h states.  Each sort asks its own hook.
 struct BamRec;
 struct BamSortJob {
     const BgzfSpan *parts; size_t n_parts;        // the buffers the records lie in; recs[i].part names one
     const BamRec *recs; size_t n_recs;
-    std::vector<uint32_t> *perm; std::string *stream;
-    // may_stay (in): the caller can do without the stream on the host.  The hook may then leave the sorted stream on the device (the one
-    // the BGZF switch names), leave `stream` empty and set `resident`: resident(comp) makes the BGZF members of the stream cut at 0xff00
-    // bytes, comp[k] for block k, and gives the device buffer back, also when it throws; resident(nullptr) only gives it back.  The
-    // caller calls it exactly once.
-    bool may_stay = false; void (*resident)(std::string *comp) = nullptr;
+    std::vector<uint32_t> *perm; BamBody *body; bool may_stay = false;
 };
 typedef bool (*BamSortFn)(BamSortJob &job);
 void bam_sort_set_device_hook(BamSortFn fn);
@@ -54,7 +67,7 @@ void bam_rec_end(std::string &o, BamRec &r);                                    
 // compression of one piece of the input runs while the next is searched.  Coordinate-sorted output (+ .bai): the parts are kept and
 // sorted, compressed and written by finish().  sort_by_name: the same with the names ordered as `samtools sort -n` orders them
 // (ps_bam_sort's rule) under @HD SO:queryname.  finish(.., keep): the records of the sorted file stay in memory, in file order, as
-// load_records() would return them (ps_map_route hands them to the lift instead of reading the file back).
+// load_records() would return them -- the file's stream as the one part (ps_map_route hands them to the lift instead of reading the file back).
 struct BamFile;
 class BamSink {
 public:
@@ -97,6 +110,8 @@ void sort_records_host(const char *records, std::vector<BamRec> &recs, int threa
 // the name order's comparator (read names as `samtools sort -n` orders them: digit runs compare as numbers; NUL-terminated), and the
 // host route of that order: recs (every name ends inside its record) by bam_name_cmp, then the pair bits of the flag, then gathered
 int bam_name_cmp(const char *a, const char *b);
+// l_read_name (byte 12 of a record, block_size first) counts the NUL that ends the name at byte 36 + l_read_name - 1
+inline bool name_ends_inside(const uint8_t *rec, size_t len) { return len >= 37 && rec[12] >= 1 && 36 + (size_t)rec[12] <= len && rec[36 + rec[12] - 1] == 0; }
 void sort_records_host_by_name(const char *records, std::vector<BamRec> &recs, int threads, char *dst);
 // The record table: the fields of the records of a BamFile as flat arrays, for the analysis modes' kernels.
 // ref, pos, flag and l_seq always; the other columns by mask.  BAM conventions throughout: pos 0-based (a kernel that wants

@@ -5,7 +5,7 @@
 // orders (key, index) over the bits that any key has set; k_bamsort_lens and an exclusive sum give every record of the sorted order
 // its destination; k_bamsort_gather -- ps_bamsort.h's group, one wave per 64 consecutive records -- moves the bytes.  The permutation
 // comes down at 4 bytes per record, the stream through the same staging -- unless the caller can do without it and the BGZF switch
-// names the same device: then the stream stays where it is and ps_bgzf.hip's compressor reads it there (resident_blocks).  No
+// names the same device: then the stream stays where it is and ps_bgzf.hip's compressor reads it there (ResidentStream).  No
 // workgroup waits for another.
 //
 // The name sort (ps_bam_name_sort_device, PS_BAM_NAME_SORT_GPU, ps_bam_name_sort_records) is the same route with another order:
@@ -18,6 +18,7 @@
 #include <atomic>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <thread>
 #define PS_BS_DEVICE
@@ -119,18 +120,18 @@ struct Buffers {                                    // grow-only, kept between c
 };
 std::mutex g_mu;
 Buffers &buffers() { static Buffers *b = new Buffers(); return *b; }
-std::atomic<int> g_device{-1}, g_name_device{-1};         // the two switches
-struct Totals { std::mutex mu; BamSortStats s; };
-Totals &totals() { static Totals *t = new Totals(); return *t; }
-struct NameTotals { std::mutex mu; BamNameSortStats s; };
-NameTotals &name_totals() { static NameTotals *t = new NameTotals(); return *t; }
-
-void check_device(int device)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error("ps_bam_sort: no HIP device available");
-    if (device < 0 || device >= n) throw Error("ps_bam_sort: no HIP device " + std::to_string(device) + " (" + std::to_string(n) + " present)");
-}
+// One order's switch: the device it names (-1: off), the totals of its calls since it was last set, and what ties it to ps_bam.cpp --
+// the environment variable that sets it when the library is loaded, where the hook is registered, the hook.  Two instances, never
+// destroyed (a writer may run during exit).
+template <class Stats> struct Switch {
+    const char *env; void (*set_hook)(BamSortFn); BamSortFn hook;
+    std::atomic<int> device{-1}; std::mutex mu; Stats total;
+    Switch(const char *e, void (*set)(BamSortFn), BamSortFn h) : env(e), set_hook(set), hook(h) {}
+};
+bool device_hook(BamSortJob &job);
+bool name_device_hook(BamSortJob &job);
+Switch<BamSortStats> &by_coordinate() { static auto *s = new Switch<BamSortStats>("PS_BAM_SORT_GPU", &bam_sort_set_device_hook, &device_hook); return *s; }
+Switch<BamNameSortStats> &by_name() { static auto *s = new Switch<BamNameSortStats>("PS_BAM_NAME_SORT_GPU", &bam_name_sort_set_device_hook, &name_device_hook); return *s; }
 
 void copy_threads(void *dst, const void *src, size_t n)
 {
@@ -160,67 +161,80 @@ uint64_t max_device_bytes()
     return mb < 0 ? 0 : (uint64_t)mb << 20;
 }
 
-void count(const BamSortStats &x)
+// what the name order counts beside the common fields
+void count_own(BamSortStats &, const BamSortStats &) {}
+void count_own(BamNameSortStats &t, const BamNameSortStats &x) { t.n_passes += x.n_passes; if (x.n_calls_device) t.key_words = x.key_words; t.ms_keys += x.ms_keys; }
+template <class Stats> void count(Switch<Stats> &sw, const Stats &x)
 {
-    Totals &t = totals(); std::lock_guard<std::mutex> l(t.mu);
-    t.s.n_records += x.n_records; t.s.bytes += x.bytes; t.s.n_calls_device += x.n_calls_device; t.s.n_calls_host += x.n_calls_host; t.s.n_resident += x.n_resident;
-    t.s.ms_upload += x.ms_upload; t.s.ms_sort += x.ms_sort; t.s.ms_gather += x.ms_gather; t.s.ms_download += x.ms_download;
+    std::lock_guard<std::mutex> l(sw.mu); Stats &t = sw.total;
+    t.n_records += x.n_records; t.bytes += x.bytes; t.n_calls_device += x.n_calls_device; t.n_calls_host += x.n_calls_host; t.n_resident += x.n_resident;
+    t.ms_upload += x.ms_upload; t.ms_sort += x.ms_sort; t.ms_gather += x.ms_gather; t.ms_download += x.ms_download;
+    count_own(t, x);
 }
+void count(const BamSortStats &x) { count(by_coordinate(), x); }
+void count(const BamNameSortStats &x) { count(by_name(), x); }
 
-void count(const BamNameSortStats &x)
-{
-    NameTotals &t = name_totals(); std::lock_guard<std::mutex> l(t.mu);
-    t.s.n_records += x.n_records; t.s.bytes += x.bytes; t.s.n_calls_device += x.n_calls_device; t.s.n_calls_host += x.n_calls_host; t.s.n_resident += x.n_resident;
-    t.s.n_passes += x.n_passes; if (x.n_calls_device) t.s.key_words = x.key_words;
-    t.s.ms_upload += x.ms_upload; t.s.ms_keys += x.ms_keys; t.s.ms_sort += x.ms_sort; t.s.ms_gather += x.ms_gather; t.s.ms_download += x.ms_download;
-}
-
-// The sorted stream of one call that stayed on the device, between the sort and the compression of its blocks: the buffer is taken
-// out of the grow-only set for that time (another thread's sort gets its own) and goes back afterwards.  One at a time: a second call
-// that finds the slot taken brings its stream down as usual.
-struct Resident { std::mutex mu; bool busy = false; DevBuf<uint8_t> out; uint64_t bytes = 0; int device = -1; };
-Resident &resident() { static Resident *r = new Resident(); return *r; }
-void resident_blocks(std::string *comp)
-{
-    Resident &r = resident();
-    struct GiveBack {
-        Resident &r;
-        ~GiveBack()
-        {
-            {
-                std::lock_guard<std::mutex> lock(g_mu);
-                Buffers &b = buffers();
-                int before = -1; (void)hipGetDevice(&before);
-                if (hipSetDevice(r.device) == hipSuccess) { if (b.device == r.device && b.out.n < r.out.n) b.out = std::move(r.out); else r.out.release(); }
-                if (before >= 0) (void)hipSetDevice(before);
-            }
-            std::lock_guard<std::mutex> l(r.mu); r.busy = false; r.bytes = 0;
+// The sorted stream of one call that stayed on the device, between the sort and the compression of its blocks (ps_bam.h: the device
+// case of a BamBody): the buffer is taken out of the grow-only set for that time (another thread's sort gets its own) and goes back
+// when the stream is destroyed -- if it is larger than what the set holds by then; otherwise it is freed.  One at a time: a second
+// call that finds the slot taken brings its stream down as usual.  run_route claims the slot before its first device call, so an
+// error on the way frees it with the empty stream.
+std::atomic<bool> g_resident_taken{false};
+struct ResidentStream : DeviceStream {
+    DevBuf<uint8_t> out; uint64_t bytes = 0; int device = -1;
+    static std::unique_ptr<ResidentStream> claim() { bool taken = false; return std::unique_ptr<ResidentStream>(g_resident_taken.compare_exchange_strong(taken, true) ? new ResidentStream() : nullptr); }
+    ~ResidentStream() override
+    {
+        if (out.p) {
+            std::lock_guard<std::mutex> lock(g_mu);
+            Buffers &b = buffers();
+            QuietDeviceScope scope(device);
+            if (scope.ok) { if (b.device == device && b.out.n < out.n) b.out = std::move(out); else out.release(); }
         }
-    } give{r};
-    if (comp) bgzf_device_compress_resident(r.out.p, r.bytes, r.device, comp, nullptr);
+        g_resident_taken = false;
+    }
+    void blocks(std::string *comp) override { bgzf_device_compress_resident(out.p, bytes, device, comp, nullptr); }
+};
+
+bool device_hook(BamSortJob &job) { return bam_sort_device_run(job, by_coordinate().device, nullptr); }
+bool name_device_hook(BamSortJob &job) { return bam_name_sort_device_run(job, by_name().device, nullptr); }
+
+// PS_BAM_SORT_GPU=<device>, PS_BAM_NAME_SORT_GPU=<device>: read once, when the library is loaded; a device that is not there fails the first sorting call
+template <class Stats> void read_env(Switch<Stats> &sw)
+{
+    const char *e = std::getenv(sw.env);
+    if (e && e[0]) { const int d = std::atoi(e); if (d >= 0) { sw.device = d; sw.set_hook(sw.hook); } }
 }
+[[maybe_unused]] const bool g_env_read = [] { read_env(by_coordinate()); read_env(by_name()); return true; }();
 
-bool device_hook(BamSortJob &job) { return bam_sort_device_run(job, g_device, nullptr); }
-bool name_device_hook(BamSortJob &job) { return bam_name_sort_device_run(job, g_name_device, nullptr); }
-
-// PS_BAM_SORT_GPU=<device>: read once, when the library is loaded; a device that is not there fails the first sorting call
-[[maybe_unused]] const bool g_env_read = [] {
-    const char *e = std::getenv("PS_BAM_SORT_GPU");
-    if (e && e[0]) { const int d = std::atoi(e); if (d >= 0) { g_device = d; bam_sort_set_device_hook(&device_hook); } }
-    return true;
-}();
-[[maybe_unused]] const bool g_name_env_read = [] {
-    const char *e = std::getenv("PS_BAM_NAME_SORT_GPU");
-    if (e && e[0]) { const int d = std::atoi(e); if (d >= 0) { g_name_device = d; bam_name_sort_set_device_hook(&name_device_hook); } }
-    return true;
-}();
-
-// the device and page-locked buffers go back when the last of the two switches goes off (g_mu held)
-void release_buffers()
+// what no switch needs any more goes back (g_mu held): the name order's rows when its switch is off, every device and page-locked
+// buffer when both are
+void release_unused()
 {
     Buffers &b = buffers();
-    if (b.device >= 0) { int before = -1; (void)hipGetDevice(&before); if (hipSetDevice(b.device) == hipSuccess) b.release(); if (before >= 0) (void)hipSetDevice(before); b.device = -1; }
-    b.release_host();
+    const bool coordinate_on = by_coordinate().device >= 0, name_on = by_name().device >= 0;
+    if (b.device >= 0 && !name_on) { QuietDeviceScope scope(b.device); if (scope.ok) { if (coordinate_on) { b.col.release(); b.col_bits.release(); } else b.release(); } }
+    if (!coordinate_on && !name_on) { b.device = -1; b.release_host(); }
+}
+
+template <class Stats> void set_device(Switch<Stats> &sw, int device)
+{
+    if (device >= 0) check_device("ps_bam_sort", device);
+    { std::lock_guard<std::mutex> l(sw.mu); sw.total = Stats(); }
+    if (device < 0) {                               // switched off: the buffers go back too (a later ps_bam_sort_records takes its own again)
+        sw.set_hook(nullptr); sw.device = -1;
+        std::lock_guard<std::mutex> lock(g_mu);
+        release_unused();
+        return;
+    }
+    sw.device = device;
+    sw.set_hook(sw.hook);
+}
+
+template <class Stats> void info(Switch<Stats> &sw, Stats &out)
+{
+    std::lock_guard<std::mutex> l(sw.mu);
+    out = sw.total; out.on_device = sw.device >= 0;
 }
 
 // One call of either route.  The stages are the same for both orders: the records checked against their buffers and the memory bound
@@ -247,15 +261,14 @@ template <class Order> bool run_route(BamSortJob &job, int device, Order &order)
         return false;
     }
     st.on_device = 1; st.n_calls_device = 1; st.n_records = n; st.bytes = total;
-    job.resident = nullptr;
-    bool stay = false;
-    if (n && job.may_stay && bgzf_device_current() == device) { Resident &r = resident(); std::lock_guard<std::mutex> l(r.mu); if (!r.busy) { r.busy = true; stay = true; } }
-    struct Unbusy { bool armed; ~Unbusy() { if (armed) { Resident &r = resident(); std::lock_guard<std::mutex> l(r.mu); r.busy = false; } } } unbusy{stay};   // an error on the way
-    job.perm->assign(n, 0); job.stream->assign(stay ? 0 : (size_t)total, '\0');
+    job.body->device.reset();
+    std::unique_ptr<ResidentStream> stay;
+    if (n && job.may_stay && bgzf_device_current() == device) stay = ResidentStream::claim();
+    job.perm->assign(n, 0); job.body->host.assign(stay ? 0 : (size_t)total, '\0');
     if (n == 0) { count(st); return true; }
 
     std::lock_guard<std::mutex> lock(g_mu);
-    check_device(device);
+    check_device("ps_bam_sort", device);
     DeviceScope scope(device);
     Buffers &b = buffers();
     if (b.device != device) { b.release(); b.device = device; }
@@ -347,21 +360,19 @@ template <class Order> bool run_route(BamSortJob &job, int device, Order &order)
             }
         };
         down((const uint8_t *)perm, (char *)job.perm->data(), n * sizeof(uint32_t));
-        if (!stay) down(b.out.p, &(*job.stream)[0], (size_t)total);
+        if (!stay) down(b.out.p, &job.body->host[0], (size_t)total);
         stg.wait_all();
         if (prev.h) copy_threads(prev.dst, prev.h, prev.bytes);
     }
     st.ms_download = ms_since(t0);
-    if (stay) {                                     // the stream's buffer leaves the set until its blocks are made
-        Resident &r = resident();
-        r.out = std::move(b.out); r.bytes = total; r.device = device;
-        unbusy.armed = false;
-        job.resident = &resident_blocks;
+    if (stay) {                                     // the stream's buffer leaves the set until the body is destroyed
+        stay->out = std::move(b.out); stay->bytes = total; stay->device = device;
+        job.body->device = std::move(stay);
         st.n_resident = 1;
     }
     count(st);
     static const bool verbose = std::getenv("PS_VERBOSE") != nullptr;
-    if (verbose) order.report(n, total, device, stay ? " (the permutation alone: the stream stays for the compressor)" : "");
+    if (verbose) order.report(n, total, device, st.n_resident ? " (the permutation alone: the stream stays for the compressor)" : "");
     return true;
 }
 
@@ -405,7 +416,7 @@ struct NameOrder {
             for (size_t i = a0; i < a1; ++i) {
                 const BamRec &r = job.recs[i];
                 const uint8_t *p = (const uint8_t *)job.parts[r.part].p + r.off;
-                if (r.len < 37 || p[12] < 1 || 36 + (size_t)p[12] > r.len || p[36 + p[12] - 1] != 0) { ok = false; return; }
+                if (!name_ends_inside(p, r.len)) { ok = false; return; }
                 const uint32_t l = (uint32_t)strnlen((const char *)p + 36, p[12] - 1u);
                 name_len[i] = (uint8_t)l; m = std::max(m, l);
             }
@@ -463,63 +474,19 @@ struct NameOrder {
 
 }  // namespace
 
-void bam_sort_set_device(int device)
-{
-    if (device >= 0) check_device(device);
-    { Totals &t = totals(); std::lock_guard<std::mutex> l(t.mu); t.s = BamSortStats(); }
-    if (device < 0) {                               // switched off: the buffers go back too (a later ps_bam_sort_records takes its own again)
-        bam_sort_set_device_hook(nullptr); g_device = -1;
-        std::lock_guard<std::mutex> lock(g_mu);
-        if (g_name_device < 0) release_buffers();
-        return;
-    }
-    g_device = device;
-    bam_sort_set_device_hook(&device_hook);
-}
+void bam_sort_set_device(int device) { set_device(by_coordinate(), device); }
+void bam_sort_info(BamSortStats &out) { info(by_coordinate(), out); }
+void bam_name_sort_set_device(int device) { set_device(by_name(), device); }
+void bam_name_sort_info(BamNameSortStats &out) { info(by_name(), out); }
 
-void bam_sort_info(BamSortStats &out)
+template <class Order, class Stats> static bool run_order(BamSortJob &job, int device, Stats *stats)
 {
-    Totals &t = totals(); std::lock_guard<std::mutex> l(t.mu);
-    out = t.s; out.on_device = g_device >= 0;
-}
-
-
-bool bam_sort_device_run(BamSortJob &job, int device, BamSortStats *stats)
-{
-    CoordinateOrder order;
+    Order order;
     const bool done = run_route(job, device, order);
     if (stats) *stats = order.st;
     return done;
 }
-
-void bam_name_sort_set_device(int device)
-{
-    if (device >= 0) check_device(device);
-    { NameTotals &t = name_totals(); std::lock_guard<std::mutex> l(t.mu); t.s = BamNameSortStats(); }
-    if (device < 0) {                               // switched off: the rows go back, and what the coordinate switch does not need
-        bam_name_sort_set_device_hook(nullptr); g_name_device = -1;
-        std::lock_guard<std::mutex> lock(g_mu);
-        Buffers &b = buffers();
-        if (g_device < 0) release_buffers();
-        else if (b.device >= 0) { int before = -1; (void)hipGetDevice(&before); if (hipSetDevice(b.device) == hipSuccess) { b.col.release(); b.col_bits.release(); } if (before >= 0) (void)hipSetDevice(before); }
-        return;
-    }
-    g_name_device = device;
-    bam_name_sort_set_device_hook(&name_device_hook);
-}
-
-void bam_name_sort_info(BamNameSortStats &out)
-{
-    NameTotals &t = name_totals(); std::lock_guard<std::mutex> l(t.mu);
-    out = t.s; out.on_device = g_name_device >= 0;
-}
-
-bool bam_name_sort_device_run(BamSortJob &job, int device, BamNameSortStats *stats)
-{
-    NameOrder order;
-    const bool done = run_route(job, device, order);
-    if (stats) *stats = order.st;
-    return done;
-}
+bool bam_sort_device_run(BamSortJob &job, int device, BamSortStats *stats) { return run_order<CoordinateOrder>(job, device, stats); }
+bool bam_name_sort_device_run(BamSortJob &job, int device, BamNameSortStats *stats) { return run_order<NameOrder>(job, device, stats); }
 
 }  // namespace ps

@@ -17,6 +17,7 @@
 namespace ps {
 
 static_assert(sizeof(DfShared) <= 48 * 1024, "k_bgzf: static LDS");
+static_assert((size_t)DF_BLOCK == kBgzfBlock, "the encoder's block is the writers' cut");
 static_assert(DF_OUT_STRIDE % 16 == 0 && DF_OUT_STRIDE >= DF_BLOCK + 8, "k_bgzf: room for n + 5 bytes in whole words");
 
 // block k of the round: in[offs[k], offs[k + 1]) -> out + k * DF_OUT_STRIDE, res[k]; tok: one word per input byte of the round
@@ -57,13 +58,6 @@ std::mutex g_mu;
 Buffers &buffers() { static Buffers *b = new Buffers(); return *b; }
 std::atomic<int> g_device{-1};
 
-void check_device(int device)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error("ps_bgzf: no HIP device available");
-    if (device < 0 || device >= n) throw Error("ps_bgzf: no HIP device " + std::to_string(device) + " (" + std::to_string(n) + " present)");
-}
-
 uint32_t allowed_encodings()
 {
     const char *e = std::getenv("PS_BGZF_BTYPE");
@@ -99,11 +93,11 @@ void bgzf_set_device(int device)
         bgzf_set_device_compressor(nullptr); g_device = -1;
         std::lock_guard<std::mutex> lock(g_mu);
         Buffers &b = buffers();
-        if (b.device >= 0) { int before = -1; (void)hipGetDevice(&before); if (hipSetDevice(b.device) == hipSuccess) b.release(); if (before >= 0) (void)hipSetDevice(before); b.device = -1; }
+        if (b.device >= 0) { QuietDeviceScope scope(b.device); if (scope.ok) b.release(); b.device = -1; }
         b.release_host();
         return;
     }
-    check_device(device);
+    check_device("ps_bgzf", device);
     g_device = device;
     bgzf_set_device_compressor(&device_batch);
 }
@@ -126,7 +120,7 @@ static void compress_rounds(const BgzfSpan *spans, size_t n_spans, const uint8_t
         const double ms_lock = ms_since(t_ask);
         const HostClock::time_point t_begin = HostClock::now();
         double ms_device = 0;                       // first upload to last byte down, summed over the rounds
-        check_device(device);
+        check_device("ps_bgzf", device);
         DeviceScope scope(device);
         Buffers &b = buffers();
         if (b.device != device) { b.release(); b.device = device; }
@@ -178,13 +172,8 @@ static void compress_rounds(const BgzfSpan *spans, size_t n_spans, const uint8_t
             ranges(nb, bytes >= ((size_t)4 << 20) ? 8 : 1, [&](size_t k0, size_t k1) {
                 for (size_t k = k0; k < k1; ++k) {
                     const DfResult &r = h_res[k];
-                    const uint32_t n = (uint32_t)n_of(r0 + k), total = 18 + r.bytes + 8;
-                    const unsigned char head[18] = {31, 139, 8, 4, 0, 0, 0, 0, 0, 255, 6, 0, 'B', 'C', 2, 0, (unsigned char)((total - 1) & 0xff), (unsigned char)((total - 1) >> 8)};
-                    unsigned char tail[8];
-                    for (int j = 0; j < 4; ++j) { tail[j] = (unsigned char)(r.crc >> (8 * j)); tail[4 + j] = (unsigned char)(n >> (8 * j)); }
-                    std::string &o = comp[r0 + k];
-                    o.clear(); o.reserve(total);
-                    o.append((const char *)head, 18); o.append((const char *)h_out + h_offs[k], r.bytes); o.append((const char *)tail, 8);
+                    comp[r0 + k].clear();
+                    bgzf_member(h_out + h_offs[k], r.bytes, r.crc, (uint32_t)n_of(r0 + k), comp[r0 + k]);
                 }
             });
             for (size_t k = 0; k < nb; ++k) {

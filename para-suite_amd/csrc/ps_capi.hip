@@ -568,9 +568,8 @@ int ps_bgzf_compress(const void *src, uint64_t n, int device, void *dst, uint64_
     PS_TRY
         if (stats && stats->struct_size < sizeof(ps_bgzf_stats)) throw Error("ps_bgzf_compress: stats->struct_size is not sizeof(ps_bgzf_stats)");
         if (n && (!src || !dst)) throw Error("ps_bgzf_compress: source and destination are required");
-        const size_t BLK = 0xff00;
         std::vector<BgzfSpan> spans;
-        for (uint64_t at = 0; at < n; at += BLK) spans.push_back(BgzfSpan{(const char *)src + at, (size_t)std::min<uint64_t>(BLK, n - at)});
+        bgzf_cut((const char *)src, (size_t)n, spans);
         std::vector<std::string> comp(spans.size());
         BgzfStats s;
         if (device >= 0) bgzf_device_compress(spans.data(), spans.size(), device, comp.data(), &s);
@@ -637,48 +636,14 @@ int64_t ps_batch_bam_records(ps_batch *b, int min_mapq, int on_device, int threa
         return (int64_t)st.bytes;
     } catch (const std::exception &e) { fail(e.what()); return -1; } catch (...) { fail("unknown error"); return -1; }
 }
+}  // extern "C"
+static const char *stats_name(const ps_bam_sort_stats *) { return "ps_bam_sort_stats"; }
+static const char *stats_name(const ps_bam_name_sort_stats *) { return "ps_bam_name_sort_stats"; }
 static void put(ps_bam_sort_stats *o, const BamSortStats &s)
 {
     if (!o) return;
     o->on_device = s.on_device; o->n_records = s.n_records; o->bytes = s.bytes; o->n_calls_device = s.n_calls_device; o->n_calls_host = s.n_calls_host;
     o->n_resident = s.n_resident; o->ms_upload = s.ms_upload; o->ms_sort = s.ms_sort; o->ms_gather = s.ms_gather; o->ms_download = s.ms_download;
-}
-int ps_bam_sort_device(int device) { PS_TRY bam_sort_set_device(device < 0 ? -1 : device); return 0; PS_CATCH_INT }
-int ps_bam_sort_info(ps_bam_sort_stats *out)
-{
-    PS_TRY
-        if (!out) throw Error("ps_bam_sort_info: no place for the result");
-        BamSortStats s; bam_sort_info(s);
-        out->struct_size = sizeof(ps_bam_sort_stats); put(out, s); return 0;
-    PS_CATCH_INT
-}
-int64_t ps_bam_sort_records(const void *records, uint64_t n_bytes, int device, int threads, void *dst, uint64_t cap, ps_bam_sort_stats *stats)
-{
-    try {
-        if (stats && stats->struct_size < sizeof(ps_bam_sort_stats)) throw Error("ps_bam_sort_records: stats->struct_size is not sizeof(ps_bam_sort_stats)");
-        BamSortStats st;
-        if (n_bytes == 0) { put(stats, st); return 0; }
-        if (!records || !dst) throw Error("ps_bam_sort_records: records and destination are required");
-        std::vector<BamRec> recs;
-        try { scan_records((const char *)records, n_bytes, recs); } catch (const Error &e) { throw Error(std::string("ps_bam_sort_records: ") + e.what()); }
-        if (n_bytes > cap) throw Error("ps_bam_sort_records: the records take " + std::to_string(n_bytes) + " bytes, the destination holds " + std::to_string(cap));
-        if (device >= 0) {
-            require_device(device);
-            const BgzfSpan part{(const char *)records, (size_t)n_bytes};
-            std::vector<uint32_t> perm; std::string stream;
-            BamSortJob job{&part, 1, recs.data(), recs.size(), &perm, &stream};
-            if (!bam_sort_device_run(job, device, &st)) throw Error("ps_bam_sort_records: the records need more device memory than PS_BAM_SORT_MAX_MB allows, or there are 2^32 of them or more");
-            if (stream.size() != n_bytes) throw Error("ps_bam_sort_records: the sorted stream has not the records' size");
-            std::memcpy(dst, stream.data(), stream.size());
-        } else {
-            const auto t0 = std::chrono::steady_clock::now();
-            sort_records_host((const char *)records, recs, threads, (char *)dst);       // nothing in it fails once the records are scanned
-            st.ms_sort = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-            st.n_calls_host = 1; st.n_records = recs.size(); st.bytes = n_bytes;
-        }
-        put(stats, st);
-        return (int64_t)n_bytes;
-    } catch (const std::exception &e) { fail(e.what()); return -1; } catch (...) { fail("unknown error"); return -1; }
 }
 static void put(ps_bam_name_sort_stats *o, const BamNameSortStats &s)
 {
@@ -687,47 +652,63 @@ static void put(ps_bam_name_sort_stats *o, const BamNameSortStats &s)
     o->n_resident = s.n_resident; o->key_words = s.key_words; o->pad_ = 0; o->n_passes = s.n_passes;
     o->ms_upload = s.ms_upload; o->ms_keys = s.ms_keys; o->ms_sort = s.ms_sort; o->ms_gather = s.ms_gather; o->ms_download = s.ms_download;
 }
-int ps_bam_name_sort_device(int device) { PS_TRY bam_name_sort_set_device(device < 0 ? -1 : device); return 0; PS_CATCH_INT }
-int ps_bam_name_sort_info(ps_bam_name_sort_stats *out)
+// The two orders' entries are one body: `who` is the entry's name in every message, Out / Stats the public struct and the library's,
+// check the look at every scanned record that the order asks for (null: none; it returns what is wrong with the record), run and
+// host the device route and the host route.
+template <class Out, class Stats> static int sort_info(const char *who, Out *out, void (*info)(Stats &))
 {
     PS_TRY
-        if (!out) throw Error("ps_bam_name_sort_info: no place for the result");
-        BamNameSortStats s; bam_name_sort_info(s);
-        out->struct_size = sizeof(ps_bam_name_sort_stats); put(out, s); return 0;
+        if (!out) throw Error(std::string(who) + ": no place for the result");
+        Stats s; info(s);
+        out->struct_size = sizeof(Out); put(out, s); return 0;
     PS_CATCH_INT
 }
-int64_t ps_bam_name_sort_records(const void *records, uint64_t n_bytes, int device, int threads, void *dst, uint64_t cap, ps_bam_name_sort_stats *stats)
+template <class Out, class Stats>
+static int64_t sort_records_entry(const char *who, const void *records, uint64_t n_bytes, int device, int threads, void *dst, uint64_t cap, Out *stats,
+                                  const char *(*check)(const uint8_t *rec, size_t len), bool (*run)(BamSortJob &, int, Stats *), void (*host)(const char *, std::vector<BamRec> &, int, char *))
 {
     try {
-        if (stats && stats->struct_size < sizeof(ps_bam_name_sort_stats)) throw Error("ps_bam_name_sort_records: stats->struct_size is not sizeof(ps_bam_name_sort_stats)");
-        BamNameSortStats st;
+        const std::string name = std::string(who) + ": ";
+        if (stats && stats->struct_size < sizeof(Out)) throw Error(name + "stats->struct_size is not sizeof(" + stats_name(stats) + ")");
+        Stats st;
         if (n_bytes == 0) { put(stats, st); return 0; }
-        if (!records || !dst) throw Error("ps_bam_name_sort_records: records and destination are required");
+        if (!records || !dst) throw Error(name + "records and destination are required");
         std::vector<BamRec> recs;
-        try { scan_records((const char *)records, n_bytes, recs); } catch (const Error &e) { throw Error(std::string("ps_bam_name_sort_records: ") + e.what()); }
-        for (size_t i = 0; i < recs.size(); ++i) {              // l_read_name at byte 12 counts the NUL that ends the name at byte 36 + l_read_name - 1
-            const uint8_t *p = (const uint8_t *)records + recs[i].off;
-            if (recs[i].len < 37 || p[12] < 1 || 36 + (size_t)p[12] > recs[i].len || p[36 + p[12] - 1] != 0)
-                throw Error("ps_bam_name_sort_records: record " + std::to_string(i + 1) + " has a name that does not end inside it");
-        }
-        if (n_bytes > cap) throw Error("ps_bam_name_sort_records: the records take " + std::to_string(n_bytes) + " bytes, the destination holds " + std::to_string(cap));
+        try { scan_records((const char *)records, n_bytes, recs); } catch (const Error &e) { throw Error(name + e.what()); }
+        for (size_t i = 0; check && i < recs.size(); ++i)
+            if (const char *why = check((const uint8_t *)records + recs[i].off, recs[i].len)) throw Error(name + "record " + std::to_string(i + 1) + " " + why);
+        if (n_bytes > cap) throw Error(name + "the records take " + std::to_string(n_bytes) + " bytes, the destination holds " + std::to_string(cap));
         if (device >= 0) {
             require_device(device);
             const BgzfSpan part{(const char *)records, (size_t)n_bytes};
-            std::vector<uint32_t> perm; std::string stream;
-            BamSortJob job{&part, 1, recs.data(), recs.size(), &perm, &stream};
-            if (!bam_name_sort_device_run(job, device, &st)) throw Error("ps_bam_name_sort_records: the records need more device memory than PS_BAM_SORT_MAX_MB allows, or there are 2^32 of them or more");
-            if (stream.size() != n_bytes) throw Error("ps_bam_name_sort_records: the sorted stream has not the records' size");
-            std::memcpy(dst, stream.data(), stream.size());
+            std::vector<uint32_t> perm; BamBody body;
+            BamSortJob job{&part, 1, recs.data(), recs.size(), &perm, &body};
+            if (!run(job, device, &st)) throw Error(name + "the records need more device memory than PS_BAM_SORT_MAX_MB allows, or there are 2^32 of them or more");
+            if (body.host.size() != n_bytes) throw Error(name + "the sorted stream has not the records' size");
+            std::memcpy(dst, body.host.data(), body.host.size());
         } else {
             const auto t0 = std::chrono::steady_clock::now();
-            sort_records_host_by_name((const char *)records, recs, threads, (char *)dst);   // nothing in it fails once the records are scanned
+            host((const char *)records, recs, threads, (char *)dst);                    // nothing in it fails once the records are scanned
             st.ms_sort = 1e3 * std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
             st.n_calls_host = 1; st.n_records = recs.size(); st.bytes = n_bytes;
         }
         put(stats, st);
         return (int64_t)n_bytes;
     } catch (const std::exception &e) { fail(e.what()); return -1; } catch (...) { fail("unknown error"); return -1; }
+}
+static const char *name_check(const uint8_t *rec, size_t len) { return name_ends_inside(rec, len) ? nullptr : "has a name that does not end inside it"; }
+extern "C" {
+int ps_bam_sort_device(int device) { PS_TRY bam_sort_set_device(device < 0 ? -1 : device); return 0; PS_CATCH_INT }
+int ps_bam_sort_info(ps_bam_sort_stats *out) { return sort_info("ps_bam_sort_info", out, &bam_sort_info); }
+int64_t ps_bam_sort_records(const void *records, uint64_t n_bytes, int device, int threads, void *dst, uint64_t cap, ps_bam_sort_stats *stats)
+{
+    return sort_records_entry("ps_bam_sort_records", records, n_bytes, device, threads, dst, cap, stats, nullptr, &bam_sort_device_run, &sort_records_host);
+}
+int ps_bam_name_sort_device(int device) { PS_TRY bam_name_sort_set_device(device < 0 ? -1 : device); return 0; PS_CATCH_INT }
+int ps_bam_name_sort_info(ps_bam_name_sort_stats *out) { return sort_info("ps_bam_name_sort_info", out, &bam_name_sort_info); }
+int64_t ps_bam_name_sort_records(const void *records, uint64_t n_bytes, int device, int threads, void *dst, uint64_t cap, ps_bam_name_sort_stats *stats)
+{
+    return sort_records_entry("ps_bam_name_sort_records", records, n_bytes, device, threads, dst, cap, stats, &name_check, &bam_name_sort_device_run, &sort_records_host_by_name);
 }
 int ps_sam_to_bam(const char *sam, const char *bam, int min_mapq, int sort_by_coordinate, int write_index, int threads, ps_bam_stats *st)
 {

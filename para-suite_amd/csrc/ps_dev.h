@@ -42,6 +42,18 @@ struct DeviceScope {                                // the calling thread's devi
     DeviceScope(const DeviceScope &) = delete;
     ~DeviceScope() { if (before >= 0) (void)hipSetDevice(before); }
 };
+struct QuietDeviceScope {                           // the same where the caller must not throw (a destructor, a switch that goes off): ok says whether the device is set
+    int before = -1; bool ok = false;
+    explicit QuietDeviceScope(int device) noexcept { (void)hipGetDevice(&before); ok = hipSetDevice(device) == hipSuccess; }
+    QuietDeviceScope(const QuietDeviceScope &) = delete;
+    ~QuietDeviceScope() { if (before >= 0) (void)hipSetDevice(before); }
+};
+inline void check_device(const char *who, int device)   // throws "<who>: no HIP device ..." unless `device` is one of those present
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(std::string(who) + ": no HIP device available");
+    if (device < 0 || device >= n) throw Error(std::string(who) + ": no HIP device " + std::to_string(device) + " (" + std::to_string(n) + " present)");
+}
 
 // f(begin, end) over [0, n) on up to `threads` threads
 template <class F> void ranges(size_t n, int threads, F f)

@@ -280,6 +280,40 @@ def test_the_resident_stream_in_more_than_one_round(mapped, monkeypatch):
         _same_files(alone, both, tag)
 
 
+def test_the_device_buffer_changes_owner_twice(mapped):
+    """the stream's buffer leaves the sort's set for the body of a file and comes back, across a switch that goes off and on: a
+    resident write, the sort's switch off (its buffers are given back) and on, a second resident write, then the compressor's switch
+    off and a third write, whose stream comes down.  Every file holds the host route's records, and its index says the same about them"""
+    import capi
+    d = mapped["dir"]
+    write = lambda p: capi.ps_sam_to_bam(mapped["sam"], p, sort_by_coordinate=True, write_index=True, threads=4)
+    host, first, second, third = (os.path.join(d, "owner.%s.bam" % t) for t in ("host", "first", "second", "third"))
+    st_host = write(host)
+    assert capi.ps_bam_sort_info()["n_calls_device"] == 0
+    capi.ps_bgzf_device(0)
+    capi.ps_bam_sort_device(0)
+    st_first, info_first = write(first), capi.ps_bam_sort_info()
+    capi.ps_bam_sort_device(-1)
+    assert capi.ps_bam_sort_info()["on_device"] == 0
+    capi.ps_bam_sort_device(0)
+    assert capi.ps_bam_sort_info()["n_calls_device"] == 0                          # the counters start again with the switch
+    st_second, info_second = write(second), capi.ps_bam_sort_info()
+    capi.ps_bgzf_device(-1)
+    st_third, info_third = write(third), capi.ps_bam_sort_info()
+    capi.ps_bam_sort_device(-1)
+    counters = lambda i: (i["on_device"], i["n_calls_device"], i["n_calls_host"], i["n_resident"], i["n_records"])
+    assert counters(info_first) == (1, 1, 0, 1, 2000) and counters(info_second) == (1, 1, 0, 1, 2000)      # resident, resident
+    assert counters(info_third) == (1, 2, 0, 1, 4000)                                                      # and not resident
+    want, want_bai = open(host, "rb").read(), open(host + ".bai", "rb").read()
+    for path, st in ((first, st_first), (second, st_second)):
+        got = open(path, "rb").read()
+        assert got != want and gzip.decompress(got) == gzip.decompress(want), path
+        assert _bai_over_the_stream(open(path + ".bai", "rb").read(), got) == _bai_over_the_stream(want_bai, want), path
+        assert (st["n_in"], st["n_out"]) == (st_host["n_in"], st_host["n_out"]) == (2000, 2000)
+    _same_files(host, third, "third")                                              # zlib again: the host route's very files
+    assert st_third == st_host
+
+
 # ---------------------------------------------------------------- e: everything on at once
 _CHILD = """
 import json, sys

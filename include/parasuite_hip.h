@@ -189,6 +189,7 @@ int64_t ps_batch_alns(ps_batch *, int64_t read, ps_aln *out, int64_t cap);
 int     ps_batch_hits(ps_batch *, ps_hit *out, int64_t cap);
 int     ps_batch_timing(ps_batch *, ps_timing *out);
 int64_t ps_ctx_read_iters(ps_ctx *, uint32_t *out, int64_t cap);   /* profiling aid (env PS_READ_ITERS=1): per read of the last search launch 20 words -- iterations | stack slots used | lower bounds as fetched (read, seed << 8) and the effort estimate's two scans (<< 16, << 24) | best score, final budget << 8, hits << 16 | 16 words of D bounds -- in the order the launch held the reads (leading-base order of the bin, not input order); returns the word count */
+int64_t ps_ctx_launch_order(ps_ctx *, uint8_t *est, uint8_t *key, float *pred, int32_t *order, int32_t *ids, int64_t cap);   /* profiling aid (env PS_READ_ITERS=1): what the last search launch was prepared with, per read by the index ps_ctx_read_iters rows have -- the estimated best score in budget units, the 8-bit class the hand-out order sorts by, the expected number of search nodes it was made from (0 under PS_ORDER=2), queue position -> read, and read -> input read; null pointers are skipped; returns the number of reads, 0 where the launch made no order */
 int     ps_batch_kstats(ps_batch *, int which /*0 width 1 backtrack 2 sa2pos*/, ps_kstats *out);
 /* what the collapsed search (ps_ctx_set_collapse) found and saved, after ps_batch_search.  The groups are EXACT: two reads share a
  * group only after all their packed words and their length have compared equal, never on a hash alone.  They may be INCOMPLETE in

@@ -242,6 +242,7 @@ SIGNATURES = {
     "ps_batch_hits": (_I, [_PTR, _PTR, _I64]),
     "ps_batch_timing": (_I, [_PTR, _P(Timing)]),
     "ps_ctx_read_iters": (_I64, [_PTR, _PTR, _I64]),
+    "ps_ctx_launch_order": (_I64, [_PTR, _PTR, _PTR, _PTR, _PTR, _PTR, _I64]),
     "ps_batch_kstats": (_I, [_PTR, _I, _P(KStats)]),
     "ps_batch_collapse_info": (_I, [_PTR, _P(CollapseInfo)]),
     "ps_batch_duplicate_of": (_I, [_PTR, _PTR, _I64]),
@@ -482,6 +483,16 @@ class Ctx:
         n = lib().ps_ctx_read_iters(self.h, None, 0)
         out = np.zeros(n, dtype=np.uint32)
         lib().ps_ctx_read_iters(self.h, out.ctypes.data, n)
+        return out
+
+    def launch_order(self):
+        """what the last search launch was prepared with (PS_READ_ITERS=1), by the read index read_iters() rows have: dict(est, key,
+        pred, order, ids) -- estimated best score in budget units, the class the hand-out order sorts by, the model's expected node
+        count, queue position -> read, read -> input read; arrays of length 0 where the launch made no order"""
+        n = lib().ps_ctx_launch_order(self.h, None, None, None, None, None, 0)
+        out = dict(est=np.zeros(n, dtype=np.uint8), key=np.zeros(n, dtype=np.uint8), pred=np.zeros(n, dtype=np.float32),
+                   order=np.zeros(n, dtype=np.int32), ids=np.zeros(n, dtype=np.int32))
+        lib().ps_ctx_launch_order(self.h, *[out[k].ctypes.data for k in ("est", "key", "pred", "order", "ids")], n)
         return out
 
     def batch_from_fastq(self, path):

@@ -339,6 +339,19 @@ int64_t ps_ctx_read_iters(ps_ctx *x, uint32_t *out, int64_t cap)
     for (int64_t i = 0; i < n && i < cap; ++i) out[i] = x->c.read_iters[i];
     return n;
 }
+int64_t ps_ctx_launch_order(ps_ctx *x, uint8_t *est, uint8_t *key, float *pred, int32_t *order, int32_t *ids, int64_t cap)
+{
+    const Ctx::LaunchOrder &lo = x->c.launch_order;
+    const int64_t n = (int64_t)lo.order.size();
+    for (int64_t i = 0; i < n && i < cap; ++i) {
+        if (est) est[i] = lo.est[(size_t)i];
+        if (key) key[i] = lo.key[(size_t)i];
+        if (pred) pred[i] = lo.pred[(size_t)i];
+        if (order) order[i] = lo.order[(size_t)i];
+        if (ids) ids[i] = lo.ids[(size_t)i];
+    }
+    return n;
+}
 int ps_batch_timing(ps_batch *b, ps_timing *o)
 {
     PS_TRY

@@ -82,6 +82,8 @@ struct Ctx : OptionParts {          // opt, search: the options in their two par
                                    // hit many places by chance -- 1.7 % of 18-40 bp reads list more than 8 intervals, 0.3 % more than 32; 0 = as aln_cap[0]
     bool want_kstats = false;      // search kernel with counters (KStats of the backtracking stage): measurement runs only
     bool want_read_iters = false; std::vector<uint32_t> read_iters;   // profiling aid: last launch's per-read profile (ps_types.h: BtArgs::read_iters), PS_RI_WORDS words per read, in the order the launch held the reads (a bin's leading-base order)
+    // ... and, in the same mode, what that launch was prepared with (ps_search.hip: search_order), by the same read index; empty where the launch made no order
+    struct LaunchOrder { std::vector<uint8_t> est, key; std::vector<float> pred; std::vector<int32_t> order, ids; void clear() { est.clear(); key.clear(); pred.clear(); order.clear(); ids.clear(); } } launch_order;
     int n_big = 4096;              // 1 MB stack slots a launch may hand to reads that outgrow their private slice
     int fetch_min = 8, hit_min = 1;    // batching hits costs more in idle lanes than it saves (measured)
     int host_threads = 8;

@@ -50,8 +50,9 @@ static void search_width(Batch &b, BtArgs &a, EventPair &t)
 // them.  PS_ORDER=0 switches it off, 2 orders by the estimated best score alone (A/B runs).  Narrow launches only: the wide
 // stack takes its reads in queue order and never reads the estimate (its budget can also pass the 63 units k_effort_model
 // has lanes for: -X 10 and up).  Sets a.order, a.est, a.est_ab, which stay null where there is no order (queue position == read);
-// t: started here if there is one to make
-static void search_order(Batch &b, BtArgs &a, const SearchKnobs &kn, std::optional<EventPair> &t)
+// t: started here if there is one to make.  ob: the key the sort took and the model's number (profiling mode only: Ctx::launch_order)
+struct OrderBufs { const uint8_t *key = nullptr; const float *pred = nullptr; };
+static void search_order(Batch &b, BtArgs &a, const SearchKnobs &kn, std::optional<EventPair> &t, OrderBufs &ob)
 {
     Ctx *ctx = b.ctx; Work *wk = b.wk; hipStream_t s = wk->stream;
     const Model &md = a.md; const int n = a.n_reads;
@@ -80,15 +81,16 @@ static void search_order(Batch &b, BtArgs &a, const SearchKnobs &kn, std::option
         em.seed_units = md.max_seed_diff * md.u_tight; em.use_seed = md.use_seed; em.seed_len = md.seed_len;
         em.max_gapo = md.max_gapo; em.indel_end_skip = md.indel_end_skip; em.u_gapo_ins = md.u_gapo_ins; em.u_gapo_del = md.u_gapo_del;
         em.depth = lv + 3; em.rows = (float)a.ix.seq_len; em.log_scale = kn.order_scale;
-        em.key = key; em.pred = nullptr;
+        em.key = key; em.pred = ctx->want_read_iters ? wk->ws_get<float>("pred", (size_t)n) : nullptr;      // profiling only: the timed launch writes no number
         launch_effort_model(em, s);
+        ob.pred = em.pred;
     }
     // stable: the given (leading-base) order inside a class.  A counting sort of our own: the library's radix sort kernels (20 KB
     // of LDS, 100 VGPRs) do not start beside the other batch's resident search launch (ps_budget.h)
     launch_order_sort(key, n, wk->ws_get<uint32_t>("order_tmp", order_sort_tmp_words(n)), order, s);
     PS_HIP(hipGetLastError());
     t->stop(s);
-    a.order = order; a.est = est; a.est_ab = ea.est_ab;
+    a.order = order; a.est = est; a.est_ab = ea.est_ab; ob.key = key;
 }
 
 // ragged launch: every read's own budget, by its length -- one table for the order's model and the search
@@ -122,7 +124,7 @@ static SearchPlan search_stacks(Batch &b, BtArgs &a, const SearchKnobs &kn, int 
 
 // width + backtracking kernels over n reads of one length that are already packed on the device
 static void run_search(Batch &b, const SearchKnobs &kn, const Model &md, int n, const uint32_t *d_bases, const uint32_t *d_nmask, const int32_t *d_lens,
-                       uint32_t pool_cap, int aln_cap, AlnRec *alns, int32_t *n_aln, uint8_t *status, bool first_tier = false)
+                       uint32_t pool_cap, int aln_cap, AlnRec *alns, int32_t *n_aln, uint8_t *status, bool first_tier = false, const int32_t *launch_ids = nullptr)
 {
     Ctx *ctx = b.ctx; Work *wk = b.wk; hipStream_t s = wk->stream;
     const int len = md.len;
@@ -138,7 +140,8 @@ static void run_search(Batch &b, const SearchKnobs &kn, const Model &md, int n, 
     EventPair t_width; std::optional<EventPair> t_order;
     search_width(b, a, t_width);
     if (d_lens) a.units_by_len = upload_units_by_len(b);
-    search_order(b, a, kn, t_order);
+    OrderBufs ob;
+    search_order(b, a, kn, t_order, ob);
     // the estimate also spares the search entries (ps_narrow.h, nt_tail): first tier and profile costs only (units == score); a read it fails on starts over without it inside the launch
     a.cap_est = (first_tier && !wide && a.est && md.profile && kn.cap) ? 1 + kn.cap_bias : 0;
     const int lm = lm_bytes(len, md.seed_len, md.n_buckets, wide);
@@ -154,7 +157,21 @@ static void run_search(Batch &b, const SearchKnobs &kn, const Model &md, int n, 
     if (t_order) b.tm.ms_width += t_order->ms();                     // reported with the width stage: both prepare the search
     { double t0_ = 0, t1_ = 0; t.span(ctx->ref_event, t0_, t1_); if (b.tm.n_backtrack_launches == 1) b.tm.bt_begin_ms = t0_; b.tm.bt_end_ms = t1_; }
     if (std::getenv("PS_VERBOSE")) std::fprintf(stderr, "[parasuite-hip]   backtrack launch: %d reads x %d bp, stack %u%s, %d lanes, %.1f ms\n", n, len, pool_cap, wide ? " (wide)" : "", p.lanes, ms);
-    if (ctx->want_read_iters) { ctx->read_iters.resize((size_t)n * PS_RI_WORDS); PS_HIP(hipMemcpyAsync(ctx->read_iters.data(), a.read_iters, (size_t)n * PS_RI_WORDS * 4, hipMemcpyDeviceToHost, s)); PS_HIP(hipStreamSynchronize(s)); }
+    if (ctx->want_read_iters) {
+        ctx->read_iters.resize((size_t)n * PS_RI_WORDS); PS_HIP(hipMemcpyAsync(ctx->read_iters.data(), a.read_iters, (size_t)n * PS_RI_WORDS * 4, hipMemcpyDeviceToHost, s));
+        // what the launch was prepared with (ps_ctx_launch_order): nothing where it made no order
+        Ctx::LaunchOrder &lo = ctx->launch_order;
+        lo.clear();
+        if (a.order) {
+            lo.est.resize((size_t)n); lo.key.resize((size_t)n); lo.pred.assign((size_t)n, 0.f); lo.order.resize((size_t)n); lo.ids.resize((size_t)n);
+            PS_HIP(hipMemcpyAsync(lo.est.data(), a.est, (size_t)n, hipMemcpyDeviceToHost, s));
+            PS_HIP(hipMemcpyAsync(lo.key.data(), ob.key, (size_t)n, hipMemcpyDeviceToHost, s));
+            if (ob.pred) PS_HIP(hipMemcpyAsync(lo.pred.data(), ob.pred, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+            PS_HIP(hipMemcpyAsync(lo.order.data(), a.order, (size_t)n * 4, hipMemcpyDeviceToHost, s));
+            for (int r = 0; r < n; ++r) lo.ids[(size_t)r] = launch_ids ? launch_ids[r] : r;
+        }
+        PS_HIP(hipStreamSynchronize(s));
+    }
 }
 
 // download the hit lists of n reads (stride aln_cap on the device) in compact form
@@ -304,7 +321,7 @@ static void search_bin(Batch &b, const SearchKnobs &kn, Bin &bin)
     if (bin.d_alns.n < (size_t)n * cap1 || bin.aln_cap != cap1) { bin.d_alns.alloc((size_t)n * cap1); bin.d_n_aln.alloc(n); bin.d_status.alloc(n); }
     bin.aln_cap = cap1;
     if (!b.collapse_on || !search_bin_collapsed(b, kn, bin))
-        run_search(b, kn, bin.md, n, bin.bases.p, bin.nmask.p, bin.ragged ? bin.d_lens.p : nullptr, ctx->pool_cap[0], bin.aln_cap, bin.d_alns.p, bin.d_n_aln.p, bin.d_status.p, true);
+        run_search(b, kn, bin.md, n, bin.bases.p, bin.nmask.p, bin.ragged ? bin.d_lens.p : nullptr, ctx->pool_cap[0], bin.aln_cap, bin.d_alns.p, bin.d_n_aln.p, bin.d_status.p, true, bin.ids.data());
     // collapsed: the larger tiers search the representatives alone -- a read whose search overflowed is the dearest kind, and all its
     // duplicates overflow with it -- and a group's members take the representative's list afterwards; size[rep]: reads it stands for
     const std::vector<int32_t> &rep_of = bin.h_rep_of;
@@ -343,7 +360,9 @@ static void search_bin(Batch &b, const SearchKnobs &kn, Bin &bin)
         if (bin.ragged) { for (int q = 0; q < m; ++q) hl[q] = bin.lens[todo[q]]; dl.alloc(m); dl.upload(hl.data(), m, s); }
         DevBuf<AlnRec> ta; DevBuf<int32_t> tn; DevBuf<uint8_t> ts;
         ta.alloc((size_t)m * ctx->aln_cap[tier]); tn.alloc(m); ts.alloc(m);
-        run_search(b, kn, bin.md, m, db.p, dm.p, bin.ragged ? dl.p : nullptr, ctx->pool_cap[tier], ctx->aln_cap[tier], ta.p, tn.p, ts.p);
+        std::vector<int32_t> tid;
+        if (ctx->want_read_iters) { tid.resize((size_t)m); for (int q = 0; q < m; ++q) tid[(size_t)q] = bin.ids[(size_t)todo[q]]; }
+        run_search(b, kn, bin.md, m, db.p, dm.p, bin.ragged ? dl.p : nullptr, ctx->pool_cap[tier], ctx->aln_cap[tier], ta.p, tn.p, ts.p, false, tid.empty() ? nullptr : tid.data());
         std::vector<uint8_t> st(m); ts.download(st.data(), m, s);
         std::vector<int32_t> na; std::vector<uint32_t> off; std::vector<AlnRec> al;
         download_alns(wk, m, ctx->aln_cap[tier], ta.p, tn.p, na, off, al);

@@ -247,7 +247,8 @@ int     ps_bam_index(const char *bam, int threads);
  *   <out_prefix>.errorprofile  4 lines x 4 values, row = reference base, each Double.toString + TAB (NaN if never seen), :504-531
  *   <out_prefix>.indelprofile  "<ins>\t<del>" without newline, :545-591
  * out_prefix NULL or "": the mapping file's name, as in the Java.  A read longer than max_read_len is an error (the
- * Java's arrays would overflow). */
+ * Java's arrays would overflow).  max_read_len 1..2275 (the counting kernel's LDS, 160 KiB at 18 words per position); the
+ * same range holds for ps_map_profiled and for max_read_len of ps_route_opts.  Outside it the call fails and writes nothing. */
 int     ps_error_profile(const char *mapping_sam_or_bam, const char *ref_fa, int max_read_len, const char *out_prefix);
 /* Everything `new ErrorProfiling(mapping, reference, maxReadLength).inferErrorProfile(infer_qualities, false)` writes -- the
  * toolkit's `error MAPPING REF MAXLEN [-q true]` mode (Main.java:560-597), whose .qualities and .indels feed the PAR-CLIP
@@ -288,7 +289,8 @@ int     ps_error_profile_full(const char *mapping_sam_or_bam, const char *ref_fa
  *                                   twice, as in the Java)
  *   <site_prefix>.sitepositions.tsv per read index 0..50 the share of crosslinked clusters with a T->C there (NaN for none)
  * The input must be coordinate-sorted by its header (@HD SO:coordinate); records with flag 4 are skipped, records whose
- * CIGAR holds (I or D) and N are skipped and counted, and the last cluster is never written (all as in the Java).
+ * CIGAR holds (I or D) and N are skipped and counted, and the last cluster is never written (all as in the Java).  Only the
+ * header is checked: records that are locally out of order under it are clustered in file order, as the Java would.
  * site_prefix NULL or "": the mapping file's name.  snp_vcf NULL or "": no known SNPs (an extension); the VCF is read whole
  * (plain, gzip or BGZF), so no .tbi is needed.  ref_fa needs its index (.ann/.pac, ps_index); sequence text comes from the
  * FASTA itself, which may be plain, gzip or BGZF like ps_index's (the same string serves both; the index is named after it as

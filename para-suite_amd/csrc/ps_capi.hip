@@ -421,7 +421,7 @@ int ps_map_profiled(int threads, const char *mm, const char *error_profile, cons
 {
     PS_TRY
         if (!profile_prefix || !profile_prefix[0]) throw Error("ps_map_profiled: no output prefix for the profile files");
-        if (max_read_len < 1 || max_read_len > 4096) throw Error("error profile: maximum read length out of range");
+        profile_check_max_len(max_read_len, 0);
         map_profiled(MapArgs{threads, mm, error_profile, indel_profile, ref_fa, fastq}, out_sam, min_mapq, max_read_len, profile_prefix); return 0;
     PS_CATCH_INT
 }

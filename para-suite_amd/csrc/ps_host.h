@@ -116,9 +116,11 @@ public:
 private:
     struct Impl; Impl *p;
 };
-// largest max_len of the quality passes, from the counting kernel's LDS (160 KiB per workgroup): 18 words per position + 1.5 KiB
-// for quals == 1 (2254), 20 words per position + 1.5 KiB for quals == 2 (2028); ps_error_profile's own kernel stops at 2275
+// largest max_len of each pass, from the counting kernel's LDS (160 KiB per workgroup): 18 words per position for quals == 0
+// (2275: ps_error_profile, ps_map_profiled, the route), 18 words per position + 1.5 KiB for quals == 1 (2254), 20 words per
+// position + 1.5 KiB for quals == 2 (2028).  profile_check_max_len throws the range error of every entry point.
 int profile_max_len(int quals);
+void profile_check_max_len(int max_len, int quals);
 void error_profile_count(const char *mapping_sam_or_bam, const char *ref_prefix, int max_len, int device, int threads, ProfileCounts &out,
                          int quals = 0, double *ms_parse = nullptr);
 void error_profile_write(const ProfileCounts &c, const std::string &out_prefix);    // <out_prefix>.errorprofile / .indelprofile

@@ -677,7 +677,7 @@ void route_run(const ps_route_opts2 &o, const std::string &who, ps_route_stats *
     const int threads = o.threads > 0 ? o.threads : 1, max_len = o.max_read_len > 0 ? o.max_read_len : 101;
     const int gm = o.mapq_genomic > 0 ? o.mapq_genomic : 10, tm = o.mapq_transcript > 0 ? o.mapq_transcript : 1;
     const char *bwa_mm = has(o.bwa_mm) ? o.bwa_mm : "2", *para_mm = has(o.parasuite_mm) ? o.parasuite_mm : "-1";
-    if (max_len > 4096) throw Error(who + "maximum read length out of range");
+    if (max_len > profile_max_len(0)) throw Error(who + "maximum read length out of range (1.." + std::to_string(profile_max_len(0)) + ")");
     const bool first_pass = !given;
     if (o.search) {                        // a stock pass runs iff there is a first pass, a profile pass iff refine
         std::string err;

@@ -242,10 +242,16 @@ static size_t prof_acc_words(int max_len, int quals)
 {
     return (size_t)max_len * 18 + 4 + (quals >= 1 ? 2 + 32 : 0) + (quals == 2 ? (size_t)max_len * 2 : 0);
 }
+// the one range check of every entry: 1..profile_max_len(quals), so a length that passes it never fails later on LDS bytes
+void profile_check_max_len(int max_len, int quals)
+{
+    if (quals < 0 || quals > 2) throw Error("error profile: quality mode out of range");
+    if (max_len < 1 || max_len > profile_max_len(quals))
+        throw Error(std::string("error profile: maximum read length out of range") + (quals ? " for the quality files" : "") + " (1.." + std::to_string(profile_max_len(quals)) + ")");
+}
 ProfileAccum::ProfileAccum(int device, const Index &ix, int max_len, int quals)
 {
-    if (max_len < 1 || max_len > 4096) throw Error("error profile: maximum read length out of range");
-    if (quals < 0 || quals > 2 || (quals && max_len > profile_max_len(quals))) throw Error("error profile: maximum read length out of range for the quality files (1.." + std::to_string(profile_max_len(quals)) + ")");
+    profile_check_max_len(max_len, quals);
     require_device(device);
     std::unique_ptr<Impl> q(new Impl());
     q->device = device; q->max_len = max_len; q->quals = quals; q->pac = ix.pac.p;
@@ -329,8 +335,7 @@ void ProfileAccum::finish(ProfileCounts &out)
 
 void error_profile_count(const char *mapping, const char *ref_prefix, int max_len, int device, int threads, ProfileCounts &out, int quals, double *ms_parse)
 {
-    if (max_len < 1 || max_len > 4096) throw Error("error profile: maximum read length out of range");
-    if (quals && max_len > profile_max_len(quals)) throw Error("error profile: maximum read length out of range for the quality files (1.." + std::to_string(profile_max_len(quals)) + ")");
+    profile_check_max_len(max_len, quals);
     require_device(device);
     ProfRecords r;
     const auto t0 = HostClock::now();

@@ -56,6 +56,13 @@ def _revcomp(a):                               # htsjdk SequenceUtil.reverseComp
 
 def infer(sam_text, ref, max_read_len, infer_qualities):
     """(files, stats): files maps each suffix of FILES to the bytes the library writes; ref = read_fasta(...)"""
+    c = counts(sam_text, ref, max_read_len, infer_qualities)
+    return render(c, max_read_len, infer_qualities), c["st"]
+
+
+def counts(sam_text, ref, max_read_len, infer_qualities):
+    """the counting loop (:145-409): everything the six files are written from, as a dict.  All of it but the quality
+    lists is a sum over the records, so the counts of a concatenation are the sums of its parts' counts"""
     ML = max_read_len
     conv = [[[0] * 4 for _ in range(4)] for _ in range(ML)]
     ins, dele = [0.0] * ML, [0.0] * ML
@@ -151,6 +158,13 @@ def infer(sam_text, ref, max_read_len, infer_qualities):
                         st["n_qual_beyond_read"] += 1
             if infer_qualities and has_q and i < len(quals):
                 qlists[i].append(quals[i])
+    return dict(conv=conv, ins=ins, dele=dele, qpm_sum=qpm_sum, qpm_cnt=qpm_cnt, qlists=qlists, st=st)
+
+
+def render(c, max_read_len, infer_qualities):
+    """the six files (:421-591) of the counts"""
+    ML = max_read_len
+    conv, ins, dele, qpm_sum, qpm_cnt, qlists = (c[k] for k in ("conv", "ins", "dele", "qpm_sum", "qpm_cnt", "qlists"))
     jd = orc.java_double
     tot, base, per_pos = [[0.0] * 4 for _ in range(4)], [0.0] * 4, [0.0] * ML
     for i in range(ML):
@@ -205,7 +219,7 @@ def infer(sam_text, ref, max_read_len, infer_qualities):
             qualities += jd(mean) + "\t" + jd(math.sqrt(div(ssd, n))) + "\n"
     files = {".errorprofile": ep, ".indelprofile": jd(ins_all) + "\t" + jd(del_all), ".errorprofile.vcf": vcf,
              ".qualityPerMismatch": qpm, ".indels": indels, ".qualities": qualities}
-    return {k: v.encode() for k, v in files.items()}, st
+    return {k: v.encode() for k, v in files.items()}
 
 
 def infer_files(sam_path, fasta_path, max_read_len, infer_qualities):

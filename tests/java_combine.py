@@ -52,7 +52,7 @@ def parse_sam(text):
             pos = int(f[3]) - 1
             recs.append(dict(name=f[0], flag=int(f[1]), ref=ref, pos=pos, mapq=int(f[4]), bin=reg2bin(pos, pos + (ref_length(f[5]) or 1)),
                              nref=ref if f[6] == "=" else -1 if f[6] == "*" else ids[f[6]], npos=int(f[7]) - 1, tlen=int(f[8]),
-                             cigar=f[5], seq=seq, qual=f[10], tags=f[11:]))
+                             cigar=f[5], seq=seq, qual="" if seq == "*" else f[10], tags=f[11:]))   # no SEQ: BAM holds no QUAL byte
     return "".join(head), refs, recs
 
 
